@@ -11,9 +11,15 @@ order to rank 0 over RCCL inside the timed step (the in-order write-out exchange
     python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 launches itself under
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   torch.distributed.run)
 
-The same JSON line carries, measured in the same run after the headline region (N = 1):
+A plain run sets up, warms up, times the K steps and prints the headline line; nothing else.
+--dump-outputs DIR writes what the last timed step produced as DIR/*.npy (see dump_outputs).
+--full adds everything else, measured in the same run after the headline region: the stage
+times and roofline, the stream's checks against the oracle and the libdeflate-made digest, and
+(N = 1)
     "e2e"      host-to-host rates: pinned submit/wait pipeline, and the Write API (ParCompress twin)
     "inflate"  the ParDecompress row (BASELINE configs[4]) over the stream just produced
+    "levels" / "mgzip3" / "cpu_baseline*"   the other levels, configs[2] and the CPU baselines
+or (N > 1) the other in-order write-outs and the strong-scaling leg.
 Other workloads: --workload inflate (configs[4] alone), --workload fastq (configs[3]: a 32 GiB
 synthetic FASTQ stream generated in HBM, sharded over the ranks).
 """
@@ -136,6 +142,33 @@ def check_full_stream(name, n, seed, out_host, block_sizes=None):
     if ok and block_sizes is not None:
         ok = hashlib.sha256(np.ascontiguousarray(block_sizes, dtype="<u4").tobytes()).hexdigest() == g["block_sizes_sha256"]
     return bool(ok), sha
+
+
+DUMP_CHUNK = 1 << 16      # --dump-outputs: bytes per CRC-32 of the stream
+DUMP_SAMPLE = 1 << 22     # ... and sampled stream bytes (16 MB as float32)
+DUMP_SEED = 20250927
+
+
+def dump_outputs(dirname, stream, block_sizes=None):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as float arrays that two builds
+    can be compared by, about 16 MB in all:
+      stream_bytes.npy        [1] float64, the length of the compressed stream
+      stream_chunk_crc32.npy  float64, the CRC-32 of every 64 KiB chunk of the stream (every byte counts)
+      stream_sample.npy       float32, 4 Mi bytes of the stream at positions drawn with a fixed seed, in order
+      block_sizes.npy         float64, the framed size of every block (N = 1 only)"""
+    import zlib
+    os.makedirs(dirname, exist_ok=True)
+    host = stream.cpu().numpy()
+    n = int(host.size)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, max(n, 1), size=min(n, DUMP_SAMPLE)))
+    out = {"stream_bytes": np.array([n], dtype=np.float64),
+           "stream_chunk_crc32": np.array([zlib.crc32(host[lo:lo + DUMP_CHUNK]) for lo in range(0, n, DUMP_CHUNK)],
+                                          dtype=np.float64),
+           "stream_sample": host[idx].astype(np.float32)}
+    if block_sizes is not None:
+        out["block_sizes"] = np.asarray(block_sizes).astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def box_libdeflate():
@@ -1001,8 +1034,10 @@ def strong_leg(args, env, ctx, cap, gathered):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` from a bare shell: re-execute under torch.distributed.run, one rank
-    per GPU (the driver may also launch it that way itself; then WORLD_SIZE is already set)."""
+    """`python bench.py --gpus N` from a bare shell: run again under torch.distributed.run, one rank
+    per GPU, in a child process whose exit code this one exits with (the driver may also launch it
+    that way itself; then WORLD_SIZE is already set)."""
+    import signal
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -1012,7 +1047,10 @@ def self_launch(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    child = subprocess.Popen(cmd, env=env)
+    # a SIGTERM to this launcher (a time limit) reaches the ranks too
+    signal.signal(signal.SIGTERM, lambda signum, frame: child.send_signal(signum))
+    sys.exit(child.wait())
 
 
 def main():
@@ -1022,8 +1060,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--slab-bytes", type=int, default=SLAB_BYTES)
     ap.add_argument("--stream-bytes", type=int, default=FASTQ_STREAM, help="--workload fastq: the whole stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline region (no e2e / inflate legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, everything else the line can carry: stage times and roofline, "
+                         "the stream's checks, the e2e / inflate / levels / mgzip3 legs and the CPU baselines (N = 1), "
+                         "the other write-outs and the strong-scaling leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="compress workload: write what the last timed step produced to DIR/*.npy (rank 0; "
+                         "see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no CPU baselines (--full; --workload inflate)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="no e2e / inflate / levels / mgzip3 legs (--full; --workload inflate: no e2e leg)")
     ap.add_argument("--writeout", choices=["rccl", "offsets"], default="rccl",
                     help="N > 1 in-order write-out: rccl = ordered gather of the compressed shards to rank 0 over "
                          "xGMI (north_star); offsets = all_gather of the shard sizes only, every rank copies its "
@@ -1042,6 +1088,10 @@ def main():
     ap.add_argument("--debug-flags", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--lib", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "compress":
+        ap.error("--dump-outputs: the compress workload only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world == 1 and "RANK" not in os.environ:
@@ -1088,15 +1138,21 @@ def main():
     # two output buffers: with N > 1 the write-out of one step's shard (asynchronous) runs while the
     # next step compresses into the other buffer, the way ParCompress's slabs overlap
     d_outs = [torch.empty(cap, dtype=torch.uint8, device=env.dev) for _ in range(2 if world > 1 else 1)]
-    # N > 1: BOTH in-order write-outs are timed in this one run, back to back -- first the one --writeout
-    # names (default rccl: north_star's ordered gather), then the other; the line's `value` is the faster one.
-    modes = [None] if world == 1 else [args.writeout] + [m for m in ("rccl", "offsets") if m != args.writeout]
+    # N > 1: BOTH in-order write-outs are timed in this one run (--full), back to back -- first the one --writeout
+    # names (default rccl: north_star's ordered gather), then the other; the line's `value` is rccl's.  A plain run
+    # times rccl's alone.
+    if world == 1:
+        modes = [None]
+    elif args.full:
+        modes = [args.writeout] + [m for m in ("rccl", "offsets") if m != args.writeout]
+    else:
+        modes = ["rccl"]
     gathered = torch.empty(cap * world, dtype=torch.uint8, device=env.dev) if (world > 1 and rank == 0) else None
     # (a third one -- the writer's buffer IPC-mapped into every rank -- is timed LAST, behind everything else the line
     # carries and under a watchdog: see peer_leg below)
     peer_box = {"win": None}
     host_out = None
-    if world > 1 and not env.emulate:
+    if "offsets" in modes and not env.emulate:
         host_out = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
         copy_stream = torch.cuda.Stream()
     nb = ctx.n_blocks(n)
@@ -1178,6 +1234,50 @@ def main():
     value_mode = None if world == 1 else "rccl"
     head = regions[value_mode]
     dt, out_len, stage_acc = head["dt"], head["out_len"], head["stage_acc"]
+    if args.dump_outputs and rank == 0:  # (N > 1: the gathered stream of the last timed step)
+        stream = state["views"][value_mode] if world > 1 else d_outs[(state["i"] - 1) % len(d_outs)][:out_len]
+        dump_outputs(args.dump_outputs, stream, block_sizes if world == 1 else None)
+    if not args.full:
+        # a plain run: the headline figure and nothing else (N > 1 with --scaling strong: the strong leg is that figure)
+        ms_per_step = dt / args.steps * 1e3
+        value, scaling = total / 2**20 / (dt / args.steps), "weak"
+        if world > 1 and args.scaling == "strong":
+            strong = strong_leg(args, env, ctx, cap, gathered)
+            if rank == 0:
+                value, ms_per_step, scaling = strong["MiBps"], strong["ms_per_step"], "strong"
+        if rank == 0:
+            print(json.dumps({
+                "metric": "BGZF compress MiB/s at level 1, 550 MiB text",
+                "value": round(value, 1),
+                "unit": "MiB/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(ms_per_step, 3),
+                "higher_is_better": True,
+                "scaling": scaling,
+                "vs_baseline": None,
+                "dtype": "u8",
+                "data": "synthetic" if not env.emulate else "synthetic (CPU emulator dry run: not a measurement)",
+                "config": {
+                    "workload": "Single MI355X: 64 KiB BGZF blocks, level 1, 550 MiB text slab, "
+                                "bit-exact vs libdeflate",
+                    "slab_bytes": total,
+                    "shard_bytes": n,
+                    "block_size": BLOCK,
+                    "blocks": nb,
+                    "level": 1,
+                    "format": "bgzf",
+                    "ratio": round(out_len / n, 4),
+                    "parallelism": "block-shard x%d%s" % (
+                        world, "" if world == 1 else " + ordered RCCL gather of the compressed shards to rank 0"),
+                    "checks": "not in a plain run (--full: the stream against the oracle and the libdeflate-made digest)",
+                    "device": ctx.device_name(),
+                },
+            }))
+        ctx.close()
+        env.close()
+        return
     # every stage, outside the timed region (thirteen event markers per step cost the step 0.03 ms) -- under the
     # write-out `value` was measured with
     ctx.set_profiling(1)

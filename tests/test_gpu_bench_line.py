@@ -1,11 +1,13 @@
 """The lines the driver's runs produce, checked on the GPU box by launching bench.py the way the driver
 does (a subprocess from a bare shell): the default headline line with its self-proving keys, and
 configs[3]'s workload (`--workload fastq`) on a 4 GiB share of the stream."""
+import hashlib
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +25,7 @@ def _bench(*args, timeout=900):
 
 
 def test_headline_line_proves_itself():
-    d = _bench("--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline")
+    d = _bench("--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline")
     c, r = d["config"], d["roofline"]
     assert d["metric"].startswith("BGZF compress MiB/s at level 1") and d["unit"] == "MiB/s" and d["n_gpus"] == 1
     assert c["verified_bit_exact_full"] is True and c["verified_bit_exact_sample"] is True  # all 8,835 blocks vs libdeflate's
@@ -36,11 +38,30 @@ def test_headline_line_proves_itself():
     assert r["library_build_id"] and ((r["traffic"] is None) == ("refused" in r["traffic_source"] or "no profiles" in r["traffic_source"]))
 
 
+def test_plain_line_is_the_headline_and_dumps_the_stream(tmp_path):
+    """A plain run (no --full): the headline figure alone, and --dump-outputs writes what the last timed step made --
+    the stream's length and the framed block sizes are those of the libdeflate-made stream (tests/golden/fullsize.json)."""
+    d = _bench("--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert d["metric"] == "BGZF compress MiB/s at level 1, 550 MiB text" and d["unit"] == "MiB/s" and d["n_gpus"] == 1
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert not {"roofline", "e2e", "inflate", "levels", "mgzip3", "cpu_baseline", "cpu_baseline_parcompress"} & set(d)
+    names = sorted(os.listdir(tmp_path))
+    assert names == ["block_sizes.npy", "stream_bytes.npy", "stream_chunk_crc32.npy", "stream_sample.npy"]
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in names) <= 64 << 20
+    out = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    with open(os.path.join(ROOT, "tests", "golden", "fullsize.json")) as f:
+        g = [e for e in json.load(f)["streams"] if e["name"] == "config2_text_550MiB_bgzf_l1"][0]
+    assert out["stream_bytes"].tolist() == [g["size"]] and out["stream_chunk_crc32"].size == -(-g["size"] // 65536)
+    assert out["block_sizes"].size == 8835
+    assert hashlib.sha256(out["block_sizes"].astype("<u4").tobytes()).hexdigest() == g["block_sizes_sha256"]
+
+
 def test_default_line_carries_the_other_configurations():
-    """Everything the default `python bench.py` line promises beside the headline: the levels legs, configs[2] (Mgzip 1 MiB
+    """Everything the `python bench.py --full` line promises beside the headline: the levels legs, configs[2] (Mgzip 1 MiB
     blocks, level 3, 4 GiB of ASCII noise) with its digest and the inflation of its own stream, configs[4] (`inflate`),
     the host-to-host legs and the CPU baseline -- every stream checked against the libdeflate-made digest inside the run."""
-    d = _bench("--steps", "3", "--warmup", "1", timeout=1500)
+    d = _bench("--steps", "3", "--warmup", "1", "--full", timeout=1500)
     for lv in ("level_3", "level_6", "level_9"):
         leg = d["levels"][lv]
         assert leg["verified_bit_exact_full"] is True and leg["gpu_inflate_crc_roundtrip_ok"] is True and leg["MiBps"] > 0

@@ -4,7 +4,7 @@ O=gpurun_out/$1; shift; mkdir -p $O
 i=0
 for V in "$@"; do
   L=${V%%|*}; A=${V#*|}; i=$((i+1))
-  timeout 600 python bench.py --steps 8 --warmup 2 --no-extras --no-cpu-baseline $A --lib $L > $O/$i.json 2> $O/$i.err
+  timeout 600 python bench.py --steps 8 --warmup 2 --full --no-extras --no-cpu-baseline $A --lib $L > $O/$i.json 2> $O/$i.err
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$1; shift; A="$1"; shift; mkdir -p $O
 for L in "$@"; do
-  timeout 600 python bench.py --steps 8 --warmup 2 --no-extras --no-cpu-baseline $A --lib $L > $O/$(basename $L).json 2> $O/$(basename $L).err
+  timeout 600 python bench.py --steps 8 --warmup 2 --full --no-extras --no-cpu-baseline $A --lib $L > $O/$(basename $L).json 2> $O/$(basename $L).err
   python - <<PY
 import json
 d=json.loads(open("$O/$(basename $L).json").read().strip().splitlines()[-1])

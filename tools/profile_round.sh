@@ -8,7 +8,7 @@ tag=${1:-r06}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+B="python $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o $tag --output-format csv -- $B > $O/prof_$tag.log 2>&1
 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_inflate -o ${tag}_inflate --output-format csv -- $B --workload inflate > $O/prof_${tag}_inflate.log 2>&1
 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_bgzf3 -o ${tag}_bgzf3 --output-format csv -- $B --workload bgzf3 > $O/prof_${tag}_bgzf3.log 2>&1

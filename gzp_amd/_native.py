@@ -34,6 +34,7 @@ SLAB_FLUSH = 2
 
 FORMAT_BGZF = 0
 FORMAT_MGZIP = 1
+FORMAT_SNAP = 2  # compression only (gzp has no ParDecompress<Snap>)
 COMPAT_1_24 = 0
 COMPAT_1_10 = 1
 STREAM_NONE = ctypes.c_void_p(-1).value  # GZPX_STREAM_NONE: the caller has synchronized, no stream dependency
@@ -59,7 +60,7 @@ EXPORTS = [
     "gzpx_pard_last_error", "gzpx_host_alloc", "gzpx_host_free", "gzpx_dctx_last_inflate_ms",
     "gzpx_debug_inflate", "gzpx_dctx_last_inflate_stage_ms", "gzpx_dctx_set_route", "gzpx_dctx_last_redo_count", "gzpx_synth_fastq_device", "gzpx_synth_ascii_device",
     "gzpx_ctx_active_compat", "gzpx_build_id", "gzpx_multi_create", "gzpx_multi_destroy", "gzpx_multi_devices", "gzpx_multi_compress_slab",
-    "gzpx_multi_shard", "gzpx_multi_compress_slab_device",
+    "gzpx_multi_shard", "gzpx_multi_compress_slab_device", "gzpx_debug_snap",
 ]
 
 
@@ -227,6 +228,8 @@ class GzpxLib:
         L.gzpx_dctx_last_inflate_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_debug_inflate.restype = i32
         L.gzpx_debug_inflate.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint64)]
+        L.gzpx_debug_snap.restype = i32
+        L.gzpx_debug_snap.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint64)]
         L.gzpx_crc32_combine.restype = ctypes.c_uint32
         L.gzpx_crc32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
         L.gzpx_adler32_combine.restype = ctypes.c_uint32
@@ -455,6 +458,13 @@ class Context:
                                                 ctypes.byref(nb))
         self.lib.check(rc, nb.value if rc == ERR_BLOCK_SIZE_EXCEEDED else None)
         return out_len.value, nb.value
+
+    def debug_snap(self, enable):
+        """Snap: k_snap_chunk's phase clocks of the last batch summed over its chunks (gzpx_debug_snap), then switch them
+        on (enable) or off: [cycles, crc, scan, extend, emit, scan steps, copies, bytes]."""
+        sums = (ctypes.c_uint64 * 8)()
+        self.lib.check(self.lib.L.gzpx_debug_snap(self.h, int(enable), sums))
+        return [int(v) for v in sums]
 
     def debug_tokens(self, block):
         toks = np.empty(max(65536, int(self.buffer_size)), dtype=np.uint32)

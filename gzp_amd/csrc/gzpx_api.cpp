@@ -111,6 +111,7 @@ struct gzpx_ctx {
     int prof_n = 0;
     uint32_t batch_blocks = 0;
     Scratch scratch = {};
+    SnapScratch snap = {};  // GZPX_FORMAT_SNAP only
     Slot slots[kSlots];
     uint64_t next_gen = 1;
     BlockMeta *h_meta = nullptr;  // pinned; CRC-only contexts and the debug hooks
@@ -143,7 +144,11 @@ size_t extra_amount(size_t n) {  // src/bgzf.rs:45,50-52
     return e < 128 ? 128 : e;
 }
 
+// Snap: stream identifier + one 8-byte chunk header per 64 KiB + the chunk stored (src/snap.rs:61-74)
+size_t snap_bound_per_block(size_t bs) { return 10 + bs + 8 * (size_t)snap_chunks_per_buffer((uint32_t)bs); }
+
 size_t framed_bound_per_block(const gzpx_ctx *ctx) {
+    if (ctx->cfg.format == GZPX_FORMAT_SNAP) return snap_bound_per_block(ctx->cfg.buffer_size);
     const size_t hdr = ctx->cfg.format == GZPX_FORMAT_BGZF ? 18 : 20;
     return hdr + ctx->cfg.buffer_size + extra_amount(ctx->cfg.buffer_size) + 8;
 }
@@ -160,11 +165,27 @@ size_t scratch_bytes_per_block(const Config &c) {
            sizeof(BlockMeta) + 8 + 4;
 }
 
+// Snap: staging per chunk, and the arrays k_scan works on
+size_t snap_scratch_bytes_per_block(size_t bs) {
+    return (size_t)snap_chunks_per_buffer((uint32_t)bs) * (kSnapStageBytes + 3 * 4) + sizeof(BlockMeta) + 8 + 4;
+}
+
 int alloc_scratch(gzpx_ctx *ctx) {
     const size_t nb = ctx->batch_blocks;
     const Config &c = ctx->dcfg;
     Scratch &s = ctx->scratch;
     HIP_TRY(hipMalloc((void **)&s.meta, nb * sizeof(BlockMeta)));
+    if (ctx->cfg.format == GZPX_FORMAT_SNAP) {
+        SnapScratch &ss = ctx->snap;
+        const size_t chunks = nb * snap_chunks_per_buffer((uint32_t)ctx->cfg.buffer_size);
+        HIP_TRY(hipMalloc((void **)&ss.stage, chunks * kSnapStageBytes));
+        HIP_TRY(hipMalloc((void **)&ss.clen, chunks * 4));
+        HIP_TRY(hipMalloc((void **)&ss.crc, chunks * 4));
+        HIP_TRY(hipMalloc((void **)&ss.coff, chunks * 4));
+        HIP_TRY(hipMalloc((void **)&s.out_off, (nb + 1) * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc((void **)&s.sizes, nb * sizeof(uint32_t)));
+        return GZPX_OK;
+    }
     if (ctx->crc_only) {  // gzpx_crc32's private context: k_init_meta + k_crc32 only
         HIP_TRY(hipHostMalloc((void **)&ctx->h_meta, nb * sizeof(BlockMeta), hipHostMallocDefault));
         return GZPX_OK;
@@ -283,6 +304,10 @@ void free_scratch(gzpx_ctx *ctx) {
     if (s.out_off) (void)hipFree(s.out_off);
     if (s.sizes) (void)hipFree(s.sizes);
     if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
+    SnapScratch &ss = ctx->snap;
+    for (void *p : {(void *)ss.stage, (void *)ss.clen, (void *)ss.crc, (void *)ss.coff, (void *)ss.dbg})
+        if (p) (void)hipFree(p);
+    ss = SnapScratch{};
     for (Slot &sl : ctx->slots) free_slot(sl);
     s = Scratch{};
 }
@@ -434,6 +459,45 @@ int enqueue_batch(gzpx_ctx *ctx, const uint8_t *d_in, size_t in_len, uint32_t nb
     return GZPX_OK;
 }
 
+// Snap's batch (src/snap.rs:61-74, FrameEncoder over every buffer): k_snap_chunk (raw Snappy + CRC-32C of every
+// 64 KiB chunk), k_snap_frame + k_scan (framed sizes, offsets), k_snap_emit.  Stage slots: 2 = k_snap_chunk,
+// 7 = k_snap_frame + k_scan, 8 = k_snap_emit; the others stay 0.  Snap has no end-of-stream marker: is_last has no
+// effect.
+int enqueue_snap_batch(gzpx_ctx *ctx, const uint8_t *d_in, size_t in_len, uint32_t nb, uint8_t *d_out,
+                       size_t out_cap, hipStream_t stream, const SlabResult *prev, SlabResult *result,
+                       hipEvent_t dom_b = nullptr, hipEvent_t dom_e = nullptr) {
+    const Scratch &s = ctx->scratch;
+    const uint32_t bs = (uint32_t)ctx->cfg.buffer_size;
+    ProfPairs pp{ctx, ctx->profiling != 0};
+    pp.dom_b = dom_b;
+    pp.dom_e = dom_e;
+    ctx->prof_n = 0;
+    if (ctx->snap.dbg)
+        HIP_TRY(hipMemsetAsync(ctx->snap.dbg, 0,
+                               (size_t)nb * snap_chunks_per_buffer(bs) * 8 * sizeof(uint64_t), stream));
+    int t = pp.begin(2, stream);
+    launch_snap_chunk(d_in, in_len, bs, nb, ctx->snap, stream);
+    pp.end(t, stream);
+    t = pp.begin(7, stream);
+    launch_snap_frame(in_len, bs, nb, s, ctx->snap, stream);
+    launch_scan(nb, s, prev, result, stream);
+    pp.end(t, stream);
+    t = pp.begin(8, stream);
+    launch_snap_emit(d_in, in_len, bs, nb, s, ctx->snap, d_out, out_cap, stream);
+    pp.end(t, stream);
+    HIP_TRY(hipGetLastError());
+    if (pp.on && !dom_b) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (int i = 0; i < ctx->prof_n; i++) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ctx->prof_ev[ctx->prof_b[i]], ctx->prof_ev[ctx->prof_e[i]]));
+            ctx->stage_ms[ctx->prof_stage[i]] += ms;
+        }
+    }
+    ctx->last_nb = nb;
+    return GZPX_OK;
+}
+
 int slot_reserve(Slot &sl, size_t n_batches, size_t n_blocks) {
     if (n_batches > sl.results_cap) {
         if (sl.d_results) (void)hipFree(sl.d_results);
@@ -574,9 +638,14 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
         size_t in_batch = in_len > in_begin ? in_len - in_begin : 0;
         if (in_batch > (size_t)nb * bs) in_batch = (size_t)nb * bs;
         const int last_batch = (b0 + nb == total_nb) ? is_last : 0;
-        rc = enqueue_batch(ctx, d_in + in_begin, in_batch, nb, last_batch, d_out, out_cap, stream,
-                           bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi,
-                           sl.dom_timed ? sl.ev_dom_b : nullptr, sl.dom_timed ? sl.ev_dom_e : nullptr);
+        if (ctx->cfg.format == GZPX_FORMAT_SNAP)
+            rc = enqueue_snap_batch(ctx, d_in + in_begin, in_batch, nb, d_out, out_cap, stream,
+                                    bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi,
+                                    sl.dom_timed ? sl.ev_dom_b : nullptr, sl.dom_timed ? sl.ev_dom_e : nullptr);
+        else
+            rc = enqueue_batch(ctx, d_in + in_begin, in_batch, nb, last_batch, d_out, out_cap, stream,
+                               bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi,
+                               sl.dom_timed ? sl.ev_dom_b : nullptr, sl.dom_timed ? sl.ev_dom_e : nullptr);
         if (rc != GZPX_OK) {
             (void)hipStreamSynchronize(stream);
             return rc;
@@ -708,7 +777,7 @@ void gzpx_config_default(gzpx_config *cfg, int format) {
     cfg->format = format;
     cfg->level = 3;  // ParCompressBuilder::new: Compression::new(3), src/par/compress.rs:54-62
     cfg->compat = GZPX_COMPAT_LIBDEFLATE_1_24;
-    // Bgzf::DEFAULT_BUFSIZE = 65280 (src/deflate.rs:583); Mgzip keeps the trait default
+    // Bgzf::DEFAULT_BUFSIZE = 65280 (src/deflate.rs:583); Mgzip and Snap keep the trait default
     // DEFAULT_BUFSIZE = BUFSIZE = 128 KiB (src/lib.rs:330, :105)
     cfg->buffer_size = format == GZPX_FORMAT_BGZF ? 65280 : 131072;
     cfg->max_slab_bytes = (size_t)1 << 30;
@@ -723,10 +792,13 @@ namespace {
 int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
     if (!cfg || !out) return GZPX_ERR_INVALID_ARG;
     *out = nullptr;
-    if (cfg->format != GZPX_FORMAT_BGZF && cfg->format != GZPX_FORMAT_MGZIP) return GZPX_ERR_INVALID_ARG;
+    const bool snap = cfg->format == GZPX_FORMAT_SNAP;
+    if (cfg->format != GZPX_FORMAT_BGZF && cfg->format != GZPX_FORMAT_MGZIP && !(snap && !crc_only))
+        return GZPX_ERR_INVALID_ARG;
     if (cfg->buffer_size < kDictSize) return GZPX_ERR_BUFFER_SIZE;  // src/par/compress.rs:68-74
-    if (cfg->level < 0 || cfg->level > 12) return GZPX_ERR_COMPRESSION_LEVEL;
-    if (cfg->compat != GZPX_COMPAT_LIBDEFLATE_1_24 && cfg->compat != GZPX_COMPAT_LIBDEFLATE_1_10)
+    // (Snap ignores the level and has no libdeflate rules, src/snap.rs:53-59, 91)
+    if (!snap && (cfg->level < 0 || cfg->level > 12)) return GZPX_ERR_COMPRESSION_LEVEL;
+    if (!snap && cfg->compat != GZPX_COMPAT_LIBDEFLATE_1_24 && cfg->compat != GZPX_COMPAT_LIBDEFLATE_1_10)
         return GZPX_ERR_INVALID_ARG;
     if (cfg->buffer_size > kMaxBlockSize) return GZPX_ERR_UNSUPPORTED;  // > 16 MiB blocks: not built
     int ndev = 0;
@@ -739,37 +811,39 @@ int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
     ctx->cfg = *cfg;
     ctx->crc_only = crc_only;
     ctx->dcfg.format = (uint32_t)cfg->format;
-    ctx->dcfg.level = (uint32_t)cfg->level;
+    // (a Snap context runs none of the deflate kernels: its level and compat are kept as given and ignored)
+    const int lvl = snap ? 0 : cfg->level, cmp = snap ? GZPX_COMPAT_LIBDEFLATE_1_24 : cfg->compat;
+    ctx->dcfg.level = (uint32_t)lvl;
     // Levels 10-12 are libdeflate 1.10's near-optimal parser (1.24 changed it; there is nothing here to pin a port of
     // the later parser on): the 1.10 rules go with it WHATEVER the caller asked for, so the stream is exactly the
     // 1.10 binary's and never a hybrid of two versions.  gzpx_ctx_active_compat() tells which rules a context runs.
-    ctx->dcfg.compat = (uint32_t)(cfg->level >= 10 ? GZPX_COMPAT_LIBDEFLATE_1_10 : cfg->compat);
-    if (cfg->level >= 10 && cfg->compat != GZPX_COMPAT_LIBDEFLATE_1_10 && getenv("GZPX_TRACE")) {
+    ctx->dcfg.compat = (uint32_t)(lvl >= 10 ? GZPX_COMPAT_LIBDEFLATE_1_10 : cmp);
+    if (lvl >= 10 && cmp != GZPX_COMPAT_LIBDEFLATE_1_10 && getenv("GZPX_TRACE")) {
         static std::atomic<bool> told{false};  // (once per process; ADVICE round 4: the override used to be silent)
         if (!told.exchange(true))
             fprintf(stderr, "gzpx: level %d runs libdeflate 1.10's near-optimal parser; compat %d was asked for, the 1.10 "
-                            "rules are in force (gzpx_ctx_active_compat)\n", cfg->level, cfg->compat);
+                            "rules are in force (gzpx_ctx_active_compat)\n", lvl, cmp);
     }
     ctx->dcfg.block_size = (uint32_t)cfg->buffer_size;
-    ctx->dcfg.xfl = cfg->level >= 9 ? 2u : cfg->level <= 1 ? 4u : 0u;  // src/bgzf.rs:278-284
+    ctx->dcfg.xfl = lvl >= 9 ? 2u : lvl <= 1 ? 4u : 0u;  // src/bgzf.rs:278-284
     ctx->dcfg.debug = 0;
     // per-block strides: padding for k_candidates' last iteration / dword-wide tile loads
     ctx->dcfg.stride = (uint32_t)((cfg->buffer_size + 2047) / 2048 * 2048 + 2048);
     // level 1 sub-blocks hold 8192 matches (>= 32768 bytes); the block splitter of levels 2-4 may
     // cut every MIN_BLOCK_LENGTH = 5000 bytes
-    ctx->dcfg.max_sub = (uint32_t)(cfg->buffer_size / (cfg->level == 1 ? 32768 : 5000) + 2);
+    ctx->dcfg.max_sub = (uint32_t)(cfg->buffer_size / (lvl == 1 ? 32768 : 5000) + 2);
     // deflate_compress: inputs up to 55 - 4*level bytes -- and everything at level 0 -- take
     // deflate_compress_none
-    ctx->dcfg.passthrough = cfg->level == 0 ? 0xFFFFFFFFu : (uint32_t)(55 - 4 * cfg->level);
+    ctx->dcfg.passthrough = lvl == 0 ? 0xFFFFFFFFu : (uint32_t)(55 - 4 * lvl);
     {
         // libdeflate_alloc_compressor: max_search_depth / nice_match_length of levels 2-9
         // (levels 10-12, deflate_compress_near_optimal: + num_optim_passes 2 / 3 / 4)
         static const uint32_t depth[13] = {0, 0, 6, 12, 16, 16, 35, 100, 300, 600, 35, 70, 150};
         static const uint32_t nice[13] = {0, 0, 10, 14, 30, 30, 65, 130, 258, 258, 75, 150, 258};
-        ctx->dcfg.hc_depth = depth[cfg->level];
-        ctx->dcfg.hc_nice = nice[cfg->level];
-        ctx->dcfg.lazy = cfg->level >= 10 ? 0u : cfg->level >= 8 ? 2u : cfg->level >= 5 ? 1u : 0u;
-        ctx->dcfg.no_passes = cfg->level >= 10 ? (uint32_t)cfg->level - 8u : 0u;
+        ctx->dcfg.hc_depth = depth[lvl];
+        ctx->dcfg.hc_nice = nice[lvl];
+        ctx->dcfg.lazy = lvl >= 10 ? 0u : lvl >= 8 ? 2u : lvl >= 5 ? 1u : 0u;
+        ctx->dcfg.no_passes = lvl >= 10 ? (uint32_t)lvl - 8u : 0u;
     }
     for (unsigned l = 0; l < 10; l++) ctx->crc_consts.pow64[l] = x2k(9 + l);
     ctx->crc_consts.pow_tile = x2k(19);  // x^(8 * 65536) = x^(2^19)
@@ -782,7 +856,10 @@ int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
     }
     const uint64_t want = blocks_of(ctx, cfg->max_slab_bytes ? cfg->max_slab_bytes : 1);
     ctx->batch_blocks = (uint32_t)(want < kMaxBatchBlocks ? want : kMaxBatchBlocks);
-    if (!crc_only) {
+    if (snap) {
+        const size_t fit = kMaxScratchBytes / snap_scratch_bytes_per_block(cfg->buffer_size);
+        if (ctx->batch_blocks > fit) ctx->batch_blocks = (uint32_t)fit;
+    } else if (!crc_only) {
         const size_t fit = kMaxScratchBytes / scratch_bytes_per_block(ctx->dcfg);
         if (ctx->batch_blocks > fit) ctx->batch_blocks = (uint32_t)fit;
     }
@@ -836,10 +913,14 @@ void gzpx_ctx_destroy(gzpx_ctx *ctx) {
     delete ctx;
 }
 
-int gzpx_ctx_active_compat(const gzpx_ctx *ctx) { return ctx ? (int)ctx->dcfg.compat : GZPX_ERR_INVALID_ARG; }
+int gzpx_ctx_active_compat(const gzpx_ctx *ctx) {
+    if (!ctx) return GZPX_ERR_INVALID_ARG;
+    return ctx->cfg.format == GZPX_FORMAT_SNAP ? ctx->cfg.compat : (int)ctx->dcfg.compat;
+}
 
 size_t gzpx_slab_bound(const gzpx_ctx *ctx, size_t in_len) {
     if (!ctx) return 0;
+    if (ctx->cfg.format == GZPX_FORMAT_SNAP) return (size_t)blocks_of(ctx, in_len) * framed_bound_per_block(ctx);
     return (size_t)blocks_of(ctx, in_len) * framed_bound_per_block(ctx) + 28 + 64;
 }
 
@@ -975,6 +1056,7 @@ void multi_part_of(size_t in_len, size_t bs, size_t G, size_t g, MultiPart &p) {
 int gzpx_multi_create(const gzpx_config *cfg, const int *devices, size_t n_devices, gzpx_multi **out) {
     if (!cfg || !devices || !n_devices || !out) return GZPX_ERR_INVALID_ARG;
     *out = nullptr;
+    if (cfg->format == GZPX_FORMAT_SNAP) return GZPX_ERR_UNSUPPORTED;  // (multi-device Snap: not built)
     gzpx_multi *m = new (std::nothrow) gzpx_multi();
     if (!m) return GZPX_ERR_DEVICE;
     m->buffer_size = cfg->buffer_size;
@@ -1913,6 +1995,8 @@ const char *gzpx_stage_name(int stage) {
 }
 
 const char *gzpx_ctx_stage_kernel(const gzpx_ctx *ctx, int stage) {
+    if (ctx && ctx->cfg.format == GZPX_FORMAT_SNAP)  // (the CRC-32C is computed inside k_snap_chunk)
+        return stage == 2 ? "k_snap_chunk" : stage == 7 ? "k_snap_frame+k_scan" : stage == 8 ? "k_snap_emit" : "-";
     // the kernels behind stages 2 and 3 depend on the level (and, at level 1, on the block size)
     if (ctx && stage == 2) {
         const Config &c = ctx->dcfg;
@@ -1926,7 +2010,8 @@ const char *gzpx_ctx_stage_kernel(const gzpx_ctx *ctx, int stage) {
 
 int gzpx_debug_tokens(gzpx_ctx *ctx, size_t block, uint32_t *tokens, size_t max_tokens,
                       size_t *n_tokens, uint32_t *sub_first_token, size_t *n_sub) {
-    if (!ctx || !n_tokens || block >= ctx->last_nb || ctx->crc_only) return GZPX_ERR_INVALID_ARG;
+    if (!ctx || !n_tokens || block >= ctx->last_nb || ctx->crc_only || ctx->cfg.format == GZPX_FORMAT_SNAP)
+        return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1947,6 +2032,33 @@ int gzpx_debug_tokens(gzpx_ctx *ctx, size_t block, uint32_t *tokens, size_t max_
     return GZPX_OK;
 }
 
+int gzpx_debug_snap(gzpx_ctx *ctx, int enable, uint64_t sums[8]) {
+    if (!ctx || ctx->cfg.format != GZPX_FORMAT_SNAP) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t chunks = (size_t)ctx->batch_blocks * snap_chunks_per_buffer((uint32_t)ctx->cfg.buffer_size);
+    SnapScratch &ss = ctx->snap;
+    if (sums) {
+        for (int k = 0; k < 8; k++) sums[k] = 0;
+        const size_t used = (size_t)ctx->last_nb * snap_chunks_per_buffer((uint32_t)ctx->cfg.buffer_size);
+        if (ss.dbg && used) {
+            std::vector<uint64_t> h(used * 8);
+            HIP_TRY(hipMemcpy(h.data(), ss.dbg, h.size() * 8, hipMemcpyDeviceToHost));
+            for (size_t c = 0; c < used; c++)
+                for (int k = 0; k < 8; k++) sums[k] += h[c * 8 + k];
+        }
+    }
+    if (enable && !ss.dbg) {
+        HIP_TRY(hipMalloc((void **)&ss.dbg, chunks * 8 * sizeof(uint64_t)));
+        HIP_TRY(hipMemset(ss.dbg, 0, chunks * 8 * sizeof(uint64_t)));
+    } else if (!enable && ss.dbg) {
+        (void)hipFree(ss.dbg);
+        ss.dbg = nullptr;
+    }
+    return GZPX_OK;
+}
+
 int gzpx_debug_set_flags(gzpx_ctx *ctx, uint32_t flags) {
     if (!ctx) return GZPX_ERR_INVALID_ARG;
     ctx->dcfg.debug = flags;
@@ -1954,7 +2066,7 @@ int gzpx_debug_set_flags(gzpx_ctx *ctx, uint32_t flags) {
 }
 
 int gzpx_debug_redo_count(gzpx_ctx *ctx, uint32_t *count) {
-    if (!ctx || !count || ctx->crc_only) return GZPX_ERR_INVALID_ARG;
+    if (!ctx || !count || ctx->crc_only || ctx->cfg.format == GZPX_FORMAT_SNAP) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -135,6 +135,23 @@ struct Scratch {
     uint8_t *no_nodes;    // [no_lanes] minimum-cost path nodes of a DEFLATE block
 };
 
+// Snap (gzpx_snap.h): per chunk of 64 KiB of a batch, chunk c = buffer * chunks_per_buffer + k
+constexpr uint32_t kSnapStageBytes = 76544;  // >= MaxCompressedLength(65536) = 32 + 65536 + 65536 / 6
+struct SnapScratch {
+    uint8_t *stage;  // [chunks][kSnapStageBytes]  raw Snappy body of each chunk
+    uint32_t *clen;  // [chunks]  its length (0: no such chunk)
+    uint32_t *crc;   // [chunks]  masked CRC-32C of the uncompressed chunk
+    uint32_t *coff;  // [chunks]  where the chunk's frame starts inside its buffer's
+    uint64_t *dbg;   // [chunks][8] k_snap_chunk's phase clocks, when measuring (else null)
+};
+inline uint32_t snap_chunks_per_buffer(uint32_t bs) { return (bs + 65535u) / 65536u; }
+void launch_snap_chunk(const uint8_t *slab, uint64_t slab_len, uint32_t bs, uint32_t nb, const SnapScratch &ss,
+                       hipStream_t stream);
+void launch_snap_frame(uint64_t slab_len, uint32_t bs, uint32_t nb, const Scratch &s, const SnapScratch &ss,
+                       hipStream_t stream);
+void launch_snap_emit(const uint8_t *slab, uint64_t slab_len, uint32_t bs, uint32_t nb, const Scratch &s,
+                      const SnapScratch &ss, uint8_t *out, uint64_t out_cap, hipStream_t stream);
+
 // Host-side launchers (gzpx_kernels.hip).  All asynchronous on `stream`.
 void launch_init_meta(const Config &cfg, uint64_t slab_len, uint32_t nb, int is_last,
                       const Scratch &s, hipStream_t stream);

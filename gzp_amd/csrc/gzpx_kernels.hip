@@ -5556,6 +5556,7 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
 }
 
 #include "gzpx_inflate_seg.h"
+#include "gzpx_snap.h"
 
 // CRC-32 of the inflated blocks (LibDeflateCrc over the whole orig_size buffer, src/check.rs:45-71):
 // the workgroup routine of k_crc32, blocks addressed through their output offsets.

@@ -856,6 +856,7 @@ int gzpx_par_finish(gzpx_par *p) {
 
 int gzpx_par_index(gzpx_par *p, gzpx_index_entry *entries, size_t max_entries, size_t *n_entries) {
     if (!p || !n_entries) return GZPX_ERR_INVALID_ARG;
+    if (p->pc && p->pc->format() == GZPX_FORMAT_SNAP) return GZPX_ERR_INVALID_ARG;  // (a BGZF / Mgzip side-product)
     return guarded(p, [&] {
         const std::vector<gzp::IndexEntry> idx = p->pc->index();
         *n_entries = idx.size();

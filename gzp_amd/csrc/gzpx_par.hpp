@@ -92,6 +92,10 @@ struct Mgzip {
     static constexpr size_t DEFAULT_BUFSIZE = BUFSIZE;  // trait default, src/lib.rs:330
     static constexpr int FORMAT = GZPX_FORMAT_MGZIP;
 };
+struct Snap {  // compression only: gzp has no ParDecompress<Snap>
+    static constexpr size_t DEFAULT_BUFSIZE = BUFSIZE;  // trait default, src/lib.rs:330
+    static constexpr int FORMAT = GZPX_FORMAT_SNAP;
+};
 
 // The wrapped `W: Write`: returns false on an I/O error (message in *err).
 using WriteFn = std::function<bool(const uint8_t *data, size_t n, std::string *err)>;
@@ -164,6 +168,7 @@ class ParCompress {
     // (compressed offset, uncompressed offset) of every block written so far, in stream order.
     // Complete after finish().
     std::vector<IndexEntry> index() const;
+    int format() const { return cfg_.format; }
 
     size_t effective_batch_blocks() const { return batch_blocks_; }
 

@@ -59,6 +59,13 @@ class Mgzip:
     FORMAT = _native.FORMAT_MGZIP
 
 
+class Snap:
+    """snap::read::FrameEncoder over every buffer (src/snap.rs:38-83).  Compression only: gzp has no ParDecompress<Snap>;
+    the level is accepted and ignored, and there is no block index."""
+    DEFAULT_BUFSIZE = BUFSIZE  # src/lib.rs:330
+    FORMAT = _native.FORMAT_SNAP
+
+
 class ParCompress:
     """`Write` + `ZWriter` (src/par/compress.rs:221-469, src/lib.rs:166-170)."""
 
@@ -365,6 +372,8 @@ class ParDecompressBuilder:
     """ParDecompressBuilder<F> (src/par/decompress.rs:17-109)."""
 
     def __init__(self, fmt=Bgzf, lib=None):
+        if fmt is Snap:  # (src/par/decompress.rs: BlockFormatSpec is Bgzf / Mgzip only)
+            raise _native.GzpxError(_native.ERR_INVALID_ARG, "ParDecompress<Snap> does not exist in gzp")
         self._fmt = fmt
         self._lib = lib
         self._device = 0

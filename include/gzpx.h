@@ -17,6 +17,7 @@
  *                              = libdeflate_crc32                       libdeflate.h:343-344
  *   gzpx_encode_block          FormatSpec::encode for Bgzf / Mgzip     src/lib.rs:351-358, src/deflate.rs:613-626, 463-472
  *                              (= bgzf::compress src/bgzf.rs:204-237 + BGZF_EOF src/bgzf.rs:24-38)
+ *                              FormatSpec::encode for Snap              src/snap.rs:61-74 (FrameEncoder over the buffer)
  *   gzpx_compress_slab*        the worker loop of ParCompress::run     src/par/compress.rs:279-294, applied to every
  *                              block of a slab cut by ParCompress::write / flush_last (src/par/compress.rs:413-463, 332-362)
  *   error codes                GzpError variants on this path          src/lib.rs:114-163
@@ -59,6 +60,14 @@ extern "C" {
 
 #define GZPX_FORMAT_BGZF 0
 #define GZPX_FORMAT_MGZIP 1
+/* Snap (src/snap.rs:38-83): every buffer_size piece is snap::read::FrameEncoder's frame stream of that piece alone --
+ * the stream identifier, then per 64 KiB chunk a header, the masked CRC-32C of the chunk and its raw Snappy encoding
+ * (or the chunk itself where that is not shorter than n - n/8); an empty piece encodes to nothing.  gzp ignores the
+ * level for Snap (src/snap.rs:53-59, 91): level and compat are accepted whatever they are.  Snap has no end-of-stream
+ * marker, so GZPX_SLAB_LAST and GZPX_SLAB_FLUSH produce the same bytes.  Compression only: gzp has no
+ * ParDecompress<Snap> (gzpx_dctx_create refuses it), and the multi-device entry points and gzpx_par_index refuse it
+ * too.  Raw chunk bodies are snappy 1.1.8's (DESIGN.md "Snap"). */
+#define GZPX_FORMAT_SNAP 2
 
 /* libdeflate behaviour pinned by Cargo.lock is 1.24; the image's binary oracle is 1.10.  The two
  * differ (for levels 1-4) only in how a Huffman code with no used symbol is emitted and in
@@ -81,7 +90,7 @@ typedef struct gzpx_config {
 
 typedef struct gzpx_ctx gzpx_ctx;
 
-/* Fills *cfg with the reference's defaults for `format` (Bgzf: buffer_size 65280, level 3 ->
+/* Fills *cfg with the reference's defaults for `format` (Bgzf: buffer_size 65280, Mgzip / Snap 131072, level 3 ->
  * callers set the level they use; compat 1.24; device 0; max_slab_bytes 1 GiB). */
 void gzpx_config_default(gzpx_config *cfg, int format);
 
@@ -185,7 +194,7 @@ int gzpx_multi_compress_slab_device(gzpx_multi *m, const void *const *d_in, size
                                     void *d_out, size_t out_cap, size_t *out_len, uint32_t *block_sizes,
                                     size_t max_blocks, size_t *n_blocks);
 
-/* FormatSpec::encode: one framed block (is_last => BGZF_EOF appended for BGZF). */
+/* FormatSpec::encode: one framed block (is_last => BGZF_EOF appended for BGZF; ignored for Snap, src/snap.rs:61-74). */
 int gzpx_encode_block(gzpx_ctx *ctx, const uint8_t *in, size_t n, int is_last, uint8_t *out,
                       size_t out_cap, size_t *out_len);
 
@@ -357,6 +366,12 @@ int gzpx_debug_tokens(gzpx_ctx *ctx, size_t block, uint32_t *tokens, size_t max_
 int gzpx_debug_set_flags(gzpx_ctx *ctx, uint32_t flags);
 /* Level 1: how many blocks of the last batch k_mparse handed back to the dense kernels. */
 int gzpx_debug_redo_count(gzpx_ctx *ctx, uint32_t *count);
+/* Snap contexts: switch k_snap_chunk's phase clocks on (1) / off (0); sums[] = the clocks of the last batch of the
+ * last launch summed over its chunks: [0] cycles of k_snap_chunk, [1] CRC-32C, [2] literal scans, [3] match
+ * extension and the table updates between copies, [4] literal and copy emission, [5] scan steps (64 probes each),
+ * [6] copies, [7] bytes.  Stage times of a Snap context: slot 2 = k_snap_chunk, 7 = k_snap_frame + k_scan,
+ * 8 = k_snap_emit (gzpx_ctx_stage_kernel). */
+int gzpx_debug_snap(gzpx_ctx *ctx, int enable, uint64_t sums[8]);
 
 /* HIP-event duration of the inflate kernels (k_inflate_seg + k_lzcopy + k_inflate over the redo list, or
  * k_inflate alone) in the last decompress launch of this context */

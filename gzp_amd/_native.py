@@ -61,6 +61,7 @@ EXPORTS = [
     "gzpx_debug_inflate", "gzpx_dctx_last_inflate_stage_ms", "gzpx_dctx_set_route", "gzpx_dctx_last_redo_count", "gzpx_synth_fastq_device", "gzpx_synth_ascii_device",
     "gzpx_ctx_active_compat", "gzpx_build_id", "gzpx_multi_create", "gzpx_multi_destroy", "gzpx_multi_devices", "gzpx_multi_compress_slab",
     "gzpx_multi_shard", "gzpx_multi_compress_slab_device", "gzpx_debug_snap",
+    "gzpx_scan_blocks_device", "gzpx_decompress_stream_device", "gzpx_index_device", "gzpx_dctx_last_scan_ms",
 ]
 
 
@@ -214,6 +215,14 @@ class GzpxLib:
         L.gzpx_decompress_blocks_wait.argtypes = [vp, ctypes.c_uint64, psz, pinfo]
         L.gzpx_decompress_blocks_device.restype = i32
         L.gzpx_decompress_blocks_device.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, psz, pinfo, vp]
+        L.gzpx_scan_blocks_device.restype = i32
+        L.gzpx_scan_blocks_device.argtypes = [vp, vp, sz, vp, vp, sz, psz, psz, vp]
+        L.gzpx_decompress_stream_device.restype = i32
+        L.gzpx_decompress_stream_device.argtypes = [vp, vp, sz, vp, sz, psz, psz, psz, pinfo, vp]
+        L.gzpx_index_device.restype = i32
+        L.gzpx_index_device.argtypes = [vp, vp, sz, vp, sz, psz, psz, pu64, vp]
+        L.gzpx_dctx_last_scan_ms.restype = i32
+        L.gzpx_dctx_last_scan_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_alloc_decompressor.restype = vp
         L.gzpx_alloc_decompressor.argtypes = []
         L.gzpx_deflate_decompress.restype = i32
@@ -753,6 +762,51 @@ class DContext:
         if rc != OK:
             self._raise(rc, info)
         return out_len.value
+
+    # ---- streams that lie in device memory: the members are found on the device (gzpx_mscan.h)
+    def scan_blocks_device(self, d_in_ptr, in_len, max_blocks=None, want_tables=True, stream=None):
+        """gzpx_scan_blocks for d_in[0..in_len) in device memory: (offsets uint64[], sizes uint32[], consumed), or
+        (n_blocks, consumed) with want_tables=False.  max_blocks=None: room for every member."""
+        nb = ctypes.c_size_t(0)
+        used = ctypes.c_size_t(0)
+        if not want_tables or max_blocks is None:
+            self.lib.check(self.lib.L.gzpx_scan_blocks_device(self.h, d_in_ptr, in_len, None, None, max_blocks or 0,
+                                                              ctypes.byref(nb), ctypes.byref(used), stream))
+            if not want_tables:
+                return nb.value, used.value
+            max_blocks = nb.value
+        offs = np.zeros(max(max_blocks, 1), dtype=np.uint64)
+        sizes = np.zeros(max(max_blocks, 1), dtype=np.uint32)
+        self.lib.check(self.lib.L.gzpx_scan_blocks_device(self.h, d_in_ptr, in_len, offs.ctypes.data, sizes.ctypes.data,
+                                                          max_blocks, ctypes.byref(nb), ctypes.byref(used), stream))
+        return offs[:nb.value], sizes[:nb.value], used.value
+
+    def decompress_stream_device(self, d_in_ptr, in_len, d_out_ptr, out_cap, stream=None):
+        """Scan + inflate of every complete member of d_in[0..in_len): (out_len, n_blocks, consumed)."""
+        out_len, nb, used = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_decompress_stream_device(self.h, d_in_ptr, in_len, d_out_ptr, out_cap, ctypes.byref(out_len),
+                                                      ctypes.byref(nb), ctypes.byref(used), ctypes.byref(info), stream)
+        if rc != OK:
+            self._raise(rc, info)
+        return out_len.value, nb.value, used.value
+
+    def index_device(self, d_in_ptr, in_len, stream=None):
+        """The block index of a stream in device memory, one row per member as a reader sees them:
+        (idx[n, 2] uint64 = (compressed offset, uncompressed offset), consumed, inflated_len)."""
+        n, used, total = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
+        self.lib.check(self.lib.L.gzpx_index_device(self.h, d_in_ptr, in_len, None, 0, ctypes.byref(n), ctypes.byref(used),
+                                                    ctypes.byref(total), stream))
+        idx = np.zeros((max(n.value, 1), 2), dtype=np.uint64)
+        self.lib.check(self.lib.L.gzpx_index_device(self.h, d_in_ptr, in_len, idx.ctypes.data, n.value, ctypes.byref(n),
+                                                    ctypes.byref(used), ctypes.byref(total), stream))
+        return idx[:n.value], used.value, total.value
+
+    def last_scan_ms(self):
+        """HIP-event duration of the member-discovery kernels of the last *_device call that scanned."""
+        ms = ctypes.c_float(0)
+        self.lib.check(self.lib.L.gzpx_dctx_last_scan_ms(self.h, ctypes.byref(ms)))
+        return ms.value
 
 
 class Decompressor:

@@ -1581,16 +1581,32 @@ struct gzpx_dctx {
     int route = kInflateRouteSeg;  // GZPX_INFLATE_ROUTE=wave / gzpx_dctx_set_route: k_inflate for every member
     int last_slot = -1;  // the slot of the last completed launch (timing / debug counters)
     size_t last_nb = 0;
+    // member discovery (gzpx_*_device calls that take no member table): scratch of one scan at a time, used under `mu`
+    MemberScanScratch ms;
+    size_t ms_seg_cap = 0;
+    uint32_t *h_rec = nullptr;  // pinned: the scan record
+    uint64_t *d_tab_off = nullptr;  // the walk's table for gzpx_scan_blocks_device
+    uint32_t *d_tab_size = nullptr;
+    size_t tab_cap = 0;
+    hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;  // around the scan kernels
+    bool have_scan = false;
     std::mutex mu;
     std::condition_variable cv_slot;
 };
 
 namespace {
 
+// what the device's walk found (dscan_run): the table itself stays in the context's scratch for launch_member_emit
+struct ScanResult {
+    size_t n_members = 0;  // whole members in front of the walk's end
+    size_t consumed = 0;   // where it ended
+    bool invalid = false;  // ... at a header that fails the checks (a cap below n_members stops the walk before it sees that)
+};
+
 int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, size_t in_len,
                     const uint64_t *offsets, const uint32_t *sizes, size_t nb, uint8_t *host_out, uint8_t *d_out,
                     size_t out_cap, hipStream_t after, bool block_for_slot, std::unique_lock<std::mutex> &lk,
-                    uint64_t *ticket);
+                    uint64_t *ticket, const ScanResult *scan = nullptr);
 
 // As on the compress side (submit_locked): a submit that fails may already have put copies and kernels on the
 // streams -- the copy-in still reads the caller's `in`, the copy-out may still write the caller's `out` -- and
@@ -1598,9 +1614,9 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
 int dsubmit_locked(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, size_t in_len,
                    const uint64_t *offsets, const uint32_t *sizes, size_t nb, uint8_t *host_out, uint8_t *d_out,
                    size_t out_cap, hipStream_t after, bool block_for_slot, std::unique_lock<std::mutex> &lk,
-                   uint64_t *ticket) {
+                   uint64_t *ticket, const ScanResult *scan = nullptr) {
     const int rc = dsubmit_enqueue(c, host_in, d_in, in_len, offsets, sizes, nb, host_out, d_out, out_cap, after,
-                                   block_for_slot, lk, ticket);
+                                   block_for_slot, lk, ticket, scan);
     if (rc != GZPX_OK && rc != GZPX_ERR_BUSY && rc != GZPX_ERR_INVALID_ARG) {
         (void)hipStreamSynchronize(c->s_h2d);
         (void)hipStreamSynchronize(c->stream);
@@ -1612,11 +1628,13 @@ int dsubmit_locked(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, si
 int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, size_t in_len,
                     const uint64_t *offsets, const uint32_t *sizes, size_t nb, uint8_t *host_out, uint8_t *d_out,
                     size_t out_cap, hipStream_t after, bool block_for_slot, std::unique_lock<std::mutex> &lk,
-                    uint64_t *ticket) {
-    if (nb && (!offsets || !sizes || (!host_in && !d_in))) return GZPX_ERR_INVALID_ARG;
+                    uint64_t *ticket, const ScanResult *scan) {
+    // `scan`: the members are the first nb of the walk dscan_run has just made over d_in (the table is still in the
+    // context's scratch); what the loop below checks of a caller's table, the walk guarantees of its own
+    if (nb && ((!scan && (!offsets || !sizes)) || (!host_in && !d_in) || (scan && !d_in))) return GZPX_ERR_INVALID_ARG;
     if (nb > 0xFFFFFFFFull) return GZPX_ERR_INVALID_ARG;
     const uint32_t hdr_len = c->format == GZPX_FORMAT_BGZF ? 18 : 20;
-    for (size_t b = 0; b < nb; b++)
+    for (size_t b = 0; b < nb && !scan; b++)
         if (sizes[b] < hdr_len + 8 || offsets[b] > in_len || sizes[b] > in_len - offsets[b]) return GZPX_ERR_INVALID_ARG;
     int si = -1;
     for (;;) {
@@ -1657,16 +1675,20 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
             HIP_TRY(hipEventRecord(c->ev_dep, after));
             HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
         }
-        memcpy(sl.h_offsets, offsets, nb * 8);
-        memcpy(sl.h_sizes, sizes, nb * 4);
-        HIP_TRY(hipMemcpyAsync(sl.d_offsets, sl.h_offsets, nb * 8, hipMemcpyHostToDevice, c->s_h2d));
-        HIP_TRY(hipMemcpyAsync(sl.d_sizes, sl.h_sizes, nb * 4, hipMemcpyHostToDevice, c->s_h2d));
-        HIP_TRY(hipEventRecord(sl.ev_h2d, c->s_h2d));
-        HIP_TRY(hipStreamWaitEvent(stream, sl.ev_h2d, 0));
+        if (scan) {  // the table goes from the scan's scratch to the slot's on the device
+            launch_member_emit(c->ms, (uint32_t)nb, sl.d_offsets, sl.d_sizes, stream);
+        } else {
+            memcpy(sl.h_offsets, offsets, nb * 8);
+            memcpy(sl.h_sizes, sizes, nb * 4);
+            HIP_TRY(hipMemcpyAsync(sl.d_offsets, sl.h_offsets, nb * 8, hipMemcpyHostToDevice, c->s_h2d));
+            HIP_TRY(hipMemcpyAsync(sl.d_sizes, sl.h_sizes, nb * 4, hipMemcpyHostToDevice, c->s_h2d));
+            HIP_TRY(hipEventRecord(sl.ev_h2d, c->s_h2d));
+            HIP_TRY(hipStreamWaitEvent(stream, sl.ev_h2d, 0));
+        }
         sl.sc.n_cu = c->n_cu;
         {
-            uint64_t csum = 0;
-            for (size_t b = 0; b < nb; b++) csum += sizes[b];
+            uint64_t csum = scan ? scan->consumed : 0;  // (the members of a walk lie back to back from offset 0)
+            for (size_t b = 0; b < nb && !scan; b++) csum += sizes[b];
             sl.sc.big_members = nb && csum / nb >= 131072u ? 1 : 0;
         }
         if (c->route == kInflateRouteSeg) {  // scratch of the decode / copy pair, sized by what the caller can take
@@ -1765,6 +1787,108 @@ int dwait_ticket(gzpx_dctx *c, uint64_t ticket, size_t *out_len, gzpx_check_info
     return rc;
 }
 
+void dscan_free(gzpx_dctx *c) {
+    MemberScanScratch &m = c->ms;
+    for (void *p : {(void *)m.pos, (void *)m.size, (void *)m.succ, (void *)m.jump[0], (void *)m.jump[1], (void *)m.idx})
+        if (p) (void)hipFree(p);
+    m.pos = nullptr;
+    m.size = m.succ = m.jump[0] = m.jump[1] = m.idx = nullptr;
+    m.cap = 0;
+}
+
+int dscan_reserve(gzpx_dctx *c, size_t n_seg, size_t cap) {
+    MemberScanScratch &m = c->ms;
+    if (!m.rec) {
+        HIP_TRY(hipMalloc((void **)&m.rec, 64));
+        HIP_TRY(hipHostMalloc((void **)&c->h_rec, 64, hipHostMallocDefault));
+        HIP_TRY(hipEventCreate(&c->ev_s0));
+        HIP_TRY(hipEventCreate(&c->ev_s1));
+    }
+    if (n_seg > c->ms_seg_cap) {
+        if (m.seg_count) (void)hipFree(m.seg_count);
+        if (m.seg_off) (void)hipFree(m.seg_off);
+        m.seg_count = m.seg_off = nullptr;
+        c->ms_seg_cap = 0;
+        HIP_TRY(hipMalloc((void **)&m.seg_count, n_seg * 4));
+        HIP_TRY(hipMalloc((void **)&m.seg_off, n_seg * 4));
+        c->ms_seg_cap = n_seg;
+    }
+    if (cap > m.cap) {
+        dscan_free(c);
+        HIP_TRY(hipMalloc((void **)&m.pos, cap * 8));
+        HIP_TRY(hipMalloc((void **)&m.size, cap * 4));
+        HIP_TRY(hipMalloc((void **)&m.succ, cap * 4));
+        HIP_TRY(hipMalloc((void **)&m.jump[0], cap * 4));
+        HIP_TRY(hipMalloc((void **)&m.jump[1], cap * 4));
+        HIP_TRY(hipMalloc((void **)&m.idx, cap * 4));
+        m.cap = (uint32_t)cap;
+    }
+    return GZPX_OK;
+}
+
+// gzpx_scan_blocks over d_in[0..in_len) on the device, without the cap: how many members the walk from offset 0
+// records and where it stops.  Returns synchronised; the table stays in c->ms (launch_member_emit) until the next
+// scan of this context.  Called with c->mu held.
+int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t after, ScanResult *r) {
+    *r = ScanResult();
+    c->have_scan = false;
+    const size_t hdr = c->format == GZPX_FORMAT_BGZF ? 18 : 20;
+    if (in_len < hdr) return GZPX_OK;  // read_exact(header) finds nothing to read
+    hipStream_t stream = c->stream;
+    if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {
+        HIP_TRY(hipEventRecord(c->ev_dep, after));
+        HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
+    }
+    // one wave per segment; 16 KiB each, larger where that keeps the single-workgroup scan of their counts short
+    const size_t span = ((uintptr_t)d_in & 15u) + in_len;
+    size_t seg_bytes = 16384;
+    while ((span + seg_bytes - 1) / seg_bytes > 65536 && seg_bytes < ((size_t)1 << 30)) seg_bytes *= 2;
+    const size_t n_seg = (span + seg_bytes - 1) / seg_bytes;
+    if (n_seg > 0xFFFFFFFFull) return GZPX_ERR_INVALID_ARG;
+    // Candidates: the members (in our own streams one per 20-odd KiB) and about one impostor per 2^17 bytes of
+    // compressed data.  A stream of tiny members, or one built to look like that, finds the arrays too small: the
+    // record says by how much, and the scan runs once more.
+    const size_t kCapMax = 0xFFFFFFF0ull;
+    size_t cap = in_len / 2048 + 4096;
+    if (cap < c->ms.cap) cap = c->ms.cap;
+    if (cap > kCapMax) cap = kCapMax;
+    for (int attempt = 0;; attempt++) {
+        const int rc = dscan_reserve(c, n_seg, cap);
+        if (rc != GZPX_OK) return rc;
+        // a walk has at most min(candidates, in_len / smallest member) members: that many indices to hand out
+        size_t chain = in_len / (hdr + 8) + 1;
+        if (chain > c->ms.cap) chain = c->ms.cap;
+        uint32_t rounds = 0;
+        while (rounds < 32 && ((size_t)1 << rounds) < chain) rounds++;
+        if (attempt == 0) HIP_TRY(hipEventRecord(c->ev_s0, stream));
+        launch_member_scan(c->format, d_in, in_len, (uint32_t)seg_bytes, (uint32_t)n_seg, rounds, c->ms, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_s1, stream));
+        HIP_TRY(hipMemcpyAsync(c->h_rec, c->ms.rec, 32, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        const size_t n_cand = c->h_rec[0];
+        if (n_cand <= c->ms.cap) break;
+        if (n_cand > kCapMax || attempt) return GZPX_ERR_DEVICE;  // (more candidates than the 32-bit indices address)
+        cap = n_cand + n_cand / 8 + 64;
+        if (cap > kCapMax) cap = kCapMax;
+    }
+    c->have_scan = true;
+    r->invalid = c->h_rec[2] != 0;
+    r->n_members = c->h_rec[1];
+    r->consumed = (size_t)((uint64_t)c->h_rec[4] | ((uint64_t)c->h_rec[5] << 32));
+    return GZPX_OK;
+}
+
+// the calls that scan and then use a slot hold c->mu from the scan to the submit (the scan's scratch is the
+// context's): they wait for the slot first
+void dwait_free_slot(gzpx_dctx *c, std::unique_lock<std::mutex> &lk) {
+    for (;;) {
+        for (int i = 0; i < kSlots; i++)
+            if (c->slots[i].state == 0) return;
+        c->cv_slot.wait(lk);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1818,6 +1942,12 @@ void gzpx_dctx_destroy(gzpx_dctx *c) {
         for (hipEvent_t e : {sl.ev_h2d, sl.ev_kernels, sl.ev_done, sl.ev_t0, sl.ev_t1, sl.ev_tm})
             if (e) (void)hipEventDestroy(e);
     }
+    dscan_free(c);
+    for (void *p : {(void *)c->ms.seg_count, (void *)c->ms.seg_off, (void *)c->ms.rec, (void *)c->d_tab_off, (void *)c->d_tab_size})
+        if (p) (void)hipFree(p);
+    if (c->h_rec) (void)hipHostFree(c->h_rec);
+    for (hipEvent_t e : {c->ev_s0, c->ev_s1})
+        if (e) (void)hipEventDestroy(e);
     if (c->ev_dep) (void)hipEventDestroy(c->ev_dep);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->s_h2d) (void)hipStreamDestroy(c->s_h2d);
@@ -1886,6 +2016,123 @@ int gzpx_decompress_blocks_device(gzpx_dctx *c, const void *d_in, size_t in_len,
     }
     if (rc != GZPX_OK) return rc;
     return dwait_ticket(c, ticket, out_len, info);
+}
+
+int gzpx_scan_blocks_device(gzpx_dctx *c, const void *d_in, size_t in_len, uint64_t *offsets, uint32_t *sizes,
+                            size_t max_blocks, size_t *n_blocks, size_t *consumed, void *hip_stream) {
+    if (!c || (!d_in && in_len) || !n_blocks || !consumed) return GZPX_ERR_INVALID_ARG;
+    *n_blocks = 0;
+    *consumed = 0;
+    std::unique_lock<std::mutex> lk(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    ScanResult r;
+    const int rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r);
+    if (rc != GZPX_OK) return rc;
+    const bool tables = offsets && sizes;  // (no tables: the cap is not looked at, as on the host)
+    if (r.invalid && !(tables && max_blocks < r.n_members)) return GZPX_ERR_INVALID_HEADER;
+    if (!tables || r.n_members == 0) {
+        *n_blocks = r.n_members;
+        *consumed = r.consumed;
+        return GZPX_OK;
+    }
+    // with the cap reached in front of a whole member the walk stops there: that member's offset is `consumed`
+    const bool capped = max_blocks < r.n_members;
+    const size_t n = capped ? max_blocks : r.n_members, n_emit = capped ? n + 1 : n;
+    if (n_emit > c->tab_cap) {
+        if (c->d_tab_off) (void)hipFree(c->d_tab_off);
+        if (c->d_tab_size) (void)hipFree(c->d_tab_size);
+        c->d_tab_off = nullptr;
+        c->d_tab_size = nullptr;
+        c->tab_cap = 0;
+        HIP_TRY(hipMalloc((void **)&c->d_tab_off, (n_emit + n_emit / 4 + 64) * 8));
+        HIP_TRY(hipMalloc((void **)&c->d_tab_size, (n_emit + n_emit / 4 + 64) * 4));
+        c->tab_cap = n_emit + n_emit / 4 + 64;
+    }
+    launch_member_emit(c->ms, (uint32_t)n_emit, c->d_tab_off, c->d_tab_size, c->stream);
+    HIP_TRY(hipGetLastError());
+    uint64_t stop = 0;
+    if (n) HIP_TRY(hipMemcpyAsync(offsets, c->d_tab_off, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(sizes, c->d_tab_size, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (capped) HIP_TRY(hipMemcpyAsync(&stop, c->d_tab_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *n_blocks = n;
+    *consumed = capped ? (size_t)stop : r.consumed;
+    return GZPX_OK;
+}
+
+int gzpx_decompress_stream_device(gzpx_dctx *c, const void *d_in, size_t in_len, void *d_out, size_t out_cap,
+                                  size_t *out_len, size_t *n_blocks, size_t *consumed, gzpx_check_info *info,
+                                  void *hip_stream) {
+    if (!c || (!d_in && in_len) || !out_len || !n_blocks || !consumed) return GZPX_ERR_INVALID_ARG;
+    *out_len = 0;
+    *n_blocks = 0;
+    *consumed = 0;
+    uint64_t ticket = 0;
+    int rc;
+    {
+        std::unique_lock<std::mutex> lk(c->mu);
+        if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+        dwait_free_slot(c, lk);
+        ScanResult r;
+        rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r);
+        if (rc != GZPX_OK) return rc;
+        if (r.invalid) return GZPX_ERR_INVALID_HEADER;
+        *n_blocks = r.n_members;
+        *consumed = r.consumed;
+        if (r.n_members == 0) return GZPX_OK;
+        rc = dsubmit_locked(c, nullptr, (const uint8_t *)d_in, in_len, nullptr, nullptr, r.n_members, nullptr,
+                            (uint8_t *)d_out, out_cap, (hipStream_t)hip_stream, true, lk, &ticket, &r);
+    }
+    if (rc != GZPX_OK) return rc;
+    return dwait_ticket(c, ticket, out_len, info);
+}
+
+int gzpx_index_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx_index_entry *entries, size_t max_entries,
+                      size_t *n_entries, size_t *consumed, uint64_t *inflated_len, void *hip_stream) {
+    if (!c || (!d_in && in_len) || !n_entries || !consumed) return GZPX_ERR_INVALID_ARG;
+    *n_entries = 0;
+    *consumed = 0;
+    if (inflated_len) *inflated_len = 0;
+    std::unique_lock<std::mutex> lk(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    dwait_free_slot(c, lk);
+    ScanResult r;
+    const int rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r);
+    if (rc != GZPX_OK) return rc;
+    if (r.invalid) return GZPX_ERR_INVALID_HEADER;
+    *n_entries = r.n_members;
+    *consumed = r.consumed;
+    if (r.n_members == 0) return GZPX_OK;
+    if (r.n_members > 0xFFFFFFFFull) return GZPX_ERR_INVALID_ARG;
+    DSlot *slp = nullptr;
+    for (DSlot &s : c->slots)
+        if (s.state == 0 && !slp) slp = &s;
+    DSlot &sl = *slp;  // (its tables only; the slot stays free, the call returns synchronised under the lock)
+    const int rr = dslot_reserve(sl, r.n_members);
+    if (rr != GZPX_OK) return rr;
+    const uint32_t nb = (uint32_t)r.n_members;
+    launch_member_emit(c->ms, nb, sl.d_offsets, sl.d_sizes, c->stream);
+    launch_member_index((const uint8_t *)d_in, sl.d_offsets, sl.d_sizes, nb, sl.d_blk, sl.d_out_off, c->stream);
+    HIP_TRY(hipGetLastError());
+    const size_t n_copy = entries ? (r.n_members < max_entries ? r.n_members : max_entries) : 0;
+    std::vector<uint64_t> un(n_copy);
+    if (n_copy) {
+        HIP_TRY(hipMemcpyAsync(sl.h_offsets, sl.d_offsets, n_copy * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(un.data(), sl.d_out_off, n_copy * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(sl.h_total, sl.d_out_off + nb, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n_copy; i++) entries[i] = gzpx_index_entry{sl.h_offsets[i], un[i]};
+    if (inflated_len) *inflated_len = *sl.h_total;
+    return GZPX_OK;
+}
+
+int gzpx_dctx_last_scan_ms(gzpx_dctx *ctx, float *ms) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    *ms = 0.0f;
+    if (!ctx->have_scan) return GZPX_OK;
+    return hipEventElapsedTime(ms, ctx->ev_s0, ctx->ev_s1) == hipSuccess ? GZPX_OK : GZPX_ERR_DEVICE;
 }
 
 int gzpx_decompress_blocks(gzpx_dctx *c, const uint8_t *in, size_t in_len, const uint64_t *offsets,

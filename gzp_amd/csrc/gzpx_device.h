@@ -201,6 +201,26 @@ void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_off
                     uint32_t *d_crc_found, const CrcConsts &cc, int debug, hipEvent_t ev_begin,
                     hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc, int route, hipEvent_t ev_mid = nullptr);
 
+// Member discovery on the device (gzpx_mscan.h): the candidate headers of a stream, sorted by position, and what the
+// chain from offset 0 makes of them.
+struct MemberScanScratch {
+    uint32_t *seg_count = nullptr;  // [segments] candidates in each segment of the stream
+    uint32_t *seg_off = nullptr;    // [segments] their exclusive prefix sum
+    uint64_t *pos = nullptr;        // [cap] candidate positions
+    uint32_t *size = nullptr;       // [cap] the member sizes their headers state
+    uint32_t *succ = nullptr;       // [cap] index of the candidate at pos + size, or a terminal
+    uint32_t *jump[2] = {nullptr, nullptr};  // [cap] pointer doubling, ping-pong
+    uint32_t *idx = nullptr;        // [cap] index in the walk from offset 0, 0xFFFFFFFF for impostors
+    uint32_t *rec = nullptr;        // [8] the scan record: candidates, members, kind of end, consumed (u64 at [4])
+    uint32_t cap = 0;
+};
+void launch_member_scan(int format, const uint8_t *d_in, uint64_t in_len, uint32_t seg_bytes, uint32_t n_seg,
+                        uint32_t rounds, const MemberScanScratch &m, hipStream_t stream);
+void launch_member_emit(const MemberScanScratch &m, uint32_t n_emit, uint64_t *d_offsets, uint32_t *d_sizes,
+                        hipStream_t stream);
+void launch_member_index(const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes, uint32_t nb, void *d_blk,
+                         uint64_t *d_out_off, hipStream_t stream);
+
 // gzpx_check.hip: (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);
 

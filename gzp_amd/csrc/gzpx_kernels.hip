@@ -5557,6 +5557,7 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
 
 #include "gzpx_inflate_seg.h"
 #include "gzpx_snap.h"
+#include "gzpx_mscan.h"
 
 // CRC-32 of the inflated blocks (LibDeflateCrc over the whole orig_size buffer, src/check.rs:45-71):
 // the workgroup routine of k_crc32, blocks addressed through their output offsets.
@@ -5851,6 +5852,50 @@ void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_off
                        (const uint64_t *)d_out_off, (const DBlock *)blk, d_crc_found, cc);
     if (sc.summary)
         hipLaunchKernelGGL(k_dsummary, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, (const uint32_t *)d_crc_found, sc.summary);
+}
+
+// Member discovery (gzpx_mscan.h).  Everything the later kernels need to know about the candidates they work on is
+// read from the scan record on the device, so the whole sequence is enqueued without a host round trip; grids are
+// sized by the capacity of the candidate arrays.
+void launch_member_scan(int format, const uint8_t *d_in, uint64_t in_len, uint32_t seg_bytes, uint32_t n_seg,
+                        uint32_t rounds, const MemberScanScratch &m, hipStream_t stream) {
+    MsStream s;
+    s.in = d_in;
+    s.len = in_len;
+    s.lead = (uint32_t)((uintptr_t)d_in & 15u);
+    s.hdr = format == 0 ? 18u : 20u;
+    s.sid = format == 0 ? ('B' | ('C' << 8)) : ('I' | ('G' << 8));
+    s.seg_words = seg_bytes / 16u;
+    const uint32_t cand_grid = (n_seg + kMsThreads / 64u - 1u) / (kMsThreads / 64u);
+    const uint32_t g = m.cap / 256u + 1u < 2048u ? m.cap / 256u + 1u : 2048u;
+    hipLaunchKernelGGL((k_mscan_cand<false>), dim3(cand_grid), dim3(kMsThreads), 0, stream, s, n_seg, m.seg_count,
+                       (const uint32_t *)nullptr, (const uint32_t *)nullptr, m.cap, (uint64_t *)nullptr, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_mscan_offsets, dim3(1), dim3(256), 0, stream, n_seg, (const uint32_t *)m.seg_count, m.seg_off, m.rec);
+    hipLaunchKernelGGL((k_mscan_cand<true>), dim3(cand_grid), dim3(kMsThreads), 0, stream, s, n_seg, m.seg_count,
+                       (const uint32_t *)m.seg_off, (const uint32_t *)m.rec, m.cap, m.pos, m.size);
+    hipLaunchKernelGGL(k_mscan_succ, dim3(g), dim3(256), 0, stream, in_len, s.hdr, m.cap, m.rec, (const uint64_t *)m.pos,
+                       (const uint32_t *)m.size, m.succ, m.jump[0], m.idx);
+    for (uint32_t r = 0; r < rounds; r++)
+        hipLaunchKernelGGL(k_mscan_jump, dim3(g), dim3(256), 0, stream, r, m.cap, (const uint32_t *)m.rec,
+                           (const uint32_t *)m.jump[r & 1u], m.jump[(r & 1u) ^ 1u], m.idx);
+    hipLaunchKernelGGL(k_mscan_finish, dim3(g), dim3(256), 0, stream, m.cap, m.rec, (const uint64_t *)m.pos,
+                       (const uint32_t *)m.size, (const uint32_t *)m.succ, (const uint32_t *)m.idx);
+}
+
+void launch_member_emit(const MemberScanScratch &m, uint32_t n_emit, uint64_t *d_offsets, uint32_t *d_sizes,
+                        hipStream_t stream) {
+    const uint32_t g = m.cap / 256u + 1u < 2048u ? m.cap / 256u + 1u : 2048u;
+    hipLaunchKernelGGL(k_mscan_emit, dim3(g), dim3(256), 0, stream, m.cap, (const uint32_t *)m.rec, n_emit,
+                       (const uint64_t *)m.pos, (const uint32_t *)m.size, (const uint32_t *)m.idx, d_offsets, d_sizes);
+}
+
+// the footers of nb members and the exclusive prefix sum of their ISIZE fields (d_out_off[nb] = the total)
+void launch_member_index(const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes, uint32_t nb, void *d_blk,
+                         uint64_t *d_out_off, hipStream_t stream) {
+    DBlock *blk = (DBlock *)d_blk;
+    hipLaunchKernelGGL(k_dinit, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, d_in, d_offsets, d_sizes, blk,
+                       (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_dscan, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, d_out_off);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

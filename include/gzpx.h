@@ -308,6 +308,28 @@ int gzpx_decompress_blocks_wait(gzpx_dctx *ctx, uint64_t ticket, size_t *out_len
 int gzpx_decompress_blocks_device(gzpx_dctx *ctx, const void *d_in, size_t in_len, const uint64_t *offsets,
                                   const uint32_t *sizes, size_t n_blocks, void *d_out, size_t out_cap,
                                   size_t *out_len, gzpx_check_info *info, void *hip_stream);
+/* ---- the same for a stream that lies in device memory: the members are found on the device (gzpx_mscan.h), no
+ * member table and no byte of the stream crosses to the host first.  hip_stream as for gzpx_decompress_blocks_device. */
+/* gzpx_scan_blocks for a stream in device memory.  offsets / sizes: optional HOST arrays (both or neither);
+ * result identical to gzpx_scan_blocks on the same bytes, for every input and every max_blocks. */
+int gzpx_scan_blocks_device(gzpx_dctx *ctx, const void *d_in, size_t in_len, uint64_t *offsets, uint32_t *sizes,
+                            size_t max_blocks, size_t *n_blocks, size_t *consumed, void *hip_stream);
+/* scan + inflate with no member table crossing to the host: every complete member of d_in[0..in_len) is inflated
+ * to d_out back to back; *consumed as above (a trailing partial member is the caller's).  An invalid header:
+ * GZPX_ERR_INVALID_HEADER, nothing inflated.  Otherwise as gzpx_decompress_blocks_device with the walk's table. */
+int gzpx_decompress_stream_device(gzpx_dctx *ctx, const void *d_in, size_t in_len, void *d_out, size_t out_cap,
+                                  size_t *out_len, size_t *n_blocks, size_t *consumed, gzpx_check_info *info,
+                                  void *hip_stream);
+/* the block index of a stream nobody here wrote: one entry per member as a reader sees them (so the BGZF EOF
+ * marker is an entry; gzpx_par_index, the writer's view, has none for it), compressed offset = member start,
+ * uncompressed offset = exclusive prefix sum of the footers' ISIZE; *inflated_len = the total.  entries: host array
+ * (may be NULL), the first max_entries are written, *n_entries = how many there are. */
+int gzpx_index_device(gzpx_dctx *ctx, const void *d_in, size_t in_len, gzpx_index_entry *entries,
+                      size_t max_entries, size_t *n_entries, size_t *consumed, uint64_t *inflated_len,
+                      void *hip_stream);
+/* HIP-event duration of the member-discovery kernels in the last of these three calls on this context (a scan whose
+ * candidate arrays were too small ran twice: both runs and the reallocation between them are inside) */
+int gzpx_dctx_last_scan_ms(gzpx_dctx *ctx, float *ms);
 typedef struct gzpx_decompressor gzpx_decompressor;
 gzpx_decompressor *gzpx_alloc_decompressor(void);
 /* 0 = ok (short output allowed, *actual = bytes produced), GZPX_ERR_BAD_DATA, GZPX_ERR_INSUFFICIENT_SPACE */

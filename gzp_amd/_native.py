@@ -40,6 +40,7 @@ COMPAT_1_10 = 1
 STREAM_NONE = ctypes.c_void_p(-1).value  # GZPX_STREAM_NONE: the caller has synchronized, no stream dependency
 N_STAGES = 9
 INFLATE_SEG, INFLATE_WAVE = 0, 1
+RANGE_UNCOMPRESSED, RANGE_VIRTUAL = 0, 1
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -62,6 +63,8 @@ EXPORTS = [
     "gzpx_ctx_active_compat", "gzpx_build_id", "gzpx_multi_create", "gzpx_multi_destroy", "gzpx_multi_devices", "gzpx_multi_compress_slab",
     "gzpx_multi_shard", "gzpx_multi_compress_slab_device", "gzpx_debug_snap",
     "gzpx_scan_blocks_device", "gzpx_decompress_stream_device", "gzpx_index_device", "gzpx_dctx_last_scan_ms",
+    "gzpx_dindex_build_device", "gzpx_dindex_entries", "gzpx_dindex_destroy", "gzpx_read_ranges_device",
+    "gzpx_dctx_last_ranges_members", "gzpx_dctx_last_ranges_ms",
 ]
 
 
@@ -86,10 +89,13 @@ WRITE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes
 
 
 class GzpxError(RuntimeError):
-    def __init__(self, code, msg, block=None):
-        super().__init__("gzpx error %d: %s%s" % (code, msg, "" if block is None else " (block %d)" % block))
+    def __init__(self, code, msg, block=None, range_index=None, needed=None):
+        super().__init__("gzpx error %d: %s%s%s" % (code, msg, "" if block is None else " (block %d)" % block,
+                                                   "" if range_index is None else " (range %d)" % range_index))
         self.code = code
         self.block = block
+        self.range_index = range_index  # read_ranges_device: the first range that is invalid
+        self.needed = needed            # read_ranges_device, ERR_INSUFFICIENT_SPACE in front of the inflate: bytes of output
 
 
 class GzpxLib:
@@ -223,6 +229,19 @@ class GzpxLib:
         L.gzpx_index_device.argtypes = [vp, vp, sz, vp, sz, psz, psz, pu64, vp]
         L.gzpx_dctx_last_scan_ms.restype = i32
         L.gzpx_dctx_last_scan_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_dindex_build_device.restype = i32
+        L.gzpx_dindex_build_device.argtypes = [vp, vp, sz, ctypes.POINTER(vp), psz, psz, pu64, vp]
+        L.gzpx_dindex_entries.restype = i32
+        L.gzpx_dindex_entries.argtypes = [vp, vp, sz, psz]
+        L.gzpx_dindex_destroy.restype = None
+        L.gzpx_dindex_destroy.argtypes = [vp]
+        L.gzpx_read_ranges_device.restype = i32
+        L.gzpx_read_ranges_device.argtypes = [vp, vp, vp, sz, vp, sz, i32, vp, sz, psz, vp, psz,
+                                              ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_ranges_members.restype = i32
+        L.gzpx_dctx_last_ranges_members.argtypes = [vp, psz]
+        L.gzpx_dctx_last_ranges_ms.restype = i32
+        L.gzpx_dctx_last_ranges_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_alloc_decompressor.restype = vp
         L.gzpx_alloc_decompressor.argtypes = []
         L.gzpx_deflate_decompress.restype = i32
@@ -807,6 +826,81 @@ class DContext:
         ms = ctypes.c_float(0)
         self.lib.check(self.lib.L.gzpx_dctx_last_scan_ms(self.h, ctypes.byref(ms)))
         return ms.value
+
+    # ---- random access by range (gzpx_ranges.h)
+    def build_index_device(self, d_in_ptr, in_len, stream=None):
+        """The index of d_in[0..in_len), kept in device memory: a DIndex for read_ranges_device."""
+        h = ctypes.c_void_p()
+        n, used, total = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
+        self.lib.check(self.lib.L.gzpx_dindex_build_device(self.h, d_in_ptr, in_len, ctypes.byref(h), ctypes.byref(n),
+                                                           ctypes.byref(used), ctypes.byref(total), stream))
+        return DIndex(self.lib, h, n.value, used.value, total.value)
+
+    def read_ranges_device(self, index, d_in_ptr, in_len, ranges, d_out_ptr, out_cap, coords="uncompressed", stream=None):
+        """ranges[n, 2] (begin, end) of the inflated stream -- or BGZF virtual offsets with coords="virtual" -- into
+        d_out back to back: (out_len, out_offsets uint64[n + 1]).  Only the members the ranges touch are inflated.  A
+        bad range raises GzpxError with .range_index; too small an out_cap raises it with .needed."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+        mode = {"uncompressed": RANGE_UNCOMPRESSED, "virtual": RANGE_VIRTUAL}[coords]
+        offs = np.zeros(r.shape[0] + 1, dtype=np.uint64)
+        out_len, bad = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_read_ranges_device(self.h, index.h, d_in_ptr, in_len, r.ctypes.data, r.shape[0], mode,
+                                                d_out_ptr, out_cap, ctypes.byref(out_len), offs.ctypes.data,
+                                                ctypes.byref(bad), ctypes.byref(info), stream)
+        if rc == OK:
+            return out_len.value, offs
+        if bad.value != ctypes.c_size_t(-1).value:
+            raise GzpxError(rc, "range %d does not lie in the stream" % bad.value, range_index=bad.value)
+        if rc == ERR_INSUFFICIENT_SPACE and out_len.value:
+            raise GzpxError(rc, "the ranges hold %d bytes" % out_len.value, needed=out_len.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def last_ranges_members(self):
+        """Members the last read_ranges_device inflated: the union of the ranges' [first, last]."""
+        n = ctypes.c_size_t(0)
+        self.lib.check(self.lib.L.gzpx_dctx_last_ranges_members(self.h, ctypes.byref(n)))
+        return n.value
+
+    def last_ranges_ms(self):
+        """HIP-event durations of the last read_ranges_device: (locate + select, inflate, gather)."""
+        ms = (ctypes.c_float * 3)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_ranges_ms(self.h, ms))
+        return ms[0], ms[1], ms[2]
+
+
+class DIndex:
+    """gzpx_dindex: the member index of a device-resident stream, in device memory (DContext.build_index_device)."""
+
+    def __init__(self, lib, h, n_members, consumed, inflated_len):
+        self.lib, self.h = lib, h
+        self.n_members, self.consumed, self.inflated_len = n_members, consumed, inflated_len
+
+    def entries(self):
+        """idx[n, 2] uint64 = (compressed offset, uncompressed offset), as DContext.index_device returns."""
+        n = ctypes.c_size_t(0)
+        idx = np.zeros((max(self.n_members, 1), 2), dtype=np.uint64)
+        self.lib.check(self.lib.L.gzpx_dindex_entries(self.h, idx.ctypes.data, self.n_members, ctypes.byref(n)))
+        return idx[:n.value]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.L.gzpx_dindex_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class Decompressor:

@@ -1514,6 +1514,7 @@ struct DSlot {
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // around the inflate kernels (timing enabled)
     hipEvent_t ev_tm = nullptr;                   // behind k_inflate_seg (the decode / copy route)
     size_t nb = 0;
+    int route = kInflateRouteSeg;  // the route of the slot's last launch (the context's may have changed since)
 };
 
 void dslot_free_tables(DSlot &c) {
@@ -1590,6 +1591,18 @@ struct gzpx_dctx {
     size_t tab_cap = 0;
     hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;  // around the scan kernels
     bool have_scan = false;
+    // reads by range (gzpx_read_ranges_device): scratch of one call at a time, used under `mu`
+    RangeScratch rr;
+    size_t rr_range_cap = 0, rr_member_cap = 0;
+    uint64_t *h_ranges = nullptr;   // pinned: the caller's ranges on their way in
+    uint64_t *h_out_off = nullptr;  // pinned: out_offsets on their way out
+    uint32_t *h_rrec = nullptr;     // pinned: the record of locate + select
+    uint8_t *d_stage = nullptr;     // the selected members, inflated back to back
+    size_t stage_cap = 0;
+    hipEvent_t ev_r[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // select [0..1], inflate [2..3], gather [3..4]
+    bool have_rr = false;           // ev_r[0..1] hold the last call's select; rr_stages: [2..4] its inflate and gather
+    bool rr_stages = false;
+    size_t last_rr_members = 0;
     std::mutex mu;
     std::condition_variable cv_slot;
 };
@@ -1607,6 +1620,26 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
                     const uint64_t *offsets, const uint32_t *sizes, size_t nb, uint8_t *host_out, uint8_t *d_out,
                     size_t out_cap, hipStream_t after, bool block_for_slot, std::unique_lock<std::mutex> &lk,
                     uint64_t *ticket, const ScanResult *scan = nullptr);
+
+// k_inflate_seg + k_lzcopy's match records and tile table for nb members that inflate to at most out_cap bytes
+int dslot_seg_scratch(DSlot &sl, size_t out_cap, size_t nb) {
+    const size_t need_m = inflate_mlist_bytes(out_cap, nb), need_t = inflate_tfirst_bytes(out_cap, nb);
+    if (need_m > sl.mlist_cap) {
+        if (sl.sc.mlist) (void)hipFree(sl.sc.mlist);
+        sl.sc.mlist = nullptr;
+        sl.mlist_cap = 0;
+        HIP_TRY(hipMalloc(&sl.sc.mlist, need_m + need_m / 8));
+        sl.mlist_cap = need_m + need_m / 8;
+    }
+    if (need_t > sl.tfirst_cap) {
+        if (sl.sc.tfirst) (void)hipFree(sl.sc.tfirst);
+        sl.sc.tfirst = nullptr;
+        sl.tfirst_cap = 0;
+        HIP_TRY(hipMalloc((void **)&sl.sc.tfirst, need_t + need_t / 8));
+        sl.tfirst_cap = need_t + need_t / 8;
+    }
+    return GZPX_OK;
+}
 
 // As on the compress side (submit_locked): a submit that fails may already have put copies and kernels on the
 // streams -- the copy-in still reads the caller's `in`, the copy-out may still write the caller's `out` -- and
@@ -1691,22 +1724,10 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
             for (size_t b = 0; b < nb && !scan; b++) csum += sizes[b];
             sl.sc.big_members = nb && csum / nb >= 131072u ? 1 : 0;
         }
+        sl.route = c->route;
         if (c->route == kInflateRouteSeg) {  // scratch of the decode / copy pair, sized by what the caller can take
-            const size_t need_m = inflate_mlist_bytes(out_cap, nb), need_t = inflate_tfirst_bytes(out_cap, nb);
-            if (need_m > sl.mlist_cap) {
-                if (sl.sc.mlist) (void)hipFree(sl.sc.mlist);
-                sl.sc.mlist = nullptr;
-                sl.mlist_cap = 0;
-                HIP_TRY(hipMalloc(&sl.sc.mlist, need_m + need_m / 8));
-                sl.mlist_cap = need_m + need_m / 8;
-            }
-            if (need_t > sl.tfirst_cap) {
-                if (sl.sc.tfirst) (void)hipFree(sl.sc.tfirst);
-                sl.sc.tfirst = nullptr;
-                sl.tfirst_cap = 0;
-                HIP_TRY(hipMalloc((void **)&sl.sc.tfirst, need_t + need_t / 8));
-                sl.tfirst_cap = need_t + need_t / 8;
-            }
+            rc = dslot_seg_scratch(sl, out_cap, nb);
+            if (rc != GZPX_OK) return rc;
         }
         launch_inflate(hdr_len, d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nb, sl.d_blk, sl.d_out_off, d_out, out_cap,
                        sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, c->route, sl.ev_tm);
@@ -1881,6 +1902,56 @@ int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t afte
 
 // the calls that scan and then use a slot hold c->mu from the scan to the submit (the scan's scratch is the
 // context's): they wait for the slot first
+void rr_free_ranges(gzpx_dctx *c) {
+    RangeScratch &r = c->rr;
+    for (void *p : {(void *)r.ranges, (void *)r.first, (void *)r.len, (void *)r.src, (void *)r.out_off})
+        if (p) (void)hipFree(p);
+    if (c->h_ranges) (void)hipHostFree(c->h_ranges);
+    if (c->h_out_off) (void)hipHostFree(c->h_out_off);
+    r.ranges = r.len = r.src = r.out_off = c->h_ranges = c->h_out_off = nullptr;
+    r.first = nullptr;
+    c->rr_range_cap = 0;
+}
+
+void rr_free_members(gzpx_dctx *c) {
+    RangeScratch &r = c->rr;
+    for (void *p : {(void *)r.diff, (void *)r.map, (void *)r.soff})
+        if (p) (void)hipFree(p);
+    r.diff = r.map = nullptr;
+    r.soff = nullptr;
+    c->rr_member_cap = 0;
+}
+
+int rr_reserve(gzpx_dctx *c, size_t n_ranges, size_t n_members) {
+    RangeScratch &r = c->rr;
+    if (!r.rec) {
+        HIP_TRY(hipMalloc((void **)&r.rec, 64));
+        HIP_TRY(hipHostMalloc((void **)&c->h_rrec, 64, hipHostMallocDefault));
+        for (hipEvent_t &e : c->ev_r) HIP_TRY(hipEventCreate(&e));
+    }
+    if (n_ranges > c->rr_range_cap) {
+        rr_free_ranges(c);
+        const size_t cap = n_ranges + n_ranges / 4 + 64;
+        HIP_TRY(hipMalloc((void **)&r.ranges, cap * 16));
+        HIP_TRY(hipMalloc((void **)&r.first, cap * 4));
+        HIP_TRY(hipMalloc((void **)&r.len, cap * 8));
+        HIP_TRY(hipMalloc((void **)&r.src, cap * 8));
+        HIP_TRY(hipMalloc((void **)&r.out_off, (cap + 1) * 8));
+        HIP_TRY(hipHostMalloc((void **)&c->h_ranges, cap * 16, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&c->h_out_off, (cap + 1) * 8, hipHostMallocDefault));
+        c->rr_range_cap = cap;
+    }
+    if (n_members + 1 > c->rr_member_cap) {
+        rr_free_members(c);
+        const size_t cap = n_members + n_members / 4 + 64;
+        HIP_TRY(hipMalloc((void **)&r.diff, cap * 4));
+        HIP_TRY(hipMalloc((void **)&r.map, cap * 4));
+        HIP_TRY(hipMalloc((void **)&r.soff, cap * 8));
+        c->rr_member_cap = cap;
+    }
+    return GZPX_OK;
+}
+
 void dwait_free_slot(gzpx_dctx *c, std::unique_lock<std::mutex> &lk) {
     for (;;) {
         for (int i = 0; i < kSlots; i++)
@@ -1942,6 +2013,13 @@ void gzpx_dctx_destroy(gzpx_dctx *c) {
         for (hipEvent_t e : {sl.ev_h2d, sl.ev_kernels, sl.ev_done, sl.ev_t0, sl.ev_t1, sl.ev_tm})
             if (e) (void)hipEventDestroy(e);
     }
+    rr_free_ranges(c);
+    rr_free_members(c);
+    for (void *p : {(void *)c->rr.rec, (void *)c->d_stage})
+        if (p) (void)hipFree(p);
+    if (c->h_rrec) (void)hipHostFree(c->h_rrec);
+    for (hipEvent_t e : c->ev_r)
+        if (e) (void)hipEventDestroy(e);
     dscan_free(c);
     for (void *p : {(void *)c->ms.seg_count, (void *)c->ms.seg_off, (void *)c->ms.rec, (void *)c->d_tab_off, (void *)c->d_tab_size})
         if (p) (void)hipFree(p);
@@ -2133,6 +2211,238 @@ int gzpx_dctx_last_scan_ms(gzpx_dctx *ctx, float *ms) {
     *ms = 0.0f;
     if (!ctx->have_scan) return GZPX_OK;
     return hipEventElapsedTime(ms, ctx->ev_s0, ctx->ev_s1) == hipSuccess ? GZPX_OK : GZPX_ERR_DEVICE;
+}
+
+}  // extern "C"
+
+struct gzpx_dindex {
+    int device = 0, format = 0;
+    size_t n = 0, consumed = 0;
+    uint64_t inflated_len = 0;
+    uint64_t *d_off = nullptr;     // [n]
+    uint32_t *d_size = nullptr;    // [n]
+    uint64_t *d_ustart = nullptr;  // [n + 1]
+};
+
+extern "C" {
+
+void gzpx_dindex_destroy(gzpx_dindex *ix) {
+    if (!ix) return;
+    (void)hipSetDevice(ix->device);
+    for (void *p : {(void *)ix->d_off, (void *)ix->d_size, (void *)ix->d_ustart})
+        if (p) (void)hipFree(p);
+    delete ix;
+}
+
+int gzpx_dindex_build_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx_dindex **out, size_t *n_members,
+                             size_t *consumed, uint64_t *inflated_len, void *hip_stream) {
+    if (!c || (!d_in && in_len) || !out) return GZPX_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (n_members) *n_members = 0;
+    if (consumed) *consumed = 0;
+    if (inflated_len) *inflated_len = 0;
+    std::unique_lock<std::mutex> lk(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    dwait_free_slot(c, lk);
+    ScanResult r;
+    int rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r);
+    if (rc != GZPX_OK) return rc;
+    if (r.invalid) return GZPX_ERR_INVALID_HEADER;
+    if (r.n_members > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    gzpx_dindex *ix = new (std::nothrow) gzpx_dindex();
+    if (!ix) return GZPX_ERR_DEVICE;
+    ix->device = c->device;
+    ix->format = c->format;
+    ix->n = r.n_members;
+    ix->consumed = r.consumed;
+    const size_t n = r.n_members;
+    rc = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&ix->d_off, (n ? n : 1) * 8));
+        HIP_TRY(hipMalloc((void **)&ix->d_size, (n ? n : 1) * 4));
+        HIP_TRY(hipMalloc((void **)&ix->d_ustart, (n + 1) * 8));
+        if (n == 0) {
+            HIP_TRY(hipMemsetAsync(ix->d_ustart, 0, 8, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            return GZPX_OK;
+        }
+        DSlot *slp = nullptr;
+        for (DSlot &s : c->slots)
+            if (s.state == 0 && !slp) slp = &s;
+        DSlot &sl = *slp;  // (its member records only; the slot stays free, the call returns synchronised under the lock)
+        const int rr = dslot_reserve(sl, n);
+        if (rr != GZPX_OK) return rr;
+        launch_member_emit(c->ms, (uint32_t)n, ix->d_off, ix->d_size, c->stream);
+        launch_member_index((const uint8_t *)d_in, ix->d_off, ix->d_size, (uint32_t)n, sl.d_blk, ix->d_ustart, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(sl.h_total, ix->d_ustart + n, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        ix->inflated_len = *sl.h_total;
+        return GZPX_OK;
+    }();
+    if (rc != GZPX_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        gzpx_dindex_destroy(ix);
+        return rc;
+    }
+    *out = ix;
+    if (n_members) *n_members = ix->n;
+    if (consumed) *consumed = ix->consumed;
+    if (inflated_len) *inflated_len = ix->inflated_len;
+    return GZPX_OK;
+}
+
+int gzpx_dindex_entries(const gzpx_dindex *ix, gzpx_index_entry *entries, size_t max_entries, size_t *n_entries) {
+    if (!ix || !n_entries) return GZPX_ERR_INVALID_ARG;
+    *n_entries = ix->n;
+    const size_t n_copy = entries ? (ix->n < max_entries ? ix->n : max_entries) : 0;
+    if (!n_copy) return GZPX_OK;
+    if (hipSetDevice(ix->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    std::vector<uint64_t> off(n_copy), un(n_copy);
+    HIP_TRY(hipMemcpy(off.data(), ix->d_off, n_copy * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(un.data(), ix->d_ustart, n_copy * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_copy; i++) entries[i] = gzpx_index_entry{off[i], un[i]};
+    return GZPX_OK;
+}
+
+int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len,
+                            const gzpx_range *ranges, size_t n_ranges, int coords, void *d_out, size_t out_cap,
+                            size_t *out_len, uint64_t *out_offsets, size_t *bad_range, gzpx_check_info *info,
+                            void *hip_stream) {
+    if (!c || !ix || !out_len || (!ranges && n_ranges) || (!d_in && in_len) || (!d_out && out_cap))
+        return GZPX_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (bad_range) *bad_range = (size_t)-1;
+    if (coords != GZPX_RANGE_UNCOMPRESSED && coords != GZPX_RANGE_VIRTUAL) return GZPX_ERR_INVALID_ARG;
+    if (coords == GZPX_RANGE_VIRTUAL && c->format != GZPX_FORMAT_BGZF) return GZPX_ERR_INVALID_ARG;
+    if (ix->device != c->device || ix->format != c->format || in_len < ix->consumed) return GZPX_ERR_INVALID_ARG;
+    if (n_ranges > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    c->have_rr = c->rr_stages = false;
+    c->last_rr_members = 0;
+    if (n_ranges == 0) {
+        if (out_offsets) out_offsets[0] = 0;
+        return GZPX_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    dwait_free_slot(c, lk);
+    int si = 0;
+    while (c->slots[si].state != 0) si++;
+    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
+    int rc = dslot_reserve(sl, ix->n ? ix->n : 1);
+    if (rc != GZPX_OK) return rc;
+    rc = rr_reserve(c, n_ranges, ix->n);
+    if (rc != GZPX_OK) return rc;
+    hipStream_t stream = c->stream, after = (hipStream_t)hip_stream;
+    if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {
+        HIP_TRY(hipEventRecord(c->ev_dep, after));
+        HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
+    }
+    // what follows a failure may still be running when the caller gets its buffers back otherwise
+    struct Drain {
+        hipStream_t s;
+        bool armed = true;
+        ~Drain() {
+            if (armed) (void)hipStreamSynchronize(s);
+        }
+    } drain{stream};
+    RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
+    memcpy(c->h_ranges, ranges, n_ranges * sizeof(gzpx_range));
+    HIP_TRY(hipMemcpyAsync(c->rr.ranges, c->h_ranges, n_ranges * 16, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->ev_r[0], stream));
+    launch_ranges_select(rix, (uint32_t)n_ranges, coords == GZPX_RANGE_VIRTUAL, c->rr, sl.d_offsets, sl.d_sizes, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_r[1], stream));
+    HIP_TRY(hipMemcpyAsync(c->h_rrec, c->rr.rec, 32, hipMemcpyDeviceToHost, stream));
+    if (out_offsets)
+        HIP_TRY(hipMemcpyAsync(c->h_out_off, c->rr.out_off, (n_ranges + 1) * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the record: the one round trip in front of the inflate
+    c->have_rr = true;
+    const uint32_t *rec = c->h_rrec;
+    if (rec[kRrRecBad] != 0xFFFFFFFFu) {
+        if (bad_range) *bad_range = rec[kRrRecBad];
+        return GZPX_ERR_INVALID_ARG;
+    }
+    const size_t nsel = rec[kRrRecSelected];
+    const uint64_t stage_bytes = (uint64_t)rec[kRrRecStage] | ((uint64_t)rec[kRrRecStage + 1] << 32);
+    const uint64_t total = (uint64_t)rec[kRrRecTotal] | ((uint64_t)rec[kRrRecTotal + 1] << 32);
+    if (total > out_cap) {
+        *out_len = (size_t)total;
+        return GZPX_ERR_INSUFFICIENT_SPACE;
+    }
+    if (total >> 44) return GZPX_ERR_INVALID_ARG;  // (the gather's grid)
+    if (out_offsets) memcpy(out_offsets, c->h_out_off, (n_ranges + 1) * 8);
+    c->last_rr_members = nsel;
+    if (nsel == 0) {  // empty ranges only
+        drain.armed = false;
+        return GZPX_OK;
+    }
+    if (stage_bytes + 64 > c->stage_cap) {
+        if (c->d_stage) (void)hipFree(c->d_stage);
+        c->d_stage = nullptr;
+        c->stage_cap = 0;
+        const size_t cap = (size_t)(stage_bytes + stage_bytes / 8 + 4096);
+        HIP_TRY(hipMalloc((void **)&c->d_stage, cap));
+        c->stage_cap = cap;
+    }
+    const uint32_t hdr_len = c->format == GZPX_FORMAT_BGZF ? 18 : 20;
+    sl.nb = nsel;
+    sl.route = c->route;
+    sl.have_blk = false;
+    sl.sc.n_cu = c->n_cu;
+    sl.sc.big_members = ix->consumed / ix->n >= 131072u ? 1 : 0;  // (the stream's average stands for the selection's)
+    if (c->route == kInflateRouteSeg) {
+        rc = dslot_seg_scratch(sl, (size_t)stage_bytes, nsel);
+        if (rc != GZPX_OK) return rc;
+    }
+    HIP_TRY(hipEventRecord(c->ev_r[2], stream));
+    launch_inflate(hdr_len, (const uint8_t *)d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nsel, sl.d_blk, sl.d_out_off,
+                   c->d_stage, stage_bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, c->route, sl.ev_tm);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, 48, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(c->ev_r[3], stream));
+    // (enqueued behind the inflate without asking how it went: after a failed check d_out holds nothing of use)
+    launch_ranges_gather(c->d_stage, (uint32_t)n_ranges, c->rr, (uint8_t *)d_out, total, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_r[4], stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    c->rr_stages = true;
+    c->last_slot = si;
+    c->last_nb = nsel;
+    const uint32_t *q = sl.h_summary;  // the first failing member of the selection, in stream order (k_dsummary)
+    if (q[0] != 0xFFFFFFFFu) {
+        const uint32_t st = q[1];
+        uint32_t member = 0;  // its index in the stream, through the rank map
+        HIP_TRY(hipMemcpy(&member, c->rr.map + q[0], 4, hipMemcpyDeviceToHost));
+        if (info) {
+            info->block = member;
+            info->found = q[2];
+            info->expected = q[3];
+        }
+        return st == 1 ? GZPX_ERR_BAD_DATA : st == 2 ? GZPX_ERR_INSUFFICIENT_SPACE : st != 0 ? GZPX_ERR_BAD_DATA : GZPX_ERR_INVALID_CHECK;
+    }
+    *out_len = (size_t)total;
+    return GZPX_OK;
+}
+
+int gzpx_dctx_last_ranges_members(gzpx_dctx *ctx, size_t *n_members_read) {
+    if (!ctx || !n_members_read) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    *n_members_read = ctx->last_rr_members;
+    return GZPX_OK;
+}
+
+int gzpx_dctx_last_ranges_ms(gzpx_dctx *ctx, float ms[3]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ms[0] = ms[1] = ms[2] = 0.0f;
+    if (!ctx->have_rr) return GZPX_OK;
+    if (hipEventElapsedTime(&ms[0], ctx->ev_r[0], ctx->ev_r[1]) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (!ctx->rr_stages) return GZPX_OK;
+    if (hipEventElapsedTime(&ms[1], ctx->ev_r[2], ctx->ev_r[3]) != hipSuccess ||
+        hipEventElapsedTime(&ms[2], ctx->ev_r[3], ctx->ev_r[4]) != hipSuccess)
+        return GZPX_ERR_DEVICE;
+    return GZPX_OK;
 }
 
 int gzpx_decompress_blocks(gzpx_dctx *c, const uint8_t *in, size_t in_len, const uint64_t *offsets,
@@ -2344,7 +2654,7 @@ int gzpx_dctx_last_inflate_stage_ms(gzpx_dctx *ctx, float ms[2]) {
     if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
     ms[0] = ms[1] = 0.0f;
-    if (!ctx->last_nb || ctx->last_slot < 0 || ctx->route != kInflateRouteSeg) return GZPX_OK;
+    if (!ctx->last_nb || ctx->last_slot < 0 || ctx->slots[ctx->last_slot].route != kInflateRouteSeg) return GZPX_OK;
     const DSlot &sl = ctx->slots[ctx->last_slot];
     if (hipEventElapsedTime(&ms[0], sl.ev_t0, sl.ev_tm) != hipSuccess || hipEventElapsedTime(&ms[1], sl.ev_tm, sl.ev_t1) != hipSuccess)
         return GZPX_ERR_DEVICE;
@@ -2362,7 +2672,8 @@ int gzpx_dctx_last_redo_count(gzpx_dctx *ctx, uint32_t *count) {
     if (!ctx || !count) return GZPX_ERR_INVALID_ARG;
     *count = 0;
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (ctx->last_slot < 0 || !ctx->slots[ctx->last_slot].sc.redo || ctx->route != kInflateRouteSeg) return GZPX_OK;
+    if (ctx->last_slot < 0 || !ctx->slots[ctx->last_slot].sc.redo || ctx->slots[ctx->last_slot].route != kInflateRouteSeg)
+        return GZPX_OK;
     if (hipSetDevice(ctx->device) != hipSuccess) return GZPX_ERR_DEVICE;
     if (hipMemcpy(count, ctx->slots[ctx->last_slot].sc.redo, 4, hipMemcpyDeviceToHost) != hipSuccess) return GZPX_ERR_DEVICE;
     return GZPX_OK;

@@ -221,6 +221,34 @@ void launch_member_emit(const MemberScanScratch &m, uint32_t n_emit, uint64_t *d
 void launch_member_index(const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes, uint32_t nb, void *d_blk,
                          uint64_t *d_out_off, hipStream_t stream);
 
+// Random access by range (gzpx_ranges.h).  The index of a stream, in device memory:
+struct RrIndex {
+    const uint64_t *off;     // [n]     member starts in the compressed stream
+    const uint32_t *size;    // [n]     member sizes
+    const uint64_t *ustart;  // [n + 1] exclusive prefix sum of ISIZE: member starts in the inflated stream, the total
+    uint32_t n;
+};
+// the record of locate + select (RangeScratch.rec, u32 words): [0] the first invalid range (0xFFFFFFFF: none),
+// [1] members selected, [2..3] the sum of their ISIZE = bytes of staging, [4..5] bytes of output
+enum { kRrRecBad = 0, kRrRecSelected = 1, kRrRecStage = 2, kRrRecTotal = 4 };
+struct RangeScratch {
+    uint64_t *ranges = nullptr;   // [2 * ranges] the caller's (begin, end) pairs
+    uint32_t *first = nullptr;    // [ranges]     the first member a range reads
+    uint64_t *len = nullptr;      // [ranges]     its length in bytes
+    uint64_t *src = nullptr;      // [ranges]     where its bytes start in staging
+    uint64_t *out_off = nullptr;  // [ranges + 1] where they go in the output
+    uint32_t *diff = nullptr;     // [members + 1] +1 / -1 where the spans [first, last] begin / end
+    uint32_t *map = nullptr;      // [members]    rank in the selection -> index in the stream
+    uint64_t *soff = nullptr;     // [members]    where a selected member starts in staging
+    uint32_t *rec = nullptr;      // [8]
+};
+// locate + select: fills the compacted member table (d_sel_off / d_sel_size, room for ix.n) and r.rec
+void launch_ranges_select(const RrIndex &ix, uint32_t n_ranges, int virt, const RangeScratch &r, uint64_t *d_sel_off,
+                          uint32_t *d_sel_size, hipStream_t stream);
+// the ranges' bytes from staging (16 readable bytes behind its last) to d_out, back to back
+void launch_ranges_gather(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, uint8_t *d_out, uint64_t total,
+                          hipStream_t stream);
+
 // gzpx_check.hip: (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);
 

@@ -5558,6 +5558,7 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
 #include "gzpx_inflate_seg.h"
 #include "gzpx_snap.h"
 #include "gzpx_mscan.h"
+#include "gzpx_ranges.h"
 
 // CRC-32 of the inflated blocks (LibDeflateCrc over the whole orig_size buffer, src/check.rs:45-71):
 // the workgroup routine of k_crc32, blocks addressed through their output offsets.
@@ -5896,6 +5897,28 @@ void launch_member_index(const uint8_t *d_in, const uint64_t *d_offsets, const u
     hipLaunchKernelGGL(k_dinit, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, d_in, d_offsets, d_sizes, blk,
                        (uint32_t *)nullptr);
     hipLaunchKernelGGL(k_dscan, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, d_out_off);
+}
+
+// Random access by range (gzpx_ranges.h): the marks and the record are cleared, every range located, the selection
+// compacted; the caller reads r.rec before it sizes the inflate.
+void launch_ranges_select(const RrIndex &ix, uint32_t n_ranges, int virt, const RangeScratch &r, uint64_t *d_sel_off,
+                          uint32_t *d_sel_size, hipStream_t stream) {
+    (void)hipMemsetAsync(r.diff, 0, ((size_t)ix.n + 1u) * 4u, stream);
+    (void)hipMemsetAsync(r.rec, 0xFF, 32, stream);
+    if (n_ranges)
+        hipLaunchKernelGGL(k_rr_locate, dim3((n_ranges + kRrThreads - 1u) / kRrThreads), dim3(kRrThreads), 0, stream, ix,
+                           n_ranges, (const uint64_t *)r.ranges, (uint32_t)(virt ? 1 : 0), r.first, r.len, r.src, r.diff, r.rec);
+    hipLaunchKernelGGL(k_rr_select, dim3(1), dim3(kRrThreads), 0, stream, ix, n_ranges, (const uint32_t *)r.diff, d_sel_off,
+                       d_sel_size, r.map, r.soff, (const uint32_t *)r.first, (const uint64_t *)r.len, r.src, r.out_off, r.rec);
+}
+
+void launch_ranges_gather(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, uint8_t *d_out, uint64_t total,
+                          hipStream_t stream) {
+    if (!total) return;
+    const uint32_t lead = (uint32_t)((uintptr_t)d_out & 15u);
+    const uint64_t tiles = (lead + total + kRrTile - 1u) / kRrTile;
+    hipLaunchKernelGGL(k_rr_gather, dim3((uint32_t)tiles), dim3(kRrThreads), 0, stream, d_stage, (const uint64_t *)r.src,
+                       (const uint64_t *)r.out_off, n_ranges, d_out, lead, total);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

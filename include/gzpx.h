@@ -330,6 +330,52 @@ int gzpx_index_device(gzpx_dctx *ctx, const void *d_in, size_t in_len, gzpx_inde
 /* HIP-event duration of the member-discovery kernels in the last of these three calls on this context (a scan whose
  * candidate arrays were too small ran twice: both runs and the reallocation between them are inside) */
 int gzpx_dctx_last_scan_ms(gzpx_dctx *ctx, float *ms);
+/* ---- random access by range (gzpx_ranges.h): the index of a device-resident stream kept ON the device, and reads of
+ * a batch of byte ranges of the inflated stream that inflate only the members the ranges touch.
+ * gzpx_dindex_build_device: the walk of gzpx_index_device (same *consumed / *inflated_len, same
+ * GZPX_ERR_INVALID_HEADER, a trailing partial member left out); the member offsets, the member sizes and the
+ * exclusive prefix sum of ISIZE stay in device memory owned by *out, only the scan record and the total cross to the
+ * host.  An empty stream gives a valid index of 0 members.  gzpx_dindex_entries copies the tables out: identical to
+ * what gzpx_index_device returns on the same bytes.  An index belongs to the device and the format of its context.
+ * (A .gzi file cannot be imported: it has no member sizes and no entry for the first or the EOF member.) */
+typedef struct gzpx_dindex gzpx_dindex;
+int gzpx_dindex_build_device(gzpx_dctx *ctx, const void *d_in, size_t in_len, gzpx_dindex **out, size_t *n_members,
+                             size_t *consumed, uint64_t *inflated_len, void *hip_stream);
+int gzpx_dindex_entries(const gzpx_dindex *ix, gzpx_index_entry *entries, size_t max_entries, size_t *n_entries);
+void gzpx_dindex_destroy(gzpx_dindex *ix);
+typedef struct gzpx_range {
+    uint64_t begin, end; /* [begin, end) */
+} gzpx_range;
+#define GZPX_RANGE_UNCOMPRESSED 0 /* offsets into the inflated stream                            */
+#define GZPX_RANGE_VIRTUAL 1      /* BGZF virtual offsets: member start << 16 | offset in member */
+/* Reads n_ranges ranges of the inflated stream into d_out, back to back in the order given: the bytes of range r
+ * land at d_out + out_offsets[r], *out_len is the total (out_offsets: optional HOST array of n_ranges + 1).
+ * `ranges` is a host array; d_in / in_len are the bytes the index was built from (the address may differ; in_len
+ * below the index's `consumed`: GZPX_ERR_INVALID_ARG); hip_stream as for gzpx_decompress_blocks_device.  Returns
+ * synchronised; runs under the context's lock and uses one slot, like gzpx_decompress_stream_device.
+ *   Ranges may overlap or repeat (their bytes are repeated in the output) and may be empty; n_ranges == 0 is OK with
+ *   0 bytes.  GZPX_RANGE_UNCOMPRESSED: begin <= end <= inflated_len.  GZPX_RANGE_VIRTUAL (BGZF contexts only, else
+ *   GZPX_ERR_INVALID_ARG): the upper 48 bits are exactly a member start of the index, the lower 16 are <= that
+ *   member's ISIZE (equal: the position in front of the next member), and begin does not lie behind end in stream
+ *   order.  A range that breaks these rules: GZPX_ERR_INVALID_ARG with *bad_range = the first such range, nothing
+ *   inflated.  The total is known before anything is inflated: above out_cap the call returns
+ *   GZPX_ERR_INSUFFICIENT_SPACE with *out_len = the bytes needed, nothing inflated.
+ *   Members read: for a non-empty range, `first` = the last member whose uncompressed start is <= begin, `last` =
+ *   the last member whose uncompressed start is < end; the union of [first, last] over the non-empty ranges is
+ *   read, every member once however many ranges touch it, and no byte of any other member
+ *   (gzpx_dctx_last_ranges_members: the size of that union in the last call).  Every member read is inflated whole
+ *   and its CRC and ISIZE are checked as everywhere else: GZPX_ERR_BAD_DATA / GZPX_ERR_INVALID_CHECK /
+ *   GZPX_ERR_INSUFFICIENT_SPACE (an ISIZE that lies) for the first failing member in stream order, info->block = its
+ *   index IN THE STREAM (after such a failure d_out[0..total) holds nothing of use: the slices are cut behind the
+ *   inflate without a round trip in between).  Both inflate routes (gzpx_dctx_set_route) serve it.
+ * gzpx_dctx_last_ranges_ms: HIP-event durations of the last call's stages: [0] locate + select, [1] inflate into the
+ * context's staging buffer, [2] gather. */
+int gzpx_read_ranges_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const void *d_in, size_t in_len,
+                            const gzpx_range *ranges, size_t n_ranges, int coords, void *d_out, size_t out_cap,
+                            size_t *out_len, uint64_t *out_offsets, size_t *bad_range, gzpx_check_info *info,
+                            void *hip_stream);
+int gzpx_dctx_last_ranges_members(gzpx_dctx *ctx, size_t *n_members_read);
+int gzpx_dctx_last_ranges_ms(gzpx_dctx *ctx, float ms[3]);
 typedef struct gzpx_decompressor gzpx_decompressor;
 gzpx_decompressor *gzpx_alloc_decompressor(void);
 /* 0 = ok (short output allowed, *actual = bytes produced), GZPX_ERR_BAD_DATA, GZPX_ERR_INSUFFICIENT_SPACE */

@@ -21,7 +21,9 @@
 //
 // Anything out of the ordinary on the true path (invalid codes, a distance before the start, output that does
 // not fit, a stream that ends early, lanes that do not re-synchronise) is NOT judged here: the member is put
-// on the redo list and k_inflate, which holds libdeflate's exact error classes, decodes it again.
+// on the redo list and k_inflate, which holds libdeflate's exact error classes, decodes it again.  The table
+// builder applies libdeflate's rule for the shape of a code itself (seg_build): the empty code and the single
+// codeword of length 1 are codes like any other, every other incomplete code is handed back like an over-subscribed one.
 
 constexpr uint32_t kInfRedo = 0x80u;     // DBlock.status while a member waits for k_inflate
 constexpr uint32_t kSegMinBits = 512u;   // segment length per lane: remaining bits / 64, within these bounds
@@ -109,7 +111,9 @@ struct InfSegLdsW {
 
 // Build the two-level decode table of one code from lens[0 .. nsyms) (nsyms <= 320): `root` index bits in
 // main[], longer codewords behind pointer entries in sub[] (sub[0] stays "invalid": where unused codewords land).  All 64
-// lanes call it.  Returns false for an over-subscribed code or a second level that does not fit.
+// lanes call it.  Returns false for an over-subscribed code, for an incomplete one (but the empty code decodes symbol 0
+// from every bit and a single codeword of length 1 is decoded from both bit values: libdeflate's build_decode_table) or
+// for a second level that does not fit.
 template <int KIND>
 __device__ __attribute__((noinline)) bool seg_build(InfSegLds &h, uint16_t *cwtab, const uint8_t *lens, uint32_t nsyms, uint32_t root,
                                        uint32_t *main, uint32_t *sub, uint32_t sub_cap, uint32_t lane) {
@@ -134,6 +138,20 @@ __device__ __attribute__((noinline)) bool seg_build(InfSegLds &h, uint16_t *cwta
         kraft += cnt[l] << (15 - l);
     }
     if (kraft > (1u << 15)) return false;
+    if (kraft < (1u << 15)) {
+        if (kraft != 0 && (kraft != (1u << 14) || cnt[1] != 1)) return false;
+        uint32_t only = 0;  // the one symbol of the code (symbol 0 for the empty code)
+        for (uint32_t r = 0; r < rounds && kraft; r++) {
+            const uint64_t m = __ballot(64 * r + lane < nsyms && lens[64 * r + lane] == 1);
+            if (m) only = 64 * r + (uint32_t)__ffsll((long long)m) - 1;
+        }
+        const uint32_t e = seg_entry<KIND>(only, 1);
+        for (uint32_t i = lane; i < (1u << root); i += 64) main[i] = e;  // (no pointer entries: the second level is never read through them)
+        if (sub)
+            for (uint32_t i = lane; i < sub_cap; i += 64) sub[i] = KIND == kSegLitlen ? kSegBadL : kSegBadO;
+        wave_sync();
+        return true;
+    }
     for (uint32_t i = lane; i < (1u << root); i += 64) main[i] = 0;
     if (sub)
         for (uint32_t i = lane; i < sub_cap; i += 64) sub[i] = KIND == kSegLitlen ? kSegBadL : kSegBadO;
@@ -419,13 +437,10 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
                         }
                         v = prev;
                     }
-                    if (i + r > total) {
-                        bad = true;
-                        break;
-                    }
-                    if (lane < r) tmp[i + lane] = (uint8_t)v;
-                    if (lane + 64 < r) tmp[i + lane + 64] = (uint8_t)v;
-                    if (lane + 128 < r) tmp[i + lane + 128] = (uint8_t)v;
+                    const uint32_t nw = r < total - i ? r : total - i;  // (the last run may overrun the total: the excess is ignored)
+                    if (lane < nw) tmp[i + lane] = (uint8_t)v;
+                    if (lane + 64 < nw) tmp[i + lane + 64] = (uint8_t)v;
+                    if (lane + 128 < nw) tmp[i + lane + 128] = (uint8_t)v;
                     prev = v;
                     i += r;
                     cur += pk & 255u;
@@ -445,7 +460,7 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
             wave_sync();
             for (uint32_t k = 0; k < 5; k++) h.lens[lane + 64 * k] = mine[k];
             wave_sync();
-            if (h.lens[256] == 0) {
+            if (h.lens[256] == 0) {  // (no end-of-block code: k_inflate's to run to its end)
                 bad = true;
                 break;
             }

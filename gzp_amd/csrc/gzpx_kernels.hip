@@ -4755,7 +4755,7 @@ constexpr uint32_t kInfR = GZPX_INF_R;  // groups of 64 bit positions decoded pe
 enum InflateStatus : uint32_t { kInfOk = 0, kInfBadData = 1, kInfInsufficientSpace = 2, kInfShortOutput = 3 };
 
 // Decode-table entries (32 bit).  bits 0-3: codeword length (0 = not in the fast table);
-//   litlen: bits 4-5 type (0 literal, 1 length, 2 end of block, 3 invalid symbol), bits 8-15 the
+//   litlen: bits 4-5 type (0 literal, 1 length, 2 end of block), bits 8-15 the
 //           literal byte or the number of extra bits, bits 16-24 the base match length;
 //   offset: bit 4 invalid symbol, bits 8-11 number of extra bits, bits 16-31 base distance;
 //   precode: bits 8-12 the symbol.
@@ -4767,12 +4767,11 @@ __device__ __forceinline__ uint32_t inflate_entry(uint32_t sym, uint32_t cl) {
     if (KIND == kInfLitlen) {
         if (sym < 256) return cl | (sym << 8);
         if (sym == 256) return cl | (2u << 4);
-        if (sym > 285) return cl | (3u << 4);
         const uint32_t slot = sym - 257;
         uint32_t base, xb = 0;
         if (slot < 8) {
             base = 3 + slot;
-        } else if (slot == 28) {
+        } else if (slot >= 28) {  // (286 and 287 too: libdeflate's table decodes them as length 258, like 285)
             base = 258;
         } else {
             xb = (slot - 4) >> 2;
@@ -4793,7 +4792,9 @@ __device__ __forceinline__ uint32_t inflate_entry(uint32_t sym, uint32_t cl) {
 
 // Build the decode tables of one code from lens[0 .. nsyms): counts, canonical first codes, symbols
 // in canonical order, and the direct-lookup table for codes of <= fast_bits bits.  All 64 lanes
-// call it.  Returns false for an over-subscribed code.
+// call it.  Returns false for an over-subscribed code and for an incomplete one, with libdeflate's two
+// exceptions (build_decode_table): the empty code, in which every bit decodes symbol 0, and a single
+// codeword of length 1, which both bit values decode.
 // (Not inlined on purpose, and cnt / fst / off indexed by a lane's own code length -- 544 bytes of
 // scratch per lane in a part of the kernel that runs once per DEFLATE sub-block.  Measured in round 3:
 // with the tables in registers / LDS and the function inlined the kernel has no scratch and 64 VGPRs,
@@ -4822,6 +4823,20 @@ __device__ bool inflate_build(const uint8_t *lens, uint32_t nsyms, uint32_t fast
         kraft += cnt[l] << (15 - l);
     }
     if (kraft > (1u << 15)) return false;
+    if (kraft < (1u << 15)) {
+        if (kraft != 0 && (kraft != (1u << 14) || cnt[1] != 1)) return false;
+        uint32_t only = 0;  // the one symbol of the code (symbol 0 for the empty code)
+        for (uint32_t base = 0; base < nsyms && kraft; base += 64) {
+            const uint64_t m = __ballot(base + lane < nsyms && lens[base + lane] == 1);
+            if (m) only = base + (uint32_t)__ffsll((long long)m) - 1;
+        }
+        wave_sync();
+        if (lane < 16) count[lane] = 0;  // (every index of the fast table holds the entry: the slow path is never asked)
+        const uint32_t e = inflate_entry<KIND>(only, 1);
+        for (uint32_t i = lane; i < (1u << fast_bits); i += 64) fast[i] = e;
+        wave_sync();
+        return true;
+    }
     wave_sync();
     if (lane < 16) {
         count[lane] = lane ? cnt[lane] : 0;
@@ -5173,13 +5188,11 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
                     val = 0;
                 }
                 bp += used;
-                if (i + rep > total) {
-                    status = kInfBadData;
-                    break;
-                }
-                if (lane < rep) tmp[i + lane] = (uint8_t)val;  // rep <= 138: up to 3 rounds
-                if (lane + 64 < rep) tmp[i + lane + 64] = (uint8_t)val;
-                if (lane + 128 < rep) tmp[i + lane + 128] = (uint8_t)val;
+                // (the last run may overrun the total: libdeflate ignores the excess, and so do the writes here)
+                const uint32_t nw = rep < total - i ? rep : total - i;
+                if (lane < nw) tmp[i + lane] = (uint8_t)val;  // rep <= 138: up to 3 rounds
+                if (lane + 64 < nw) tmp[i + lane + 64] = (uint8_t)val;
+                if (lane + 128 < nw) tmp[i + lane + 128] = (uint8_t)val;
                 prev = val;
                 i += rep;
             }
@@ -5197,10 +5210,8 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
             wave_sync();
             for (uint32_t k = 0; k < 5; k++) h.lens[lane + 64 * k] = mine[k];
             wave_sync();
-            if (h.lens[256] == 0) {  // no end-of-block code: the sub-block could never end
-                status = kInfBadData;
-                break;
-            }
+            // (a code without an end-of-block codeword is not judged: like libdeflate's, the symbol loop below runs
+            // until the output is full -- InsufficientSpace -- or the input is spent -- BadData; every symbol takes a bit)
         }
         if (!inflate_build<kInfLitlen>(h.lens, 288, 10, h.lfast, h.lsorted, h.lcount, h.lfirst, h.loffs, lane) ||
             !inflate_build<kInfOffset>(h.lens + 288, 32, 8, h.ofast, h.osorted, h.ocount, h.ofirst, h.ooffs,
@@ -5471,10 +5482,6 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
             if (stype == 2) {
                 bp += scl;
                 eob = true;
-                break;
-            }
-            if (stype == 3) {
-                status = kInfBadData;
                 break;
             }
             if (stype == 0) {

@@ -41,6 +41,8 @@ STREAM_NONE = ctypes.c_void_p(-1).value  # GZPX_STREAM_NONE: the caller has sync
 N_STAGES = 9
 INFLATE_SEG, INFLATE_WAVE = 0, 1
 RANGE_UNCOMPRESSED, RANGE_VIRTUAL = 0, 1
+WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # inflate_batch_device: RFC 1951 / 1950 / 1952
+BATCH_SHORT_OK = 1
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -65,6 +67,7 @@ EXPORTS = [
     "gzpx_scan_blocks_device", "gzpx_decompress_stream_device", "gzpx_index_device", "gzpx_dctx_last_scan_ms",
     "gzpx_dindex_build_device", "gzpx_dindex_entries", "gzpx_dindex_destroy", "gzpx_read_ranges_device",
     "gzpx_dctx_last_ranges_members", "gzpx_dctx_last_ranges_ms",
+    "gzpx_inflate_batch_device", "gzpx_dctx_last_check_ms",
 ]
 
 
@@ -82,6 +85,12 @@ class GzpxParConfig(ctypes.Structure):
 
 class GzpxCheckInfo(ctypes.Structure):
     _fields_ = [("block", ctypes.c_size_t), ("found", ctypes.c_uint32), ("expected", ctypes.c_uint32)]
+
+
+class GzpxMemberResult(ctypes.Structure):
+    """gzpx_member_result: one row of inflate_batch_device's d_results."""
+    _fields_ = [("status", ctypes.c_uint32), ("produced", ctypes.c_uint32), ("found", ctypes.c_uint32),
+                ("expected", ctypes.c_uint32)]
 
 
 READ_FN = ctypes.CFUNCTYPE(ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t)
@@ -242,6 +251,11 @@ class GzpxLib:
         L.gzpx_dctx_last_ranges_members.argtypes = [vp, psz]
         L.gzpx_dctx_last_ranges_ms.restype = i32
         L.gzpx_dctx_last_ranges_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_inflate_batch_device.restype = i32
+        L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
+                                                ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_check_ms.restype = i32
+        L.gzpx_dctx_last_check_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_alloc_decompressor.restype = vp
         L.gzpx_alloc_decompressor.argtypes = []
         L.gzpx_deflate_decompress.restype = i32
@@ -869,6 +883,37 @@ class DContext:
         ms = (ctypes.c_float * 3)()
         self.lib.check(self.lib.L.gzpx_dctx_last_ranges_ms(self.h, ms))
         return ms[0], ms[1], ms[2]
+
+    # ---- batches of raw / zlib / gzip members that lie in device memory (gzpx_wrap.h)
+    def inflate_batch_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr,
+                             out_cap, d_out_offsets_ptr=None, d_results_ptr=None, short_ok=False, stream=None,
+                             raise_on_member_error=True):
+        """n independent members in the wrapper `wrap` (WRAP_RAW / WRAP_ZLIB / WRAP_GZIP), member i at
+        d_in[offsets[i], offsets[i] + sizes[i]), inflated into slots of out_sizes[i] bytes back to back in d_out.  Every
+        table is a DEVICE array (offsets uint64, sizes uint32; d_out_sizes_ptr may be None for WRAP_GZIP: the trailers'
+        ISIZE); d_out_offsets_ptr (uint64[n + 1]) and d_results_ptr (GzpxMemberResult[n]) are optional and written.
+        short_ok: out_sizes are capacities (RAW, ZLIB; the one-wave-per-member route).  Returns (out_len, n_failed);
+        a failing member raises GzpxError with block= the first one's index, unless raise_on_member_error=False:
+        then (out_len, n_failed, first_failed) with first_failed None when every member is good."""
+        out_len, n_failed = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_inflate_batch_device(self.h, int(wrap), BATCH_SHORT_OK if short_ok else 0, d_in_ptr, in_len,
+                                                  d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr, out_cap,
+                                                  d_out_offsets_ptr, d_results_ptr, ctypes.byref(out_len),
+                                                  ctypes.byref(n_failed), ctypes.byref(info), stream)
+        if n_failed.value == 0:
+            if rc != OK:  # the call itself was refused, or the device failed
+                raise GzpxError(rc, self.lib.strerror(rc))
+            return (out_len.value, 0) if raise_on_member_error else (out_len.value, 0, None)
+        if raise_on_member_error:
+            self._raise(rc, info)
+        return out_len.value, n_failed.value, info.block
+
+    def last_check_ms(self):
+        """HIP-event duration of the check kernel (Adler-32 / CRC-32) of the last inflate_batch_device."""
+        ms = ctypes.c_float(0)
+        self.lib.check(self.lib.L.gzpx_dctx_last_check_ms(self.h, ctypes.byref(ms)))
+        return ms.value
 
 
 class DIndex:

@@ -1513,6 +1513,8 @@ struct DSlot {
     hipEvent_t ev_h2d = nullptr, ev_kernels = nullptr, ev_done = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // around the inflate kernels (timing enabled)
     hipEvent_t ev_tm = nullptr;                   // behind k_inflate_seg (the decode / copy route)
+    hipEvent_t ev_tc = nullptr;                   // behind the check kernel of gzpx_inflate_batch_device
+    bool have_check = false;                      // ev_t1 .. ev_tc hold the slot's last launch
     size_t nb = 0;
     int route = kInflateRouteSeg;  // the route of the slot's last launch (the context's may have changed since)
 };
@@ -1545,6 +1547,7 @@ int dslot_reserve(DSlot &c, size_t nb) {
         HIP_TRY(hipEventCreate(&c.ev_t0));
         HIP_TRY(hipEventCreate(&c.ev_t1));
         HIP_TRY(hipEventCreate(&c.ev_tm));
+        HIP_TRY(hipEventCreate(&c.ev_tc));
         HIP_TRY(hipHostMalloc((void **)&c.h_total, 64, hipHostMallocDefault));
         HIP_TRY(hipHostMalloc((void **)&c.h_summary, 64, hipHostMallocDefault));
         HIP_TRY(hipMalloc((void **)&c.sc.summary, 64));
@@ -1736,6 +1739,7 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
         // debug counters
         HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, 48, hipMemcpyDeviceToHost, stream));
         sl.have_blk = c->debug != 0;
+        sl.have_check = false;
         if (c->debug) HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, nb * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipMemcpyAsync(sl.h_total, sl.d_out_off + nb, 8, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipEventRecord(sl.ev_kernels, stream));
@@ -2010,7 +2014,7 @@ void gzpx_dctx_destroy(gzpx_dctx *c) {
         if (sl.d_out) (void)hipFree(sl.d_out);
         if (sl.sc.mlist) (void)hipFree(sl.sc.mlist);
         if (sl.sc.tfirst) (void)hipFree(sl.sc.tfirst);
-        for (hipEvent_t e : {sl.ev_h2d, sl.ev_kernels, sl.ev_done, sl.ev_t0, sl.ev_t1, sl.ev_tm})
+        for (hipEvent_t e : {sl.ev_h2d, sl.ev_kernels, sl.ev_done, sl.ev_t0, sl.ev_t1, sl.ev_tm, sl.ev_tc})
             if (e) (void)hipEventDestroy(e);
     }
     rr_free_ranges(c);
@@ -2388,6 +2392,7 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
     sl.nb = nsel;
     sl.route = c->route;
     sl.have_blk = false;
+    sl.have_check = false;
     sl.sc.n_cu = c->n_cu;
     sl.sc.big_members = ix->consumed / ix->n >= 131072u ? 1 : 0;  // (the stream's average stands for the selection's)
     if (c->route == kInflateRouteSeg) {
@@ -2422,6 +2427,93 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
         return st == 1 ? GZPX_ERR_BAD_DATA : st == 2 ? GZPX_ERR_INSUFFICIENT_SPACE : st != 0 ? GZPX_ERR_BAD_DATA : GZPX_ERR_INVALID_CHECK;
     }
     *out_len = (size_t)total;
+    return GZPX_OK;
+}
+
+int gzpx_inflate_batch_device(gzpx_dctx *c, int wrap, unsigned flags, const void *d_in, size_t in_len,
+                              const uint64_t *d_in_offsets, const uint32_t *d_in_sizes, const uint32_t *d_out_sizes,
+                              size_t n, void *d_out, size_t out_cap, uint64_t *d_out_offsets,
+                              gzpx_member_result *d_results, size_t *out_len, size_t *n_failed, gzpx_check_info *info,
+                              void *hip_stream) {
+    static_assert(sizeof(gzpx_member_result) == 16, "k_dresult writes this layout");
+    if (!c || !out_len || !n_failed || (!d_in && in_len) || (!d_out && out_cap)) return GZPX_ERR_INVALID_ARG;
+    *out_len = 0;
+    *n_failed = 0;
+    if (wrap != GZPX_WRAP_RAW && wrap != GZPX_WRAP_ZLIB && wrap != GZPX_WRAP_GZIP) return GZPX_ERR_INVALID_ARG;
+    if (flags & ~GZPX_BATCH_SHORT_OK) return GZPX_ERR_INVALID_ARG;
+    const bool short_ok = (flags & GZPX_BATCH_SHORT_OK) != 0;
+    if (short_ok && (wrap == GZPX_WRAP_GZIP || !d_out_sizes)) return GZPX_ERR_INVALID_ARG;
+    if (!d_out_sizes && wrap != GZPX_WRAP_GZIP) return GZPX_ERR_INVALID_ARG;  // (only a gzip trailer states a size)
+    if (n && (!d_in_offsets || !d_in_sizes)) return GZPX_ERR_INVALID_ARG;
+    if (n > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    hipStream_t stream = c->stream, after = (hipStream_t)hip_stream;
+    if (n == 0) {
+        if (d_out_offsets) {
+            HIP_TRY(hipMemsetAsync(d_out_offsets, 0, 8, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+        return GZPX_OK;
+    }
+    dwait_free_slot(c, lk);
+    int si = 0;
+    while (c->slots[si].state != 0) si++;
+    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
+    int rc = dslot_reserve(sl, n);
+    if (rc != GZPX_OK) return rc;
+    if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {
+        HIP_TRY(hipEventRecord(c->ev_dep, after));
+        HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
+    }
+    struct Drain {  // what follows a failure may still be running when the caller gets its buffers back otherwise
+        hipStream_t s;
+        bool armed = true;
+        ~Drain() {
+            if (armed) (void)hipStreamSynchronize(s);
+        }
+    } drain{stream};
+    sl.nb = n;
+    sl.route = short_ok ? (int)kInflateRouteWave : c->route;
+    sl.have_blk = c->debug != 0;
+    sl.sc.n_cu = c->n_cu;
+    sl.sc.big_members = in_len / n >= 131072u ? 1 : 0;  // (the sizes are on the device: the input's average stands for them)
+    if (sl.route == kInflateRouteSeg) {
+        rc = dslot_seg_scratch(sl, out_cap, n);
+        if (rc != GZPX_OK) return rc;
+    }
+    // the slot's own size table is free here (the caller's is read where it lies): it holds the members' slots
+    launch_inflate_batch(wrap, short_ok ? 1 : 0, (const uint8_t *)d_in, in_len, d_in_offsets, d_in_sizes, d_out_sizes,
+                         (uint32_t)n, sl.d_blk, sl.d_sizes, sl.d_out_off, (uint8_t *)d_out, out_cap, sl.d_crc, c->cc,
+                         c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, d_out_offsets, d_results, sl.ev_tm,
+                         sl.ev_tc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, 32, hipMemcpyDeviceToHost, stream));
+    if (c->debug) HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, n * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    sl.have_check = true;
+    c->last_slot = si;
+    c->last_nb = n;
+    const uint32_t *q = sl.h_summary;  // k_dresult's record
+    *out_len = (size_t)((uint64_t)q[6] | ((uint64_t)q[7] << 32));
+    *n_failed = q[4];
+    if (q[0] == 0xFFFFFFFFu) return GZPX_OK;
+    if (info) {
+        info->block = q[0];
+        info->found = q[2];
+        info->expected = q[3];
+    }
+    return (int)q[1];
+}
+
+int gzpx_dctx_last_check_ms(gzpx_dctx *ctx, float *ms) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    *ms = 0.0f;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (ctx->last_slot < 0 || !ctx->slots[ctx->last_slot].have_check) return GZPX_OK;
+    const DSlot &sl = ctx->slots[ctx->last_slot];
+    if (hipEventElapsedTime(ms, sl.ev_t1, sl.ev_tc) != hipSuccess) return GZPX_ERR_DEVICE;
     return GZPX_OK;
 }
 

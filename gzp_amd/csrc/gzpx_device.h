@@ -181,6 +181,7 @@ void launch_emit(const Config &cfg, const uint8_t *slab, uint64_t slab_len, uint
 struct DBlockHost {
     uint64_t in_off;
     uint32_t size, isize, crc, status, produced, nmatch;
+    uint32_t pay_off, pay_len;  // the DEFLATE payload inside the member
     uint32_t cyc[8];  // debug launches: see DBlock in gzpx_kernels.hip
 };
 // Scratch of the two-kernel inflate (gzpx_inflate_seg.h): the members' match records, the first record of every
@@ -200,6 +201,15 @@ void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_off
                     uint32_t nb, void *d_blk, uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap,
                     uint32_t *d_crc_found, const CrcConsts &cc, int debug, hipEvent_t ev_begin,
                     hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc, int route, hipEvent_t ev_mid = nullptr);
+
+// A batch of independent members in a raw / zlib / gzip wrapper (gzpx_wrap.h): the table and every result in device
+// memory; sc.summary gets k_dresult's record (kWrRec*: first failing member, its status and values, failures, total).
+void launch_inflate_batch(int wrap, int short_ok, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets,
+                          const uint32_t *d_sizes, const uint32_t *d_out_sizes, uint32_t nb, void *d_blk, uint32_t *d_slot,
+                          uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap, uint32_t *d_check, const CrcConsts &cc,
+                          int debug, hipEvent_t ev_begin, hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc,
+                          int route, uint64_t *d_user_off, void *d_results, hipEvent_t ev_mid = nullptr,
+                          hipEvent_t ev_check = nullptr);  // (ev_end .. ev_check: the check kernel)
 
 // Member discovery on the device (gzpx_mscan.h): the candidate headers of a stream, sorted by position, and what the
 // chain from offset 0 makes of them.
@@ -249,7 +259,7 @@ void launch_ranges_select(const RrIndex &ix, uint32_t n_ranges, int virt, const 
 void launch_ranges_gather(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, uint8_t *d_out, uint64_t total,
                           hipStream_t stream);
 
-// gzpx_check.hip: (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
+// gzpx_wrap.h (k_adler32_tiles): (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);
 
 }  // namespace gzpx

@@ -488,7 +488,7 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
 // members fill the chip), kSegBigW for Mgzip members (a 1 MiB member is a million symbols: one wave would take its
 // lanes through 16 thousand steps each, and a slab holds too few members for the chip).
 template <bool DBG, int W>
-__device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uint32_t tid, uint32_t hdr_len, const uint8_t *__restrict__ in_all,
+__device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uint32_t tid, const uint8_t *__restrict__ in_all,
                                                      DBlock *__restrict__ blk_all, const uint64_t *__restrict__ out_off, uint8_t *out_all,
                                                      uint64_t out_cap, LzMatch *__restrict__ mlist_all, uint32_t *__restrict__ tfirst_all,
                                                      uint32_t *__restrict__ redo, uint32_t *hint_p) {
@@ -506,8 +506,8 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
         return;
     }
     uint8_t *out = out_all + ooff;
-    const uint8_t *pay = in_all + blk->in_off + hdr_len;
-    const uint32_t pay_len = blk->size - hdr_len - 8;
+    const uint8_t *pay = in_all + blk->in_off + blk->pay_off;
+    const uint32_t pay_len = blk->pay_len;
     LzMatch *ml = mlist_all + (ooff / 3u + b);
     uint32_t *tf = tfirst_all + ((ooff >> kLzTileShift) + 2ull * b);
     const bool multi = isize > kLzTile;  // more than one k_lzcopy tile: the first record of every tile is noted
@@ -517,7 +517,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
 
     const uint32_t pmis = (uint32_t)((uintptr_t)pay & 3u);
     const uint32_t *pay32 = (const uint32_t *)(pay - pmis);
-    const uint32_t pay_words = (pmis + pay_len + 8 + 3) >> 2;  // the 8 footer bytes are readable too
+    const uint32_t pay_words = (pmis + (blk->size - blk->pay_off) + 3) >> 2;  // the member's bytes behind the payload are readable too
     const uint32_t last_w = pay_words - 1;
     const uint32_t bit0 = 8u * pmis, bit_end = bit0 + 8u * pay_len;
     SegWin win;
@@ -929,7 +929,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
 // The members are claimed from a ticket counter (redo[1 + nb]): the launch holds as many workgroups as the chip keeps
 // resident, and one that finishes a member takes the next -- 8,835 members on 4,096 wave slots are 2.16 member times, not three.
 template <bool DBG, int W>
-__global__ __launch_bounds__(64 * W, GZPX_SEG_WAVES) void k_inflate_seg(uint32_t hdr_len, const uint8_t *__restrict__ in_all,
+__global__ __launch_bounds__(64 * W, GZPX_SEG_WAVES) void k_inflate_seg(const uint8_t *__restrict__ in_all,
                                                                        DBlock *__restrict__ blk_all,
                                                                        const uint64_t *__restrict__ out_off, uint8_t *out_all,
                                                                        uint64_t out_cap, LzMatch *__restrict__ mlist_all,
@@ -945,7 +945,7 @@ __global__ __launch_bounds__(64 * W, GZPX_SEG_WAVES) void k_inflate_seg(uint32_t
         const uint32_t b = uniform(s_ticket);
         if (b >= nb) break;
         wave_sync();
-        seg_member<DBG, W>(b, tid, hdr_len, in_all, blk_all, out_off, out_all, out_cap, mlist_all, tfirst_all, redo, hint_p);
+        seg_member<DBG, W>(b, tid, in_all, blk_all, out_off, out_all, out_cap, mlist_all, tfirst_all, redo, hint_p);
     }
 }
 

@@ -4891,12 +4891,14 @@ struct DBlock {
     uint32_t status;    // InflateStatus
     uint32_t produced;  // bytes actually inflated
     uint32_t nmatch;    // k_inflate_seg: records in the member's match list (0 after k_inflate)
+    uint32_t pay_off;   // where the DEFLATE payload starts inside the member (BGZF 18, Mgzip 20; gzpx_wrap.h: per member)
+    uint32_t pay_len;   // its length; the member's bytes behind it (the trailer) are readable, nothing behind the member is
     uint32_t cyc[8];    // debug launches only: shader-clock cycles [0] whole block, [1] headers + table
                         // builds, [2] round set-up (input bits + table gathers), [3] literal stores +
                         // match copies; counts [4] rounds, [5] literals, [6] matches, [7] window flushes
 };
 
-__global__ void k_dinit(uint32_t nb, const uint8_t *__restrict__ in, const uint64_t *__restrict__ offsets,
+__global__ void k_dinit(uint32_t hdr_len, uint32_t nb, const uint8_t *__restrict__ in, const uint64_t *__restrict__ offsets,
                         const uint32_t *__restrict__ sizes, DBlock *__restrict__ blk, uint32_t *__restrict__ redo) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b == 0 && redo) {
@@ -4913,6 +4915,8 @@ __global__ void k_dinit(uint32_t nb, const uint8_t *__restrict__ in, const uint6
     d.status = kInfOk;
     d.produced = 0;
     d.nmatch = 0;
+    d.pay_off = hdr_len;
+    d.pay_len = sizes[b] - hdr_len - 8;
     for (uint32_t k = 0; k < 8; k++) d.cyc[k] = 0;
     blk[b] = d;
 }
@@ -4950,7 +4954,7 @@ __global__ __launch_bounds__(256) void k_dscan(uint32_t nb, const DBlock *__rest
 #define GZPX_INF_WAVES 5  // waves per SIMD the global-window k_inflate is compiled for (VGPR budget 512 / n)
 #endif
 template <bool DBG, bool GWIN>
-__global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint32_t hdr_len, const uint8_t *__restrict__ in_all,
+__global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const uint8_t *__restrict__ in_all,
                                                               DBlock *__restrict__ blk_all,
                                                               const uint64_t *__restrict__ out_off,
                                                               uint8_t *out_all, uint64_t out_cap,
@@ -4972,8 +4976,8 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
         return;
     }
     uint8_t *out = out_all + ooff;
-    const uint8_t *pay = in_all + blk->in_off + hdr_len;
-    const uint32_t pay_len = blk->size - hdr_len - 8;
+    const uint8_t *pay = in_all + blk->in_off + blk->pay_off;
+    const uint32_t pay_len = blk->pay_len;
     uint8_t *win8 = (uint8_t *)h.win;
     const long long t_begin = DBG ? clock64() : 0;
     uint32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -4982,7 +4986,9 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
     // registers; bit positions count from the aligned dword that holds the first payload byte
     const uint32_t pmis = (uint32_t)((uintptr_t)pay & 3u);
     const uint32_t *pay32 = (const uint32_t *)(pay - pmis);
-    const uint32_t pay_words = (pmis + pay_len + 8 + 3) >> 2;  // the 8 footer bytes are readable too
+    // (the member's bytes behind the payload -- a BGZF footer's 8 -- are readable too; nothing behind the member is.
+    // A member of no bytes at all never gets here: k_dinit_wrap.)
+    const uint32_t pay_words = (pmis + (blk->size - blk->pay_off) + 3) >> 2;
     const uint32_t bit0 = 8u * pmis, bit_end = bit0 + 8u * pay_len;
     uint32_t hi_w = 0;  // dwords [.., hi_w) are in the ring; `pre` holds [hi_w, hi_w + 64)
     // (index clamped to readable memory.)  Bits past the end of the payload read as zeros, the way
@@ -5566,6 +5572,7 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(uint3
 #include "gzpx_snap.h"
 #include "gzpx_mscan.h"
 #include "gzpx_ranges.h"
+#include "gzpx_wrap.h"
 
 // CRC-32 of the inflated blocks (LibDeflateCrc over the whole orig_size buffer, src/check.rs:45-71):
 // the workgroup routine of k_crc32, blocks addressed through their output offsets.
@@ -5801,16 +5808,11 @@ void launch_emit(const Config &cfg, const uint8_t *slab, uint64_t, uint32_t nb, 
                        (const uint32_t *)s.hdr, (const uint64_t *)s.out_off, out, out_cap, nb);
 }
 
-void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes,
-                    uint32_t nb, void *d_blk, uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap,
-                    uint32_t *d_crc_found, const CrcConsts &cc, int debug, hipEvent_t ev_begin,
-                    hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc, int route, hipEvent_t ev_mid) {
-    DBlock *blk = (DBlock *)d_blk;
-    const bool seg = route != kInflateRouteWave && sc.mlist && sc.tfirst && sc.redo;
-    hipLaunchKernelGGL(k_dinit, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, d_in, d_offsets, d_sizes, blk,
-                       seg ? sc.redo : (uint32_t *)nullptr);
-    hipLaunchKernelGGL(k_dscan, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, d_out_off);
-    if (ev_begin) (void)hipEventRecord(ev_begin, stream);
+// The decode of nb members whose records and output offsets are in place (k_dinit + k_dscan, or k_dinit_wrap +
+// k_dscan_slots): k_inflate_seg + k_lzcopy + k_inflate over the redo list, or k_inflate for every member.
+static void launch_inflate_members(const uint8_t *d_in, uint32_t nb, DBlock *blk, uint64_t *d_out_off, uint8_t *d_out,
+                                   uint64_t out_cap, uint32_t *d_crc_found, const CrcConsts &cc, int debug,
+                                   hipStream_t stream, const InflateScratch &sc, bool seg, hipEvent_t ev_mid) {
     if (seg) {
         // decode (literals + match records), LZ copy, then k_inflate over whatever the two left on the redo list
         LzMatch *ml = (LzMatch *)sc.mlist;
@@ -5821,10 +5823,10 @@ void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_off
 #define GZPX_LAUNCH_SEG(DBG_)                                                                                              \
     do {                                                                                                                   \
         if (big)                                                                                                           \
-            hipLaunchKernelGGL((k_inflate_seg<DBG_, kSegBigW>), dim3(seg_grid), dim3(64 * kSegBigW), 0, stream, hdr_len,   \
+            hipLaunchKernelGGL((k_inflate_seg<DBG_, kSegBigW>), dim3(seg_grid), dim3(64 * kSegBigW), 0, stream,            \
                                d_in, blk, (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint); \
         else                                                                                                               \
-            hipLaunchKernelGGL((k_inflate_seg<DBG_, kSegSmallW>), dim3(seg_grid), dim3(64 * kSegSmallW), 0, stream, hdr_len, d_in, blk, \
+            hipLaunchKernelGGL((k_inflate_seg<DBG_, kSegSmallW>), dim3(seg_grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk, \
                                (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint);         \
         if (ev_mid) (void)hipEventRecord(ev_mid, stream);                                                                  \
     } while (0)
@@ -5832,34 +5834,83 @@ void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_off
             GZPX_LAUNCH_SEG(true);
             hipLaunchKernelGGL((k_lzcopy<false>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off,
                                d_out, (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
-            hipLaunchKernelGGL((k_inflate<true, true>), dim3(nb), dim3(64), 0, stream, hdr_len, d_in, blk,
+            hipLaunchKernelGGL((k_inflate<true, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
                                (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)sc.redo);
         } else if (debug == 2) {  // k_lzcopy's clocks instead of k_inflate_seg's
             GZPX_LAUNCH_SEG(false);
             hipLaunchKernelGGL((k_lzcopy<true>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off,
                                d_out, (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
-            hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, hdr_len, d_in, blk,
+            hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
                                (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)sc.redo);
         } else {
             GZPX_LAUNCH_SEG(false);
             hipLaunchKernelGGL((k_lzcopy<false>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off,
                                d_out, (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
-            hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, hdr_len, d_in, blk,
+            hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
                                (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)sc.redo);
         }
 #undef GZPX_LAUNCH_SEG
     } else if (debug) {
-        hipLaunchKernelGGL((k_inflate<true, true>), dim3(nb), dim3(64), 0, stream, hdr_len, d_in, blk,
+        hipLaunchKernelGGL((k_inflate<true, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
                            (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)nullptr);
     } else {
-        hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, hdr_len, d_in, blk,
+        hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
                            (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)nullptr);
     }
+}
+
+void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes,
+                    uint32_t nb, void *d_blk, uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap,
+                    uint32_t *d_crc_found, const CrcConsts &cc, int debug, hipEvent_t ev_begin,
+                    hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc, int route, hipEvent_t ev_mid) {
+    static_assert(sizeof(DBlock) == sizeof(DBlockHost), "the host allocates and reads the records as DBlockHost");
+    DBlock *blk = (DBlock *)d_blk;
+    const bool seg = route != kInflateRouteWave && sc.mlist && sc.tfirst && sc.redo;
+    hipLaunchKernelGGL(k_dinit, dim3((nb + 255) / 256), dim3(256), 0, stream, hdr_len, nb, d_in, d_offsets, d_sizes, blk,
+                       seg ? sc.redo : (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_dscan, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, d_out_off);
+    if (ev_begin) (void)hipEventRecord(ev_begin, stream);
+    launch_inflate_members(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, debug, stream, sc, seg, ev_mid);
     if (ev_end) (void)hipEventRecord(ev_end, stream);
     hipLaunchKernelGGL(k_dcrc32, dim3(nb), dim3(kCrcThreads), 0, stream, (const uint8_t *)d_out,
                        (const uint64_t *)d_out_off, (const DBlock *)blk, d_crc_found, cc);
     if (sc.summary)
         hipLaunchKernelGGL(k_dsummary, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, (const uint32_t *)d_crc_found, sc.summary);
+}
+
+// A batch of members in a wrapper (gzpx_wrap.h).  Everything is read from and written to device memory; what the host
+// reads afterwards is k_dresult's record in sc.summary.  `d_slot` is scratch of nb words.
+void launch_inflate_batch(int wrap, int short_ok, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets,
+                          const uint32_t *d_sizes, const uint32_t *d_out_sizes, uint32_t nb, void *d_blk, uint32_t *d_slot,
+                          uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap, uint32_t *d_check, const CrcConsts &cc,
+                          int debug, hipEvent_t ev_begin, hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc,
+                          int route, uint64_t *d_user_off, void *d_results, hipEvent_t ev_mid, hipEvent_t ev_check) {
+    DBlock *blk = (DBlock *)d_blk;
+    // (fewer bytes than the slot are k_inflate's to see: k_inflate_seg hands such a member over anyway)
+    const bool seg = route != kInflateRouteWave && !short_ok && sc.mlist && sc.tfirst && sc.redo;
+    WrapTable t{d_in, in_len, d_offsets, d_sizes, d_out_sizes, (uint32_t)wrap};
+    hipLaunchKernelGGL(k_dinit_wrap, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, t, blk, d_slot,
+                       seg ? sc.redo : (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_dscan_slots, dim3(1), dim3(256), 0, stream, nb, (const uint32_t *)d_slot, blk, out_cap, d_out_off);
+    if (ev_begin) (void)hipEventRecord(ev_begin, stream);
+    launch_inflate_members(d_in, nb, blk, d_out_off, d_out, out_cap, d_check, cc, debug, stream, sc, seg, ev_mid);
+    if (ev_end) (void)hipEventRecord(ev_end, stream);
+    if (wrap == kWrapGzip)
+        hipLaunchKernelGGL(k_dcrc32, dim3(nb), dim3(kCrcThreads), 0, stream, (const uint8_t *)d_out,
+                           (const uint64_t *)d_out_off, (const DBlock *)blk, d_check, cc);
+    else if (wrap == kWrapZlib)
+        hipLaunchKernelGGL(k_dadler32, dim3(nb), dim3(kAdlerThreads), 0, stream, (const uint8_t *)d_out,
+                           (const uint64_t *)d_out_off, (const DBlock *)blk, d_check);
+    if (ev_check) (void)hipEventRecord(ev_check, stream);
+    hipLaunchKernelGGL(k_dresult, dim3(1), dim3(256), 0, stream, nb, (uint32_t)wrap, (uint32_t)(short_ok ? 1 : 0),
+                       (const DBlock *)blk, (const uint32_t *)d_slot, (const uint32_t *)d_check, (const uint64_t *)d_out_off,
+                       (WrapResult *)d_results, d_user_off, sc.summary);
+}
+
+// gzpx_adler32: (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
+void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream) {
+    const uint32_t tiles = (uint32_t)((n + kAdlerTile - 1) / kAdlerTile);
+    if (tiles) hipLaunchKernelGGL(k_adler32_tiles, dim3(tiles), dim3(kAdlerThreads), 0, stream, d_in, n, d_out3);
 }
 
 // Member discovery (gzpx_mscan.h).  Everything the later kernels need to know about the candidates they work on is
@@ -5901,8 +5952,8 @@ void launch_member_emit(const MemberScanScratch &m, uint32_t n_emit, uint64_t *d
 void launch_member_index(const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes, uint32_t nb, void *d_blk,
                          uint64_t *d_out_off, hipStream_t stream) {
     DBlock *blk = (DBlock *)d_blk;
-    hipLaunchKernelGGL(k_dinit, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, d_in, d_offsets, d_sizes, blk,
-                       (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_dinit, dim3((nb + 255) / 256), dim3(256), 0, stream, 18u, nb, d_in, d_offsets, d_sizes, blk,
+                       (uint32_t *)nullptr);  // (the footers only: nothing reads the payload bounds)
     hipLaunchKernelGGL(k_dscan, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, d_out_off);
 }
 

@@ -376,6 +376,66 @@ int gzpx_read_ranges_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const void *d
                             void *hip_stream);
 int gzpx_dctx_last_ranges_members(gzpx_dctx *ctx, size_t *n_members_read);
 int gzpx_dctx_last_ranges_ms(gzpx_dctx *ctx, float ms[3]);
+/* ---- batches of independent DEFLATE members that this library did not write (gzpx_wrap.h): GZIP pages of Parquet,
+ * zlib chunks of HDF5 / Zarr / ORC, PNG IDAT streams, members of a multi-member gzip file whose extents are known.
+ * The counterpart of libdeflate_deflate_decompress / libdeflate_zlib_decompress / libdeflate_gzip_decompress for a
+ * table of members in device memory: member i is d_in[in_offsets[i], in_offsets[i] + in_sizes[i]), wrapper included;
+ * the members are inflated back to back by the kernels that inflate BGZF, each is checked with the checksum its
+ * wrapper carries, and the call reports a status per member.
+ *   Context: any gzpx_dctx, whatever format it was created for.  Runs under the context's lock, uses one slot,
+ *   honours gzpx_dctx_set_route, returns synchronised; hip_stream as for gzpx_decompress_stream_device.
+ *   Tables: d_in_offsets / d_in_sizes / d_out_sizes / d_out_offsets / d_results are DEVICE arrays; none crosses to the
+ *   host in either direction (what comes back is one 32-byte record).  n == 0 is OK with 0 bytes.
+ *   Placement: member i's slot is out_sizes[i] bytes (d_out_sizes == NULL, GZIP only: its trailer's ISIZE; 0 for a
+ *   member whose table entry is invalid); the slots lie back to back in table order, d_out_offsets (n + 1 entries) is
+ *   their exclusive prefix sum with [n] = *out_len, and no offset depends on whether a member failed.  A failed
+ *   member's slot holds nothing of use.  Bytes of d_out at and behind min(*out_len, out_cap) are never written.
+ *   Sizes: out_sizes[i] is the exact number of bytes member i inflates to (libdeflate without actual_out_nbytes_ret).
+ *   With GZPX_BATCH_SHORT_OK it is a capacity, `produced` says how much came out, and the rest of the slot is zeroed;
+ *   every member of such a call goes through the one-wave-per-member kernel (GZPX_INFLATE_WAVE), so it is NOT the
+ *   fast case.  The flag is refused (GZPX_ERR_INVALID_ARG) with GZIP, whose trailer states the size, and with
+ *   d_out_sizes == NULL.  GZIP with d_out_sizes: an ISIZE that differs from out_sizes[i] fails the member with
+ *   GZPX_ERR_INVALID_CHECK (found = ISIZE, expected = out_sizes[i]); nothing is decoded for it.  A slot of 0 bytes is
+ *   not decoded (as an ISIZE of 0 on the BGZF path); its check, taken over no bytes, still has to match.
+ *   Status of one member, the first that applies:
+ *     GZPX_ERR_INVALID_ARG         the table entry reaches outside [0, in_len), or the member is shorter than its
+ *                                  wrapper (ZLIB 6 bytes, GZIP 18)
+ *     GZPX_ERR_INVALID_HEADER      ZLIB: CM != 8, CINFO > 7, (CMF << 8 | FLG) % 31 != 0, or FDICT set (preset
+ *                                  dictionaries are not supported).  GZIP: wrong magic, CM != 8, a reserved flag bit
+ *                                  (5-7) set, or an FEXTRA / FNAME / FCOMMENT / FHCRC field that does not end in front
+ *                                  of the member's last 8 bytes.  FTEXT is ignored; FHCRC's two bytes are skipped and
+ *                                  not verified (libdeflate does not verify them either).
+ *     GZPX_ERR_INSUFFICIENT_SPACE  the slot ends behind out_cap, or the stream has more output than the slot
+ *     GZPX_ERR_BAD_DATA            the DEFLATE stream is invalid, or ends short of the slot without SHORT_OK
+ *     GZPX_ERR_INVALID_CHECK       Adler-32 (ZLIB) or CRC-32 (GZIP) over the `produced` bytes differs from the trailer
+ *   RAW has no check.
+ *   Trailer: the member's last 4 (ZLIB) or 8 (GZIP) bytes AS THE TABLE GIVES THEM; payload bytes between the final
+ *   block and the trailer are ignored, as on the BGZF path.  This is where the call is stricter than libdeflate about
+ *   extents: libdeflate finds the trailer behind the final block and ignores what follows it, so a member has to be
+ *   cut exactly here.
+ *   Returns the status of the first failing member in table order with info->block = its index (found / expected
+ *   for GZPX_ERR_INVALID_CHECK); every other member is still inflated and checked in full, d_results says which
+ *   failed, *n_failed how many.  *out_len is the sum of the slots in every case.
+ * gzpx_dctx_last_check_ms: HIP-event duration of the last batch call's check kernel (Adler-32 or the CRC-32 pass
+ * behind the copy kernel's own; 0 for RAW bar the event pair); gzpx_dctx_last_kernel_ms gives the inflate kernels. */
+#define GZPX_WRAP_RAW  0  /* RFC 1951: no header, no trailer, no check                          */
+#define GZPX_WRAP_ZLIB 1  /* RFC 1950: CMF/FLG, Adler-32 (big endian) behind the stream         */
+#define GZPX_WRAP_GZIP 2  /* RFC 1952: any legal header fields, CRC-32 + ISIZE behind the stream */
+#define GZPX_BATCH_SHORT_OK 1u  /* flags: out_sizes are capacities, fewer bytes are accepted (RAW, ZLIB) */
+typedef struct gzpx_member_result {
+    uint32_t status;          /* GZPX_OK or the GZPX_ERR_* of this member            */
+    uint32_t produced;        /* bytes inflated into the member's slot                */
+    uint32_t found, expected; /* GZPX_ERR_INVALID_CHECK: the two values               */
+} gzpx_member_result;
+int gzpx_inflate_batch_device(gzpx_dctx *ctx, int wrap, unsigned flags,
+                              const void *d_in, size_t in_len,
+                              const uint64_t *d_in_offsets, const uint32_t *d_in_sizes, /* DEVICE arrays [n] */
+                              const uint32_t *d_out_sizes,   /* DEVICE [n]; may be NULL for GZIP: the footers' ISIZE */
+                              size_t n, void *d_out, size_t out_cap,
+                              uint64_t *d_out_offsets,       /* DEVICE [n + 1], optional: written */
+                              gzpx_member_result *d_results, /* DEVICE [n], optional: written */
+                              size_t *out_len, size_t *n_failed, gzpx_check_info *info, void *hip_stream);
+int gzpx_dctx_last_check_ms(gzpx_dctx *ctx, float *ms);
 typedef struct gzpx_decompressor gzpx_decompressor;
 gzpx_decompressor *gzpx_alloc_decompressor(void);
 /* 0 = ok (short output allowed, *actual = bytes produced), GZPX_ERR_BAD_DATA, GZPX_ERR_INSUFFICIENT_SPACE */

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string.h>
@@ -19,6 +20,7 @@
 
 #include "../../include/gzpx.h"
 #include "gzpx_device.h"
+#include "gzpx_own.h"
 
 using namespace gzpx;
 
@@ -72,18 +74,21 @@ constexpr int kSlots = 3;  // slabs of one context that may be in flight (copy i
 // One slab in flight.  Host-buffer jobs own a pair of device staging buffers per slot, so the H2D
 // copy of slab k+1 and the D2H copy of slab k-1 run (on their own streams) while the kernels of
 // slab k occupy the compute stream.
-struct Slot {
+struct Slot : NoCopy {
     int state = 0;  // 0 free, 1 submitted, 2 a thread is inside wait()
     uint64_t gen = 0;
+    Event ev_h2d, ev_kernels, ev_d2h;  // (created with the slot's first job)
+    Event ev_dom_b, ev_dom_e;          // profiling mode 2: around the dominant stage of this job (timing enabled)
+    bool dom_timed = false;            // ... recorded for this job (read back in wait)
     uint8_t *d_in = nullptr, *d_out = nullptr;  // staging of host-buffer jobs (grown on demand)
     size_t d_in_cap = 0, d_out_cap = 0;
-    hipEvent_t ev_h2d = nullptr, ev_kernels = nullptr, ev_d2h = nullptr;
-    hipEvent_t ev_dom_b = nullptr, ev_dom_e = nullptr;  // profiling mode 2: around the dominant stage of this job
-    bool dom_timed = false;                             // ... recorded for this job (read back in wait)
+    Allocs in_mem, out_mem;
     SlabResult *d_results = nullptr, *h_results = nullptr;  // one per batch of the slab (h_: pinned)
     size_t results_cap = 0;
+    Allocs results_mem;
     uint32_t *h_sizes = nullptr;  // pinned: framed size of every block of the slab
     size_t sizes_cap = 0;
+    Allocs sizes_mem;
     // the job
     uint8_t *job_d_out = nullptr;  // where the kernels wrote
     size_t job_out_cap = 0;
@@ -95,27 +100,31 @@ struct Slot {
 
 }  // namespace
 
-struct gzpx_ctx {
+// (members are destroyed last to first: memory, then events, then streams)
+struct gzpx_ctx : NoCopy {
     gzpx_config cfg;
     Config dcfg;
     CrcConsts crc_consts;
-    hipStream_t stream = nullptr;  // compute: every kernel of this context, in submission order
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    hipStream_t s_side = nullptr;  // k_crc32 next to k_candidates (needs only the input)
-    hipEvent_t ev_meta = nullptr, ev_crc = nullptr;    // fork / join of the side stream
-    hipEvent_t ev_crc_t0 = nullptr, ev_crc_t1 = nullptr;  // timing of k_crc32 when profiling
-    hipEvent_t ev_dep = nullptr;  // "the caller's stream got this far" (device jobs)
-    hipEvent_t prof_ev[2 * 64] = {nullptr};  // measurement mode: begin / end of launch groups
+    Stream stream;  // compute: every kernel of this context, in submission order
+    Stream s_h2d, s_d2h;
+    Stream s_side;  // k_crc32 next to k_candidates (needs only the input); lowest priority
+    Event ev_meta, ev_crc;        // fork / join of the side stream
+    Event ev_crc_t0, ev_crc_t1;   // timing of k_crc32 when profiling
+    Event ev_dep;  // "the caller's stream got this far" (device jobs)
+    Event prof_ev[2 * kProfPairs];  // measurement mode: begin / end of launch groups
     int prof_stage[64] = {0};
     int prof_b[64] = {0}, prof_e[64] = {0};  // a group's begin / end event (indices into prof_ev)
     int prof_n = 0;
     uint32_t batch_blocks = 0;
     Scratch scratch = {};
     SnapScratch snap = {};  // GZPX_FORMAT_SNAP only
-    Slot slots[kSlots];
-    uint64_t next_gen = 1;
     BlockMeta *h_meta = nullptr;  // pinned; CRC-only contexts and the debug hooks
     SubMeta *h_sub = nullptr;     // pinned, max_sub entries (debug hooks)
+    Allocs fixed;     // everything alloc_scratch allocates, but for ...
+    Allocs lanes;     // ... scratch.no_*: the near-optimal lanes (retried with fewer of them)
+    Allocs snap_dbg;  // snap.dbg, while gzpx_debug_snap has it enabled
+    Slot slots[kSlots];
+    uint64_t next_gen = 1;
     int profiling = 0;  // 0 off, 1 every stage, 2 the dominant stage only (two markers per batch instead of thirteen)
     bool crc_only = false;
     float stage_ms[GZPX_N_STAGES] = {0};
@@ -126,16 +135,6 @@ struct gzpx_ctx {
 };
 
 namespace {
-
-// (GZPX_TRACE in the environment: the failing runtime call is named on stderr)
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) {                                                                         \
-            if (getenv("GZPX_TRACE")) fprintf(stderr, "gzpx: %s:%d %s -> %s\n", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            return GZPX_ERR_DEVICE;                                                                     \
-        }                                                                                               \
-    } while (0)
 
 thread_local int t_last_status = GZPX_OK;  // libdeflate-shaped calls have no status channel
 
@@ -174,40 +173,41 @@ int alloc_scratch(gzpx_ctx *ctx) {
     const size_t nb = ctx->batch_blocks;
     const Config &c = ctx->dcfg;
     Scratch &s = ctx->scratch;
-    HIP_TRY(hipMalloc((void **)&s.meta, nb * sizeof(BlockMeta)));
+    Allocs &a = ctx->fixed;
+    GZPX_TRY(a.dev(s.meta, nb * sizeof(BlockMeta)));
     if (ctx->cfg.format == GZPX_FORMAT_SNAP) {
         SnapScratch &ss = ctx->snap;
         const size_t chunks = nb * snap_chunks_per_buffer((uint32_t)ctx->cfg.buffer_size);
-        HIP_TRY(hipMalloc((void **)&ss.stage, chunks * kSnapStageBytes));
-        HIP_TRY(hipMalloc((void **)&ss.clen, chunks * 4));
-        HIP_TRY(hipMalloc((void **)&ss.crc, chunks * 4));
-        HIP_TRY(hipMalloc((void **)&ss.coff, chunks * 4));
-        HIP_TRY(hipMalloc((void **)&s.out_off, (nb + 1) * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc((void **)&s.sizes, nb * sizeof(uint32_t)));
+        GZPX_TRY(a.dev(ss.stage, chunks * kSnapStageBytes));
+        GZPX_TRY(a.dev(ss.clen, chunks * 4));
+        GZPX_TRY(a.dev(ss.crc, chunks * 4));
+        GZPX_TRY(a.dev(ss.coff, chunks * 4));
+        GZPX_TRY(a.dev(s.out_off, (nb + 1) * sizeof(uint64_t)));
+        GZPX_TRY(a.dev(s.sizes, nb * sizeof(uint32_t)));
         return GZPX_OK;
     }
     if (ctx->crc_only) {  // gzpx_crc32's private context: k_init_meta + k_crc32 only
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_meta, nb * sizeof(BlockMeta), hipHostMallocDefault));
+        GZPX_TRY(a.pinned(ctx->h_meta, nb * sizeof(BlockMeta)));
         return GZPX_OK;
     }
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_meta, sizeof(BlockMeta), hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&s.sub, nb * (size_t)c.max_sub * sizeof(SubMeta)));
-    HIP_TRY(hipMalloc((void **)&s.cand, nb * (size_t)c.stride * sizeof(uint16_t)));
-    HIP_TRY(hipMalloc((void **)&s.len8, nb * (size_t)c.stride));
-    HIP_TRY(hipMalloc((void **)&s.which, nb * (size_t)(c.stride / 32) * 4));
-    HIP_TRY(hipMalloc((void **)&s.alt, nb * (size_t)c.stride * sizeof(uint16_t)));
-    HIP_TRY(hipMalloc((void **)&s.tok, nb * (size_t)c.stride * 4));
-    HIP_TRY(hipMalloc((void **)&s.redo, (nb + 1 + 8) * sizeof(uint32_t)));
+    GZPX_TRY(a.pinned(ctx->h_meta, sizeof(BlockMeta)));
+    GZPX_TRY(a.dev(s.sub, nb * (size_t)c.max_sub * sizeof(SubMeta)));
+    GZPX_TRY(a.dev(s.cand, nb * (size_t)c.stride * sizeof(uint16_t)));
+    GZPX_TRY(a.dev(s.len8, nb * (size_t)c.stride));
+    GZPX_TRY(a.dev(s.which, nb * (size_t)(c.stride / 32) * 4));
+    GZPX_TRY(a.dev(s.alt, nb * (size_t)c.stride * sizeof(uint16_t)));
+    GZPX_TRY(a.dev(s.tok, nb * (size_t)c.stride * 4));
+    GZPX_TRY(a.dev(s.redo, (nb + 1 + 8) * sizeof(uint32_t)));
     HIP_TRY(hipMemset(s.redo, 0, (nb + 1 + 8) * sizeof(uint32_t)));
     s.claim = s.redo + nb + 1;
     if (c.level >= 2) {  // hc_matchfinder levels: hash4 chain links + per-block parse state
-        HIP_TRY(hipMalloc((void **)&s.d4, nb * (size_t)c.stride * sizeof(uint16_t)));
-        HIP_TRY(hipMalloc((void **)&s.hc, nb * sizeof(HcState)));
-        HIP_TRY(hipMalloc((void **)&s.pending, 64));
+        GZPX_TRY(a.dev(s.d4, nb * (size_t)c.stride * sizeof(uint16_t)));
+        GZPX_TRY(a.dev(s.hc, nb * sizeof(HcState)));
+        GZPX_TRY(a.dev(s.pending, 64));
     }
     if (c.lazy) {  // levels 5-9: the matches of the half / quarter depth searches
-        HIP_TRY(hipMalloc((void **)&s.lz_len, nb * 2 * (size_t)c.stride));
-        HIP_TRY(hipMalloc((void **)&s.lz_dist, nb * 2 * (size_t)c.stride * sizeof(uint16_t)));
+        GZPX_TRY(a.dev(s.lz_len, nb * 2 * (size_t)c.stride));
+        GZPX_TRY(a.dev(s.lz_dist, nb * 2 * (size_t)c.stride * sizeof(uint16_t)));
     }
     if (c.level >= 10) {
         // levels 10-12: one lane per block in flight, each with its trees / cache / path nodes (gzpx_nearopt.hip);
@@ -223,18 +223,11 @@ int alloc_scratch(gzpx_ctx *ctx) {
         size_t lanes = budget / per_lane;
         if (lanes > nb) lanes = nb;
         if (lanes < 1) lanes = 1;
-        for (;;) {
-            const bool ok = hipMalloc(&s.no_state, lanes * no_lane_bytes()) == hipSuccess &&
-                            hipMalloc((void **)&s.no_cache, lanes * no_cache_bytes()) == hipSuccess &&
-                            hipMalloc((void **)&s.no_nodes, lanes * no_nodes_bytes(c.block_size)) == hipSuccess;
-            if (ok) break;
+        Allocs &l = ctx->lanes;
+        while (l.dev(s.no_state, lanes * no_lane_bytes()) != GZPX_OK || l.dev(s.no_cache, lanes * no_cache_bytes()) != GZPX_OK ||
+               l.dev(s.no_nodes, lanes * no_nodes_bytes(c.block_size)) != GZPX_OK) {
             (void)hipGetLastError();
-            if (s.no_state) (void)hipFree(s.no_state);
-            if (s.no_cache) (void)hipFree(s.no_cache);
-            if (s.no_nodes) (void)hipFree(s.no_nodes);
-            s.no_state = nullptr;
-            s.no_cache = nullptr;
-            s.no_nodes = nullptr;
+            l.release();
             if (lanes == 1) return GZPX_ERR_DEVICE;
             lanes = (lanes + 1) / 2;
         }
@@ -247,69 +240,36 @@ int alloc_scratch(gzpx_ctx *ctx) {
             tables[258 * k + 257] = (uint8_t)(int)(-std::log2(probs[k] / 29.0) * 16);
         }
         uint8_t *d_tables = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_tables, sizeof(tables)));
-        hipError_t te = hipMemcpy(d_tables, tables, sizeof(tables), hipMemcpyHostToDevice);
-        if (te == hipSuccess) {
-            launch_near_optimal_tables(s.no_state, s.no_lanes, d_tables, nullptr);
-            te = hipDeviceSynchronize();
-        }
-        (void)hipFree(d_tables);  // (on every path)
-        HIP_TRY(te);
+        Allocs tmp;  // (gone at the end of this block, on every path)
+        GZPX_TRY(tmp.dev(d_tables, sizeof(tables)));
+        HIP_TRY(hipMemcpy(d_tables, tables, sizeof(tables), hipMemcpyHostToDevice));
+        launch_near_optimal_tables(s.no_state, s.no_lanes, d_tables, nullptr);
+        HIP_TRY(hipDeviceSynchronize());
     }
-    HIP_TRY(hipMalloc((void **)&s.hist, nb * (size_t)c.max_sub * kHistStride * 4));
-    HIP_TRY(hipMalloc((void **)&s.codes, nb * (size_t)c.max_sub * kCodeWords * 4));
-    HIP_TRY(hipMalloc((void **)&s.hdr, nb * (size_t)c.max_sub * kHdrWords * 4));
-    HIP_TRY(hipMalloc((void **)&s.out_off, (nb + 1) * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void **)&s.sizes, nb * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_sub, (size_t)c.max_sub * sizeof(SubMeta), hipHostMallocDefault));
+    GZPX_TRY(a.dev(s.hist, nb * (size_t)c.max_sub * kHistStride * 4));
+    GZPX_TRY(a.dev(s.codes, nb * (size_t)c.max_sub * kCodeWords * 4));
+    GZPX_TRY(a.dev(s.hdr, nb * (size_t)c.max_sub * kHdrWords * 4));
+    GZPX_TRY(a.dev(s.out_off, (nb + 1) * sizeof(uint64_t)));
+    GZPX_TRY(a.dev(s.sizes, nb * sizeof(uint32_t)));
+    GZPX_TRY(a.pinned(ctx->h_sub, (size_t)c.max_sub * sizeof(SubMeta)));
     return GZPX_OK;
 }
 
-void free_slot(Slot &sl) {
-    if (sl.d_in) (void)hipFree(sl.d_in);
-    if (sl.d_out) (void)hipFree(sl.d_out);
-    if (sl.d_results) (void)hipFree(sl.d_results);
-    if (sl.h_results) (void)hipHostFree(sl.h_results);
-    if (sl.h_sizes) (void)hipHostFree(sl.h_sizes);
-    if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);
-    if (sl.ev_kernels) (void)hipEventDestroy(sl.ev_kernels);
-    if (sl.ev_d2h) (void)hipEventDestroy(sl.ev_d2h);
-    if (sl.ev_dom_b) (void)hipEventDestroy(sl.ev_dom_b);
-    if (sl.ev_dom_e) (void)hipEventDestroy(sl.ev_dom_e);
-    sl = Slot();
-}
-
-void free_scratch(gzpx_ctx *ctx) {
-    Scratch &s = ctx->scratch;
-    if (s.meta) (void)hipFree(s.meta);
-    if (s.sub) (void)hipFree(s.sub);
-    if (ctx->h_sub) (void)hipHostFree(ctx->h_sub);
-    if (s.cand) (void)hipFree(s.cand);
-    if (s.tok) (void)hipFree(s.tok);
-    if (s.redo) (void)hipFree(s.redo);
-    if (s.no_state) (void)hipFree(s.no_state);
-    if (s.no_cache) (void)hipFree(s.no_cache);
-    if (s.no_nodes) (void)hipFree(s.no_nodes);
-    if (s.len8) (void)hipFree(s.len8);
-    if (s.which) (void)hipFree(s.which);
-    if (s.alt) (void)hipFree(s.alt);
-    if (s.d4) (void)hipFree(s.d4);
-    if (s.hc) (void)hipFree(s.hc);
-    if (s.pending) (void)hipFree(s.pending);
-    if (s.lz_len) (void)hipFree(s.lz_len);
-    if (s.lz_dist) (void)hipFree(s.lz_dist);
-    if (s.hist) (void)hipFree(s.hist);
-    if (s.codes) (void)hipFree(s.codes);
-    if (s.hdr) (void)hipFree(s.hdr);
-    if (s.out_off) (void)hipFree(s.out_off);
-    if (s.sizes) (void)hipFree(s.sizes);
-    if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
-    SnapScratch &ss = ctx->snap;
-    for (void *p : {(void *)ss.stage, (void *)ss.clen, (void *)ss.crc, (void *)ss.coff, (void *)ss.dbg})
-        if (p) (void)hipFree(p);
-    ss = SnapScratch{};
-    for (Slot &sl : ctx->slots) free_slot(sl);
-    s = Scratch{};
+// Everything a context holds for its whole life: streams, events, the scratch of one batch.  A failure leaves what
+// exists by then to gzpx_ctx_destroy.
+int ctx_acquire(gzpx_ctx *ctx) {
+    GZPX_TRY(ctx->stream.create());
+    GZPX_TRY(ctx->s_h2d.create());
+    GZPX_TRY(ctx->s_d2h.create());
+    GZPX_TRY(ctx->s_side.create(true));
+    GZPX_TRY(ctx->ev_meta.create());
+    GZPX_TRY(ctx->ev_crc.create());
+    GZPX_TRY(ctx->ev_crc_t0.create(true));
+    GZPX_TRY(ctx->ev_crc_t1.create(true));
+    GZPX_TRY(ctx->ev_dep.create());
+    GZPX_TRY(alloc_scratch(ctx));
+    for (Event &e : ctx->prof_ev) GZPX_TRY(e.create(true));
+    return GZPX_OK;
 }
 
 // HIP-event pairs around groups of launches (measurement mode only): a stage may consist of several
@@ -499,53 +459,19 @@ int enqueue_snap_batch(gzpx_ctx *ctx, const uint8_t *d_in, size_t in_len, uint32
 }
 
 int slot_reserve(Slot &sl, size_t n_batches, size_t n_blocks) {
-    if (n_batches > sl.results_cap) {
-        if (sl.d_results) (void)hipFree(sl.d_results);
-        if (sl.h_results) (void)hipHostFree(sl.h_results);
-        sl.d_results = sl.h_results = nullptr;
-        sl.results_cap = 0;
-        const size_t cap = n_batches + 8;
-        HIP_TRY(hipMalloc((void **)&sl.d_results, cap * sizeof(SlabResult)));
-        HIP_TRY(hipHostMalloc((void **)&sl.h_results, cap * sizeof(SlabResult), hipHostMallocDefault));
-        sl.results_cap = cap;
-    }
-    if (n_blocks > sl.sizes_cap) {
-        if (sl.h_sizes) (void)hipHostFree(sl.h_sizes);
-        sl.h_sizes = nullptr;
-        sl.sizes_cap = 0;
-        const size_t cap = n_blocks + n_blocks / 4 + 64;
-        HIP_TRY(hipHostMalloc((void **)&sl.h_sizes, cap * sizeof(uint32_t), hipHostMallocDefault));
-        sl.sizes_cap = cap;
-    }
-    return GZPX_OK;
+    GZPX_TRY(grow(sl.results_mem, sl.results_cap, n_batches, n_batches + 8, [&](size_t cap) -> int {
+        GZPX_TRY(sl.results_mem.dev(sl.d_results, cap * sizeof(SlabResult)));
+        return sl.results_mem.pinned(sl.h_results, cap * sizeof(SlabResult));
+    }));
+    return grow(sl.sizes_mem, sl.sizes_cap, n_blocks, n_blocks + n_blocks / 4 + 64,
+                [&](size_t cap) { return sl.sizes_mem.pinned(sl.h_sizes, cap * sizeof(uint32_t)); });
 }
 
 int slot_staging(Slot &sl, size_t in_len, size_t out_need) {
-    if (in_len + 16 > sl.d_in_cap) {
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        sl.d_in = nullptr;
-        sl.d_in_cap = 0;
-        const size_t cap = in_len + in_len / 8 + 4096;
-        HIP_TRY(hipMalloc((void **)&sl.d_in, cap));
-        sl.d_in_cap = cap;
-    }
-    if (out_need > sl.d_out_cap) {
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        sl.d_out = nullptr;
-        sl.d_out_cap = 0;
-        const size_t cap = out_need + out_need / 8 + 4096;
-        HIP_TRY(hipMalloc((void **)&sl.d_out, cap));
-        sl.d_out_cap = cap;
-    }
-    return GZPX_OK;
-}
-
-// The side stream runs at the lowest priority the device offers: its workgroups are only meant to
-// fill what the main stream's kernels leave free.
-hipError_t create_side_stream(hipStream_t *s) {
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-    return hipStreamCreateWithPriority(s, hipStreamNonBlocking, least);
+    GZPX_TRY(grow(sl.in_mem, sl.d_in_cap, in_len + 16, in_len + in_len / 8 + 4096,
+                  [&](size_t cap) { return sl.in_mem.dev(sl.d_in, cap); }));
+    return grow(sl.out_mem, sl.d_out_cap, out_need, out_need + out_need / 8 + 4096,
+                [&](size_t cap) { return sl.out_mem.dev(sl.d_out, cap); });
 }
 
 int check_slab_args(const gzpx_ctx *ctx, const void *in, size_t in_len, int mode, const void *out) {
@@ -597,11 +523,11 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
     }
     Slot &sl = ctx->slots[si];
     if (!sl.ev_kernels) {
-        HIP_TRY(hipEventCreateWithFlags(&sl.ev_h2d, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl.ev_kernels, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl.ev_d2h, hipEventDisableTiming));
-        HIP_TRY(hipEventCreate(&sl.ev_dom_b));
-        HIP_TRY(hipEventCreate(&sl.ev_dom_e));
+        GZPX_TRY(sl.ev_h2d.create());
+        GZPX_TRY(sl.ev_kernels.create());
+        GZPX_TRY(sl.ev_d2h.create());
+        GZPX_TRY(sl.ev_dom_b.create(true));
+        GZPX_TRY(sl.ev_dom_e.create(true));
     }
     const size_t bs = ctx->cfg.buffer_size;
     const uint64_t total_nb = blocks_of(ctx, in_len);
@@ -630,6 +556,7 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
     // profiling mode 2 on a one-batch slab: the job carries its own pair of events around the dominant stage and
     // stays asynchronous (the pair is read when the ticket is waited for); every other measurement waits per batch
     sl.dom_timed = ctx->profiling == 2 && n_batches == 1;
+    const hipEvent_t dom_b = sl.dom_timed ? sl.ev_dom_b.h : nullptr, dom_e = sl.dom_timed ? sl.ev_dom_e.h : nullptr;
     const int is_last = mode == GZPX_SLAB_LAST;
     for (uint64_t bi = 0; bi < n_batches; bi++) {
         const uint64_t b0 = bi * ctx->batch_blocks;
@@ -640,12 +567,10 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
         const int last_batch = (b0 + nb == total_nb) ? is_last : 0;
         if (ctx->cfg.format == GZPX_FORMAT_SNAP)
             rc = enqueue_snap_batch(ctx, d_in + in_begin, in_batch, nb, d_out, out_cap, stream,
-                                    bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi,
-                                    sl.dom_timed ? sl.ev_dom_b : nullptr, sl.dom_timed ? sl.ev_dom_e : nullptr);
+                                    bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi, dom_b, dom_e);
         else
             rc = enqueue_batch(ctx, d_in + in_begin, in_batch, nb, last_batch, d_out, out_cap, stream,
-                               bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi,
-                               sl.dom_timed ? sl.ev_dom_b : nullptr, sl.dom_timed ? sl.ev_dom_e : nullptr);
+                               bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi, dom_b, dom_e);
         if (rc != GZPX_OK) {
             (void)hipStreamSynchronize(stream);
             return rc;
@@ -864,21 +789,7 @@ int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
         if (ctx->batch_blocks > fit) ctx->batch_blocks = (uint32_t)fit;
     }
     if (ctx->batch_blocks == 0) ctx->batch_blocks = 1;
-    int rc = GZPX_OK;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&ctx->s_h2d, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&ctx->s_d2h, hipStreamNonBlocking) != hipSuccess ||
-        create_side_stream(&ctx->s_side) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_meta, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_crc, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreate(&ctx->ev_crc_t0) != hipSuccess || hipEventCreate(&ctx->ev_crc_t1) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_dep, hipEventDisableTiming) != hipSuccess)
-        rc = GZPX_ERR_DEVICE;
-    if (rc == GZPX_OK) rc = alloc_scratch(ctx);
-    if (rc == GZPX_OK) {
-        for (int i = 0; i < 2 * kProfPairs; i++)
-            if (hipEventCreate(&ctx->prof_ev[i]) != hipSuccess) rc = GZPX_ERR_DEVICE;
-    }
+    const int rc = ctx_acquire(ctx);
     if (rc != GZPX_OK) {
         gzpx_ctx_destroy(ctx);
         return rc;
@@ -894,22 +805,7 @@ extern "C" {
 void gzpx_ctx_destroy(gzpx_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->cfg.device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->s_h2d) (void)hipStreamSynchronize(ctx->s_h2d);
-    if (ctx->s_d2h) (void)hipStreamSynchronize(ctx->s_d2h);
-    free_scratch(ctx);
-    for (hipEvent_t e : ctx->prof_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->ev_dep) (void)hipEventDestroy(ctx->ev_dep);
-    for (hipEvent_t e : {ctx->ev_meta, ctx->ev_crc, ctx->ev_crc_t0, ctx->ev_crc_t1})
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->s_side) {
-        (void)hipStreamSynchronize(ctx->s_side);
-        (void)hipStreamDestroy(ctx->s_side);
-    }
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
-    if (ctx->s_d2h) (void)hipStreamDestroy(ctx->s_d2h);
+    for (const Stream *st : {&ctx->stream, &ctx->s_h2d, &ctx->s_d2h, &ctx->s_side}) st->sync();
     delete ctx;
 }
 
@@ -1030,8 +926,12 @@ struct gzpx_multi {
     size_t buffer_size = 0;
     std::mutex mu;
     // device-resident form: every device's own output staging (its shard before the gather)
-    std::vector<uint8_t *> d_stage;
-    std::vector<size_t> d_stage_cap;
+    struct Stage {
+        uint8_t *d = nullptr;
+        size_t cap = 0;
+        Allocs mem;
+    };
+    std::unique_ptr<Stage[]> stage;  // one per device
 };
 
 namespace {
@@ -1060,6 +960,11 @@ int gzpx_multi_create(const gzpx_config *cfg, const int *devices, size_t n_devic
     gzpx_multi *m = new (std::nothrow) gzpx_multi();
     if (!m) return GZPX_ERR_DEVICE;
     m->buffer_size = cfg->buffer_size;
+    m->stage.reset(new (std::nothrow) gzpx_multi::Stage[n_devices]);
+    if (!m->stage) {
+        delete m;
+        return GZPX_ERR_DEVICE;
+    }
     for (size_t g = 0; g < n_devices; g++) {
         gzpx_config c = *cfg;
         c.device = devices[g];
@@ -1088,9 +993,8 @@ int gzpx_multi_create(const gzpx_config *cfg, const int *devices, size_t n_devic
 
 void gzpx_multi_destroy(gzpx_multi *m) {
     if (!m) return;
-    for (size_t g = 0; g < m->d_stage.size(); g++)
-        if (m->d_stage[g] && g < m->ctxs.size() && hipSetDevice(m->ctxs[g]->cfg.device) == hipSuccess)
-            (void)hipFree(m->d_stage[g]);
+    for (size_t g = 0; g < m->ctxs.size(); g++)
+        if (hipSetDevice(m->ctxs[g]->cfg.device) == hipSuccess) m->stage[g].mem.release();
     for (gzpx_ctx *c : m->ctxs) gzpx_ctx_destroy(c);
     delete m;
 }
@@ -1128,8 +1032,6 @@ int gzpx_multi_compress_slab_device(gzpx_multi *m, const void *const *d_in, size
         bool submitted = false;
     };
     std::vector<Part> parts(G);
-    m->d_stage.resize(G, nullptr);
-    m->d_stage_cap.resize(G, 0);
     int rc = GZPX_OK;
     // 1. every device: the kernels of its range, output into its own staging (devices work concurrently)
     for (size_t g = 0; g < G && rc == GZPX_OK; g++) {
@@ -1148,18 +1050,11 @@ int gzpx_multi_compress_slab_device(gzpx_multi *m, const void *const *d_in, size
             break;
         }
         const size_t need = gzpx_slab_bound(ctx, p.r.n);
-        if (need > m->d_stage_cap[g]) {
-            if (m->d_stage[g]) (void)hipFree(m->d_stage[g]);
-            m->d_stage[g] = nullptr;
-            m->d_stage_cap[g] = 0;
-            if (hipMalloc((void **)&m->d_stage[g], need + need / 8 + 4096) != hipSuccess) {
-                rc = GZPX_ERR_DEVICE;
-                break;
-            }
-            m->d_stage_cap[g] = need + need / 8 + 4096;
-        }
+        gzpx_multi::Stage &st = m->stage[g];
+        rc = grow(st.mem, st.cap, need, need + need / 8 + 4096, [&](size_t cap) { return st.mem.dev(st.d, cap); });
+        if (rc != GZPX_OK) break;
         rc = submit_locked(ctx, nullptr, (const uint8_t *)d_in[g], p.r.n, owns_end ? mode : GZPX_SLAB_FULL_BLOCKS, nullptr,
-                           m->d_stage[g], m->d_stage_cap[g], (hipStream_t)GZPX_STREAM_NONE, true, lk, &p.ticket);  // (the caller's contract: the ranges are ready)
+                           st.d, st.cap, (hipStream_t)GZPX_STREAM_NONE, true, lk, &p.ticket);  // (the caller's contract: the ranges are ready)
         p.submitted = rc == GZPX_OK;
     }
     // 2. shard sizes -> stream offsets
@@ -1192,7 +1087,7 @@ int gzpx_multi_compress_slab_device(gzpx_multi *m, const void *const *d_in, size
         if (!p.submitted || !p.c.produced) continue;
         gzpx_ctx *ctx = m->ctxs[g];
         if (hipSetDevice(ctx->cfg.device) != hipSuccess ||
-            hipMemcpyPeerAsync((uint8_t *)d_out + offs[g], root_dev, m->d_stage[g], ctx->cfg.device, p.c.produced,
+            hipMemcpyPeerAsync((uint8_t *)d_out + offs[g], root_dev, m->stage[g].d, ctx->cfg.device, p.c.produced,
                                ctx->s_d2h) != hipSuccess ||
             hipEventRecord(p.slot->ev_d2h, ctx->s_d2h) != hipSuccess)
             rc = GZPX_ERR_DEVICE;
@@ -1437,11 +1332,23 @@ uint32_t gzpx_adler32_combine(uint32_t adler1, uint32_t adler2, uint64_t len2) {
 }
 
 int gzpx_adler32_checked(uint32_t adler, const void *buf, size_t n, uint32_t *out) {
-    static std::mutex mu;
-    static uint8_t *d_in = nullptr;
-    static uint32_t *d_out3 = nullptr, *h_out3 = nullptr;
-    static hipStream_t stream = nullptr;
     constexpr size_t kChunk = (size_t)64 << 20, kTiles = kChunk / 65536;
+    // the stream and the buffers of every call, made by the first one: whole or not at all (a call that fails to
+    // make them leaves nothing behind and the next one tries again), then kept for the life of the process
+    struct State {
+        Stream stream;
+        uint8_t *d_in = nullptr;
+        uint32_t *d_out3 = nullptr, *h_out3 = nullptr;
+        Allocs mem;
+        int init() {
+            GZPX_TRY(stream.create());
+            GZPX_TRY(mem.dev(d_in, kChunk));
+            GZPX_TRY(mem.dev(d_out3, kTiles * 12));
+            return mem.pinned(h_out3, kTiles * 12);
+        }
+    };
+    static std::mutex mu;
+    static State *state = nullptr;  // (never deleted: no HIP call at process exit)
     if (!out || (!buf && n)) return GZPX_ERR_INVALID_ARG;
     *out = adler;
     if (n == 0) return GZPX_OK;
@@ -1449,12 +1356,15 @@ int gzpx_adler32_checked(uint32_t adler, const void *buf, size_t n, uint32_t *ou
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GZPX_ERR_NO_DEVICE;
     if (hipSetDevice(0) != hipSuccess) return GZPX_ERR_DEVICE;
-    if (!stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        HIP_TRY(hipMalloc((void **)&d_in, kChunk));
-        HIP_TRY(hipMalloc((void **)&d_out3, kTiles * 12));
-        HIP_TRY(hipHostMalloc((void **)&h_out3, kTiles * 12, hipHostMallocDefault));
+    if (!state) {
+        std::unique_ptr<State> fresh(new (std::nothrow) State());
+        if (!fresh) return GZPX_ERR_DEVICE;
+        GZPX_TRY(fresh->init());
+        state = fresh.release();
     }
+    uint8_t *const d_in = state->d_in;
+    uint32_t *const d_out3 = state->d_out3, *const h_out3 = state->h_out3;
+    const hipStream_t stream = state->stream;
     const uint32_t base = 65521u;
     uint32_t a = adler & 0xFFFFu, b = (adler >> 16) & 0xFFFFu;
     const uint8_t *p = (const uint8_t *)buf;
@@ -1492,9 +1402,18 @@ namespace {
 // One slab of blocks being inflated.  Everything a slab needs lives in its slot (block tables,
 // staging), so up to kSlots slabs are in flight: copy-in of one, kernels of another, copy-out of
 // a third, each on its own stream.
-struct DSlot {
+struct DSlot : NoCopy {
     int state = 0;  // 0 free, 1 submitted, 2 a thread is inside wait()
     uint64_t gen = 0;
+    Event ev_h2d, ev_kernels, ev_done;  // (all seven: created with the slot's first use)
+    Event ev_t0, ev_t1;  // around the inflate kernels (timing enabled)
+    Event ev_tm;         // behind k_inflate_seg (the decode / copy route)
+    Event ev_tc;         // behind the check kernel of gzpx_inflate_batch_device
+    bool have_check = false;  // ev_t1 .. ev_tc hold the slot's last launch
+    InflateScratch sc;  // match records / tile table of k_inflate_seg + k_lzcopy; sc.redo lives with the block tables
+    uint64_t *h_total = nullptr;    // pinned
+    uint32_t *h_summary = nullptr;  // pinned: k_dsummary's record (the first failing member, its checksums)
+    Allocs once;  // h_total, h_summary, sc.summary: 64 bytes each, made with the events
     size_t cap_blocks = 0;
     uint64_t *d_offsets = nullptr, *d_out_off = nullptr;
     uint32_t *d_sizes = nullptr, *d_crc = nullptr;
@@ -1503,82 +1422,52 @@ struct DSlot {
     uint32_t *h_crc = nullptr;    // pinned
     uint64_t *h_offsets = nullptr;  // pinned copies of the caller's arrays (the caller's may be pageable
     uint32_t *h_sizes = nullptr;    //  and must not be referenced after submit returns)
-    uint64_t *h_total = nullptr;  // pinned
-    uint32_t *h_summary = nullptr;  // pinned: k_dsummary's record (the first failing member, its checksums)
+    Allocs tables;  // the ten arrays of cap_blocks members, sc.redo among them
     bool have_blk = false;          // h_blk holds this launch's records (debug launches only)
     uint8_t *d_in = nullptr, *d_out = nullptr;
     size_t d_in_cap = 0, d_out_cap = 0;
-    InflateScratch sc;  // match records / tile table of k_inflate_seg + k_lzcopy; sc.redo lives with the block tables
+    Allocs in_mem, out_mem;
     size_t mlist_cap = 0, tfirst_cap = 0;
-    hipEvent_t ev_h2d = nullptr, ev_kernels = nullptr, ev_done = nullptr;
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // around the inflate kernels (timing enabled)
-    hipEvent_t ev_tm = nullptr;                   // behind k_inflate_seg (the decode / copy route)
-    hipEvent_t ev_tc = nullptr;                   // behind the check kernel of gzpx_inflate_batch_device
-    bool have_check = false;                      // ev_t1 .. ev_tc hold the slot's last launch
+    Allocs mlist_mem, tfirst_mem;  // sc.mlist, sc.tfirst
     size_t nb = 0;
     int route = kInflateRouteSeg;  // the route of the slot's last launch (the context's may have changed since)
 };
 
-void dslot_free_tables(DSlot &c) {
-    if (c.d_offsets) (void)hipFree(c.d_offsets);
-    if (c.d_out_off) (void)hipFree(c.d_out_off);
-    if (c.d_sizes) (void)hipFree(c.d_sizes);
-    if (c.d_crc) (void)hipFree(c.d_crc);
-    if (c.d_blk) (void)hipFree(c.d_blk);
-    if (c.h_blk) (void)hipHostFree(c.h_blk);
-    if (c.h_crc) (void)hipHostFree(c.h_crc);
-    if (c.h_offsets) (void)hipHostFree(c.h_offsets);
-    if (c.h_sizes) (void)hipHostFree(c.h_sizes);
-    if (c.sc.redo) (void)hipFree(c.sc.redo);
-    c.sc.redo = nullptr;
-    c.d_offsets = c.d_out_off = nullptr;
-    c.d_sizes = c.d_crc = nullptr;
-    c.d_blk = c.h_blk = nullptr;
-    c.h_crc = c.h_sizes = nullptr;
-    c.h_offsets = nullptr;
-    c.cap_blocks = 0;
-}
-
 int dslot_reserve(DSlot &c, size_t nb) {
     if (!c.ev_kernels) {
-        HIP_TRY(hipEventCreateWithFlags(&c.ev_h2d, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c.ev_kernels, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreate(&c.ev_t0));
-        HIP_TRY(hipEventCreate(&c.ev_t1));
-        HIP_TRY(hipEventCreate(&c.ev_tm));
-        HIP_TRY(hipEventCreate(&c.ev_tc));
-        HIP_TRY(hipHostMalloc((void **)&c.h_total, 64, hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void **)&c.h_summary, 64, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&c.sc.summary, 64));
+        GZPX_TRY(c.ev_h2d.create());
+        GZPX_TRY(c.ev_kernels.create());
+        GZPX_TRY(c.ev_done.create());
+        for (Event *e : {&c.ev_t0, &c.ev_t1, &c.ev_tm, &c.ev_tc}) GZPX_TRY(e->create(true));
+        GZPX_TRY(c.once.pinned(c.h_total, 64));
+        GZPX_TRY(c.once.pinned(c.h_summary, 64));
+        GZPX_TRY(c.once.dev(c.sc.summary, 64));
         HIP_TRY(hipMemset(c.sc.summary, 0, 64));  // (word 15: k_inflate_seg's first-block hint, kept from launch to launch)
     }
-    if (nb <= c.cap_blocks) return GZPX_OK;
-    dslot_free_tables(c);
-    const size_t cap = nb + nb / 4 + 64;
-    HIP_TRY(hipMalloc((void **)&c.d_offsets, cap * 8));
-    HIP_TRY(hipMalloc((void **)&c.d_out_off, (cap + 1) * 8));
-    HIP_TRY(hipMalloc((void **)&c.d_sizes, cap * 4));
-    HIP_TRY(hipMalloc((void **)&c.d_crc, cap * 4));
-    HIP_TRY(hipMalloc((void **)&c.d_blk, cap * sizeof(DBlockHost)));
-    HIP_TRY(hipMalloc((void **)&c.sc.redo, (cap + 2) * 4));
-    HIP_TRY(hipHostMalloc((void **)&c.h_blk, cap * sizeof(DBlockHost), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&c.h_crc, cap * 4, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&c.h_offsets, cap * 8, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&c.h_sizes, cap * 4, hipHostMallocDefault));
-    c.cap_blocks = cap;
-    return GZPX_OK;
+    Allocs &t = c.tables;
+    return grow(t, c.cap_blocks, nb, nb + nb / 4 + 64, [&](size_t cap) -> int {
+        GZPX_TRY(t.dev(c.d_offsets, cap * 8));
+        GZPX_TRY(t.dev(c.d_out_off, (cap + 1) * 8));
+        GZPX_TRY(t.dev(c.d_sizes, cap * 4));
+        GZPX_TRY(t.dev(c.d_crc, cap * 4));
+        GZPX_TRY(t.dev(c.d_blk, cap * sizeof(DBlockHost)));
+        GZPX_TRY(t.dev(c.sc.redo, (cap + 2) * 4));
+        GZPX_TRY(t.pinned(c.h_blk, cap * sizeof(DBlockHost)));
+        GZPX_TRY(t.pinned(c.h_crc, cap * 4));
+        GZPX_TRY(t.pinned(c.h_offsets, cap * 8));
+        return t.pinned(c.h_sizes, cap * 4);
+    });
 }
 
 }  // namespace
 
-struct gzpx_dctx {
+// (members are destroyed last to first: memory, then events, then streams)
+struct gzpx_dctx : NoCopy {
     int device = 0;
     int format = 0;
     CrcConsts cc;
-    hipStream_t stream = nullptr, s_h2d = nullptr, s_d2h = nullptr;
-    hipEvent_t ev_dep = nullptr;
-    DSlot slots[kSlots];
+    Stream stream, s_h2d, s_d2h;
+    Event ev_dep;
     uint64_t next_gen = 1;
     int n_cu = 0;
     int debug = 0;  // 1: instrumented k_inflate_seg / k_inflate, 2: instrumented k_lzcopy
@@ -1586,26 +1475,35 @@ struct gzpx_dctx {
     int last_slot = -1;  // the slot of the last completed launch (timing / debug counters)
     size_t last_nb = 0;
     // member discovery (gzpx_*_device calls that take no member table): scratch of one scan at a time, used under `mu`
+    Event ev_s0, ev_s1;  // around the scan kernels (created with scan_once)
+    bool have_scan = false;
     MemberScanScratch ms;
-    size_t ms_seg_cap = 0;
     uint32_t *h_rec = nullptr;  // pinned: the scan record
+    Allocs scan_once;           // ms.rec, h_rec
+    size_t ms_seg_cap = 0;
+    Allocs scan_seg;   // ms.seg_count, ms.seg_off
+    Allocs scan_cand;  // the six candidate arrays of ms.cap entries
     uint64_t *d_tab_off = nullptr;  // the walk's table for gzpx_scan_blocks_device
     uint32_t *d_tab_size = nullptr;
     size_t tab_cap = 0;
-    hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;  // around the scan kernels
-    bool have_scan = false;
+    Allocs tab_mem;
     // reads by range (gzpx_read_ranges_device): scratch of one call at a time, used under `mu`
+    Event ev_r[5];         // select [0..1], inflate [2..3], gather [3..4] (created with rr_once)
+    bool have_rr = false;  // ev_r[0..1] hold the last call's select; rr_stages: [2..4] its inflate and gather
+    bool rr_stages = false;
+    size_t last_rr_members = 0;
     RangeScratch rr;
+    uint32_t *h_rrec = nullptr;  // pinned: the record of locate + select
+    Allocs rr_once;              // rr.rec, h_rrec
     size_t rr_range_cap = 0, rr_member_cap = 0;
     uint64_t *h_ranges = nullptr;   // pinned: the caller's ranges on their way in
     uint64_t *h_out_off = nullptr;  // pinned: out_offsets on their way out
-    uint32_t *h_rrec = nullptr;     // pinned: the record of locate + select
-    uint8_t *d_stage = nullptr;     // the selected members, inflated back to back
+    Allocs rr_ranges;   // rr.ranges, first, len, src, out_off and the two pinned arrays above
+    Allocs rr_members;  // rr.diff, map, soff
+    uint8_t *d_stage = nullptr;  // the selected members, inflated back to back
     size_t stage_cap = 0;
-    hipEvent_t ev_r[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // select [0..1], inflate [2..3], gather [3..4]
-    bool have_rr = false;           // ev_r[0..1] hold the last call's select; rr_stages: [2..4] its inflate and gather
-    bool rr_stages = false;
-    size_t last_rr_members = 0;
+    Allocs stage_mem;
+    DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
 };
@@ -1627,21 +1525,10 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
 // k_inflate_seg + k_lzcopy's match records and tile table for nb members that inflate to at most out_cap bytes
 int dslot_seg_scratch(DSlot &sl, size_t out_cap, size_t nb) {
     const size_t need_m = inflate_mlist_bytes(out_cap, nb), need_t = inflate_tfirst_bytes(out_cap, nb);
-    if (need_m > sl.mlist_cap) {
-        if (sl.sc.mlist) (void)hipFree(sl.sc.mlist);
-        sl.sc.mlist = nullptr;
-        sl.mlist_cap = 0;
-        HIP_TRY(hipMalloc(&sl.sc.mlist, need_m + need_m / 8));
-        sl.mlist_cap = need_m + need_m / 8;
-    }
-    if (need_t > sl.tfirst_cap) {
-        if (sl.sc.tfirst) (void)hipFree(sl.sc.tfirst);
-        sl.sc.tfirst = nullptr;
-        sl.tfirst_cap = 0;
-        HIP_TRY(hipMalloc((void **)&sl.sc.tfirst, need_t + need_t / 8));
-        sl.tfirst_cap = need_t + need_t / 8;
-    }
-    return GZPX_OK;
+    GZPX_TRY(grow(sl.mlist_mem, sl.mlist_cap, need_m, need_m + need_m / 8,
+                  [&](size_t cap) { return sl.mlist_mem.dev(sl.sc.mlist, cap); }));
+    return grow(sl.tfirst_mem, sl.tfirst_cap, need_t, need_t + need_t / 8,
+                [&](size_t cap) { return sl.tfirst_mem.dev(sl.sc.tfirst, cap); });
 }
 
 // As on the compress side (submit_locked): a submit that fails may already have put copies and kernels on the
@@ -1690,20 +1577,10 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
     hipStream_t stream = c->stream;
     if (nb) {
         if (host_in) {  // staging
-            if (in_len + 16 > sl.d_in_cap) {
-                if (sl.d_in) (void)hipFree(sl.d_in);
-                sl.d_in = nullptr;
-                sl.d_in_cap = 0;
-                HIP_TRY(hipMalloc((void **)&sl.d_in, in_len + in_len / 8 + 4096));
-                sl.d_in_cap = in_len + in_len / 8 + 4096;
-            }
-            if (out_cap + 16 > sl.d_out_cap) {
-                if (sl.d_out) (void)hipFree(sl.d_out);
-                sl.d_out = nullptr;
-                sl.d_out_cap = 0;
-                HIP_TRY(hipMalloc((void **)&sl.d_out, out_cap + out_cap / 8 + 4096));
-                sl.d_out_cap = out_cap + out_cap / 8 + 4096;
-            }
+            GZPX_TRY(grow(sl.in_mem, sl.d_in_cap, in_len + 16, in_len + in_len / 8 + 4096,
+                          [&](size_t cap) { return sl.in_mem.dev(sl.d_in, cap); }));
+            GZPX_TRY(grow(sl.out_mem, sl.d_out_cap, out_cap + 16, out_cap + out_cap / 8 + 4096,
+                          [&](size_t cap) { return sl.out_mem.dev(sl.d_out, cap); }));
             HIP_TRY(hipMemcpyAsync(sl.d_in, host_in, in_len, hipMemcpyHostToDevice, c->s_h2d));
             d_in = sl.d_in;
             d_out = sl.d_out;
@@ -1812,43 +1689,27 @@ int dwait_ticket(gzpx_dctx *c, uint64_t ticket, size_t *out_len, gzpx_check_info
     return rc;
 }
 
-void dscan_free(gzpx_dctx *c) {
-    MemberScanScratch &m = c->ms;
-    for (void *p : {(void *)m.pos, (void *)m.size, (void *)m.succ, (void *)m.jump[0], (void *)m.jump[1], (void *)m.idx})
-        if (p) (void)hipFree(p);
-    m.pos = nullptr;
-    m.size = m.succ = m.jump[0] = m.jump[1] = m.idx = nullptr;
-    m.cap = 0;
-}
-
 int dscan_reserve(gzpx_dctx *c, size_t n_seg, size_t cap) {
     MemberScanScratch &m = c->ms;
     if (!m.rec) {
-        HIP_TRY(hipMalloc((void **)&m.rec, 64));
-        HIP_TRY(hipHostMalloc((void **)&c->h_rec, 64, hipHostMallocDefault));
-        HIP_TRY(hipEventCreate(&c->ev_s0));
-        HIP_TRY(hipEventCreate(&c->ev_s1));
+        GZPX_TRY(c->scan_once.dev(m.rec, 64));
+        GZPX_TRY(c->scan_once.pinned(c->h_rec, 64));
+        GZPX_TRY(c->ev_s0.create(true));
+        GZPX_TRY(c->ev_s1.create(true));
     }
-    if (n_seg > c->ms_seg_cap) {
-        if (m.seg_count) (void)hipFree(m.seg_count);
-        if (m.seg_off) (void)hipFree(m.seg_off);
-        m.seg_count = m.seg_off = nullptr;
-        c->ms_seg_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m.seg_count, n_seg * 4));
-        HIP_TRY(hipMalloc((void **)&m.seg_off, n_seg * 4));
-        c->ms_seg_cap = n_seg;
-    }
-    if (cap > m.cap) {
-        dscan_free(c);
-        HIP_TRY(hipMalloc((void **)&m.pos, cap * 8));
-        HIP_TRY(hipMalloc((void **)&m.size, cap * 4));
-        HIP_TRY(hipMalloc((void **)&m.succ, cap * 4));
-        HIP_TRY(hipMalloc((void **)&m.jump[0], cap * 4));
-        HIP_TRY(hipMalloc((void **)&m.jump[1], cap * 4));
-        HIP_TRY(hipMalloc((void **)&m.idx, cap * 4));
-        m.cap = (uint32_t)cap;
-    }
-    return GZPX_OK;
+    GZPX_TRY(grow(c->scan_seg, c->ms_seg_cap, n_seg, n_seg, [&](size_t n) -> int {
+        GZPX_TRY(c->scan_seg.dev(m.seg_count, n * 4));
+        return c->scan_seg.dev(m.seg_off, n * 4);
+    }));
+    Allocs &a = c->scan_cand;
+    return grow(a, m.cap, cap, cap, [&](size_t n) -> int {
+        GZPX_TRY(a.dev(m.pos, n * 8));
+        GZPX_TRY(a.dev(m.size, n * 4));
+        GZPX_TRY(a.dev(m.succ, n * 4));
+        GZPX_TRY(a.dev(m.jump[0], n * 4));
+        GZPX_TRY(a.dev(m.jump[1], n * 4));
+        return a.dev(m.idx, n * 4);
+    });
 }
 
 // gzpx_scan_blocks over d_in[0..in_len) on the device, without the cap: how many members the walk from offset 0
@@ -1906,54 +1767,28 @@ int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t afte
 
 // the calls that scan and then use a slot hold c->mu from the scan to the submit (the scan's scratch is the
 // context's): they wait for the slot first
-void rr_free_ranges(gzpx_dctx *c) {
-    RangeScratch &r = c->rr;
-    for (void *p : {(void *)r.ranges, (void *)r.first, (void *)r.len, (void *)r.src, (void *)r.out_off})
-        if (p) (void)hipFree(p);
-    if (c->h_ranges) (void)hipHostFree(c->h_ranges);
-    if (c->h_out_off) (void)hipHostFree(c->h_out_off);
-    r.ranges = r.len = r.src = r.out_off = c->h_ranges = c->h_out_off = nullptr;
-    r.first = nullptr;
-    c->rr_range_cap = 0;
-}
-
-void rr_free_members(gzpx_dctx *c) {
-    RangeScratch &r = c->rr;
-    for (void *p : {(void *)r.diff, (void *)r.map, (void *)r.soff})
-        if (p) (void)hipFree(p);
-    r.diff = r.map = nullptr;
-    r.soff = nullptr;
-    c->rr_member_cap = 0;
-}
-
 int rr_reserve(gzpx_dctx *c, size_t n_ranges, size_t n_members) {
     RangeScratch &r = c->rr;
     if (!r.rec) {
-        HIP_TRY(hipMalloc((void **)&r.rec, 64));
-        HIP_TRY(hipHostMalloc((void **)&c->h_rrec, 64, hipHostMallocDefault));
-        for (hipEvent_t &e : c->ev_r) HIP_TRY(hipEventCreate(&e));
+        GZPX_TRY(c->rr_once.dev(r.rec, 64));
+        GZPX_TRY(c->rr_once.pinned(c->h_rrec, 64));
+        for (Event &e : c->ev_r) GZPX_TRY(e.create(true));
     }
-    if (n_ranges > c->rr_range_cap) {
-        rr_free_ranges(c);
-        const size_t cap = n_ranges + n_ranges / 4 + 64;
-        HIP_TRY(hipMalloc((void **)&r.ranges, cap * 16));
-        HIP_TRY(hipMalloc((void **)&r.first, cap * 4));
-        HIP_TRY(hipMalloc((void **)&r.len, cap * 8));
-        HIP_TRY(hipMalloc((void **)&r.src, cap * 8));
-        HIP_TRY(hipMalloc((void **)&r.out_off, (cap + 1) * 8));
-        HIP_TRY(hipHostMalloc((void **)&c->h_ranges, cap * 16, hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void **)&c->h_out_off, (cap + 1) * 8, hipHostMallocDefault));
-        c->rr_range_cap = cap;
-    }
-    if (n_members + 1 > c->rr_member_cap) {
-        rr_free_members(c);
-        const size_t cap = n_members + n_members / 4 + 64;
-        HIP_TRY(hipMalloc((void **)&r.diff, cap * 4));
-        HIP_TRY(hipMalloc((void **)&r.map, cap * 4));
-        HIP_TRY(hipMalloc((void **)&r.soff, cap * 8));
-        c->rr_member_cap = cap;
-    }
-    return GZPX_OK;
+    Allocs &a = c->rr_ranges, &b = c->rr_members;
+    GZPX_TRY(grow(a, c->rr_range_cap, n_ranges, n_ranges + n_ranges / 4 + 64, [&](size_t cap) -> int {
+        GZPX_TRY(a.dev(r.ranges, cap * 16));
+        GZPX_TRY(a.dev(r.first, cap * 4));
+        GZPX_TRY(a.dev(r.len, cap * 8));
+        GZPX_TRY(a.dev(r.src, cap * 8));
+        GZPX_TRY(a.dev(r.out_off, (cap + 1) * 8));
+        GZPX_TRY(a.pinned(c->h_ranges, cap * 16));
+        return a.pinned(c->h_out_off, (cap + 1) * 8);
+    }));
+    return grow(b, c->rr_member_cap, n_members + 1, n_members + n_members / 4 + 64, [&](size_t cap) -> int {
+        GZPX_TRY(b.dev(r.diff, cap * 4));
+        GZPX_TRY(b.dev(r.map, cap * 4));
+        return b.dev(r.soff, cap * 8);
+    });
 }
 
 void dwait_free_slot(gzpx_dctx *c, std::unique_lock<std::mutex> &lk) {
@@ -1988,10 +1823,8 @@ int gzpx_dctx_create(int device, int format, gzpx_dctx **out) {
     for (unsigned l = 0; l < 10; l++) c->cc.pow64[l] = x2k(9 + l);
     c->cc.pow_tile = x2k(19);
     c->cc.pow_small = x2k(17);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming) != hipSuccess) {
+    if (c->stream.create() != GZPX_OK || c->s_h2d.create() != GZPX_OK || c->s_d2h.create() != GZPX_OK ||
+        c->ev_dep.create() != GZPX_OK) {
         gzpx_dctx_destroy(c);
         return GZPX_ERR_DEVICE;
     }
@@ -2002,38 +1835,7 @@ int gzpx_dctx_create(int device, int format, gzpx_dctx **out) {
 void gzpx_dctx_destroy(gzpx_dctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->s_h2d) (void)hipStreamSynchronize(c->s_h2d);
-    if (c->s_d2h) (void)hipStreamSynchronize(c->s_d2h);
-    for (DSlot &sl : c->slots) {
-        dslot_free_tables(sl);
-        if (sl.h_total) (void)hipHostFree(sl.h_total);
-        if (sl.h_summary) (void)hipHostFree(sl.h_summary);
-        if (sl.sc.summary) (void)hipFree(sl.sc.summary);
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.sc.mlist) (void)hipFree(sl.sc.mlist);
-        if (sl.sc.tfirst) (void)hipFree(sl.sc.tfirst);
-        for (hipEvent_t e : {sl.ev_h2d, sl.ev_kernels, sl.ev_done, sl.ev_t0, sl.ev_t1, sl.ev_tm, sl.ev_tc})
-            if (e) (void)hipEventDestroy(e);
-    }
-    rr_free_ranges(c);
-    rr_free_members(c);
-    for (void *p : {(void *)c->rr.rec, (void *)c->d_stage})
-        if (p) (void)hipFree(p);
-    if (c->h_rrec) (void)hipHostFree(c->h_rrec);
-    for (hipEvent_t e : c->ev_r)
-        if (e) (void)hipEventDestroy(e);
-    dscan_free(c);
-    for (void *p : {(void *)c->ms.seg_count, (void *)c->ms.seg_off, (void *)c->ms.rec, (void *)c->d_tab_off, (void *)c->d_tab_size})
-        if (p) (void)hipFree(p);
-    if (c->h_rec) (void)hipHostFree(c->h_rec);
-    for (hipEvent_t e : {c->ev_s0, c->ev_s1})
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_dep) (void)hipEventDestroy(c->ev_dep);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->s_h2d) (void)hipStreamDestroy(c->s_h2d);
-    if (c->s_d2h) (void)hipStreamDestroy(c->s_d2h);
+    for (const Stream *st : {&c->stream, &c->s_h2d, &c->s_d2h}) st->sync();
     delete c;
 }
 
@@ -2120,16 +1922,10 @@ int gzpx_scan_blocks_device(gzpx_dctx *c, const void *d_in, size_t in_len, uint6
     // with the cap reached in front of a whole member the walk stops there: that member's offset is `consumed`
     const bool capped = max_blocks < r.n_members;
     const size_t n = capped ? max_blocks : r.n_members, n_emit = capped ? n + 1 : n;
-    if (n_emit > c->tab_cap) {
-        if (c->d_tab_off) (void)hipFree(c->d_tab_off);
-        if (c->d_tab_size) (void)hipFree(c->d_tab_size);
-        c->d_tab_off = nullptr;
-        c->d_tab_size = nullptr;
-        c->tab_cap = 0;
-        HIP_TRY(hipMalloc((void **)&c->d_tab_off, (n_emit + n_emit / 4 + 64) * 8));
-        HIP_TRY(hipMalloc((void **)&c->d_tab_size, (n_emit + n_emit / 4 + 64) * 4));
-        c->tab_cap = n_emit + n_emit / 4 + 64;
-    }
+    GZPX_TRY(grow(c->tab_mem, c->tab_cap, n_emit, n_emit + n_emit / 4 + 64, [&](size_t cap) -> int {
+        GZPX_TRY(c->tab_mem.dev(c->d_tab_off, cap * 8));
+        return c->tab_mem.dev(c->d_tab_size, cap * 4);
+    }));
     launch_member_emit(c->ms, (uint32_t)n_emit, c->d_tab_off, c->d_tab_size, c->stream);
     HIP_TRY(hipGetLastError());
     uint64_t stop = 0;
@@ -2219,22 +2015,32 @@ int gzpx_dctx_last_scan_ms(gzpx_dctx *ctx, float *ms) {
 
 }  // extern "C"
 
-struct gzpx_dindex {
+struct gzpx_dindex : NoCopy {
     int device = 0, format = 0;
     size_t n = 0, consumed = 0;
     uint64_t inflated_len = 0;
     uint64_t *d_off = nullptr;     // [n]
     uint32_t *d_size = nullptr;    // [n]
     uint64_t *d_ustart = nullptr;  // [n + 1]
+    Allocs mem;
 };
+
+namespace {
+// what follows a failure may still be running when the caller gets its buffers back otherwise
+struct Drain {
+    hipStream_t s;
+    bool armed = true;
+    ~Drain() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
+}  // namespace
 
 extern "C" {
 
 void gzpx_dindex_destroy(gzpx_dindex *ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
-    for (void *p : {(void *)ix->d_off, (void *)ix->d_size, (void *)ix->d_ustart})
-        if (p) (void)hipFree(p);
     delete ix;
 }
 
@@ -2253,45 +2059,38 @@ int gzpx_dindex_build_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx
     if (rc != GZPX_OK) return rc;
     if (r.invalid) return GZPX_ERR_INVALID_HEADER;
     if (r.n_members > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
-    gzpx_dindex *ix = new (std::nothrow) gzpx_dindex();
+    std::unique_ptr<gzpx_dindex> ix(new (std::nothrow) gzpx_dindex());  // (c's device is current: a return frees it)
     if (!ix) return GZPX_ERR_DEVICE;
     ix->device = c->device;
     ix->format = c->format;
     ix->n = r.n_members;
     ix->consumed = r.consumed;
     const size_t n = r.n_members;
-    rc = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&ix->d_off, (n ? n : 1) * 8));
-        HIP_TRY(hipMalloc((void **)&ix->d_size, (n ? n : 1) * 4));
-        HIP_TRY(hipMalloc((void **)&ix->d_ustart, (n + 1) * 8));
-        if (n == 0) {
-            HIP_TRY(hipMemsetAsync(ix->d_ustart, 0, 8, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            return GZPX_OK;
-        }
+    Drain drain{c->stream};  // (a failure: nothing still runs on the arrays when they are freed)
+    GZPX_TRY(ix->mem.dev(ix->d_off, (n ? n : 1) * 8));
+    GZPX_TRY(ix->mem.dev(ix->d_size, (n ? n : 1) * 4));
+    GZPX_TRY(ix->mem.dev(ix->d_ustart, (n + 1) * 8));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(ix->d_ustart, 0, 8, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    } else {
         DSlot *slp = nullptr;
         for (DSlot &s : c->slots)
             if (s.state == 0 && !slp) slp = &s;
         DSlot &sl = *slp;  // (its member records only; the slot stays free, the call returns synchronised under the lock)
-        const int rr = dslot_reserve(sl, n);
-        if (rr != GZPX_OK) return rr;
+        GZPX_TRY(dslot_reserve(sl, n));
         launch_member_emit(c->ms, (uint32_t)n, ix->d_off, ix->d_size, c->stream);
         launch_member_index((const uint8_t *)d_in, ix->d_off, ix->d_size, (uint32_t)n, sl.d_blk, ix->d_ustart, c->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(sl.h_total, ix->d_ustart + n, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         ix->inflated_len = *sl.h_total;
-        return GZPX_OK;
-    }();
-    if (rc != GZPX_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        gzpx_dindex_destroy(ix);
-        return rc;
     }
-    *out = ix;
+    drain.armed = false;
     if (n_members) *n_members = ix->n;
     if (consumed) *consumed = ix->consumed;
     if (inflated_len) *inflated_len = ix->inflated_len;
+    *out = ix.release();
     return GZPX_OK;
 }
 
@@ -2341,14 +2140,7 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
         HIP_TRY(hipEventRecord(c->ev_dep, after));
         HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
     }
-    // what follows a failure may still be running when the caller gets its buffers back otherwise
-    struct Drain {
-        hipStream_t s;
-        bool armed = true;
-        ~Drain() {
-            if (armed) (void)hipStreamSynchronize(s);
-        }
-    } drain{stream};
+    Drain drain{stream};
     RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
     memcpy(c->h_ranges, ranges, n_ranges * sizeof(gzpx_range));
     HIP_TRY(hipMemcpyAsync(c->rr.ranges, c->h_ranges, n_ranges * 16, hipMemcpyHostToDevice, stream));
@@ -2380,14 +2172,8 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
         drain.armed = false;
         return GZPX_OK;
     }
-    if (stage_bytes + 64 > c->stage_cap) {
-        if (c->d_stage) (void)hipFree(c->d_stage);
-        c->d_stage = nullptr;
-        c->stage_cap = 0;
-        const size_t cap = (size_t)(stage_bytes + stage_bytes / 8 + 4096);
-        HIP_TRY(hipMalloc((void **)&c->d_stage, cap));
-        c->stage_cap = cap;
-    }
+    GZPX_TRY(grow(c->stage_mem, c->stage_cap, (size_t)(stage_bytes + 64), (size_t)(stage_bytes + stage_bytes / 8 + 4096),
+                  [&](size_t cap) { return c->stage_mem.dev(c->d_stage, cap); }));
     const uint32_t hdr_len = c->format == GZPX_FORMAT_BGZF ? 18 : 20;
     sl.nb = nsel;
     sl.route = c->route;
@@ -2466,13 +2252,7 @@ int gzpx_inflate_batch_device(gzpx_dctx *c, int wrap, unsigned flags, const void
         HIP_TRY(hipEventRecord(c->ev_dep, after));
         HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
     }
-    struct Drain {  // what follows a failure may still be running when the caller gets its buffers back otherwise
-        hipStream_t s;
-        bool armed = true;
-        ~Drain() {
-            if (armed) (void)hipStreamSynchronize(s);
-        }
-    } drain{stream};
+    Drain drain{stream};
     sl.nb = n;
     sl.route = short_ok ? (int)kInflateRouteWave : c->route;
     sl.have_blk = c->debug != 0;
@@ -2699,11 +2479,10 @@ int gzpx_debug_snap(gzpx_ctx *ctx, int enable, uint64_t sums[8]) {
         }
     }
     if (enable && !ss.dbg) {
-        HIP_TRY(hipMalloc((void **)&ss.dbg, chunks * 8 * sizeof(uint64_t)));
+        GZPX_TRY(ctx->snap_dbg.dev(ss.dbg, chunks * 8 * sizeof(uint64_t)));
         HIP_TRY(hipMemset(ss.dbg, 0, chunks * 8 * sizeof(uint64_t)));
-    } else if (!enable && ss.dbg) {
-        (void)hipFree(ss.dbg);
-        ss.dbg = nullptr;
+    } else if (!enable) {
+        ctx->snap_dbg.release();
     }
     return GZPX_OK;
 }

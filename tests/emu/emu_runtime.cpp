@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 
+#include <atomic>
 #include <chrono>
 #include <mutex>
 #include <vector>
@@ -281,21 +282,40 @@ static double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-hipError_t hipMalloc(void **p, size_t n) {
-    *p = malloc(n ? n : 1);
-    if (*p) memset(*p, 0xA5, n);  // "device memory" starts as garbage
-    return *p ? hipSuccess : hipErrorOutOfMemory;
+// Ownership hooks for the leak / allocation-failure tests: what is live right now (allocations of both kinds,
+// events, streams -- the stream handles are null, so their calls are counted), and a failure injected into the
+// n-th allocation of either kind from now (0 = off).  A failed allocation leaves *p alone, as the runtime does.
+static std::atomic<long> live_allocs{0}, live_events{0}, live_streams{0};  // (gzpx_par allocates from its workers)
+static long inject_alloc = 0;
+extern "C" long emu_live_allocs() { return live_allocs; }
+extern "C" long emu_live_events() { return live_events; }
+extern "C" long emu_live_streams() { return live_streams; }
+extern "C" long emu_fail_nth_alloc(long nth) {  // (returns what was left of the previous arming: armed minus that = allocations seen)
+    const long left = inject_alloc;
+    inject_alloc = nth;
+    return left;
 }
-hipError_t hipFree(void *p) {
-    free(p);
+static hipError_t emu_alloc(void **p, size_t n, int fill) {
+    if (inject_alloc > 0 && --inject_alloc == 0) return hipErrorOutOfMemory;
+    void *q = malloc(n ? n : 1);
+    if (!q) return hipErrorOutOfMemory;
+    if (fill >= 0) memset(q, fill, n);
+    *p = q;
+    live_allocs++;
     return hipSuccess;
 }
-hipError_t hipHostMalloc(void **p, size_t n, unsigned) {
-    *p = malloc(n ? n : 1);
-    return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-hipError_t hipHostFree(void *p) {
+static void emu_free(void *p) {
+    if (p) live_allocs--;
     free(p);
+}
+hipError_t hipMalloc(void **p, size_t n) { return emu_alloc(p, n, 0xA5); }  // "device memory" starts as garbage
+hipError_t hipFree(void *p) {
+    emu_free(p);
+    return hipSuccess;
+}
+hipError_t hipHostMalloc(void **p, size_t n, unsigned) { return emu_alloc(p, n, -1); }
+hipError_t hipHostFree(void *p) {
+    emu_free(p);
     return hipSuccess;
 }
 hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) {
@@ -323,13 +343,14 @@ hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) {
 }
 hipError_t hipStreamCreate(hipStream_t *s) {
     *s = nullptr;
+    live_streams++;
     return hipSuccess;
 }
-hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
-    *s = nullptr;
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return hipStreamCreate(s); }
+hipError_t hipStreamDestroy(hipStream_t) {
+    live_streams--;
     return hipSuccess;
 }
-hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) {
     stream_syncs++;
     return hipSuccess;
@@ -338,10 +359,12 @@ hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuc
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t *e) {
     *e = new emu_event{0.0};
+    live_events++;
     return hipSuccess;
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) {
+    if (e) live_events--;
     delete e;
     return hipSuccess;
 }

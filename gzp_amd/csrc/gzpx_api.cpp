@@ -71,6 +71,68 @@ constexpr int kProfPairs = 64;  // launch groups of one batch that measurement m
 
 constexpr int kSlots = 3;  // slabs of one context that may be in flight (copy in / kernels / copy out)
 
+// ---- what gzpx_ctx and gzpx_dctx do alike.  Both keep `slots[kSlots]` (state: 0 free, 1 submitted, 2 a thread is
+// inside wait(); gen: which job), `next_gen`, and `mu` + `cv_slot` for them.
+
+// The first free slot, with the context's mutex held through `lk`.  None: waits for one (the wait lets go of the
+// mutex), or returns -1 at once.
+template <class Ctx>
+int free_slot(Ctx *c, std::unique_lock<std::mutex> &lk, bool wait) {
+    for (;;) {
+        for (int i = 0; i < kSlots; i++)
+            if (c->slots[i].state == 0) return i;
+        if (!wait) return -1;
+        c->cv_slot.wait(lk);
+    }
+}
+
+// slot si holds a submitted job from here on: its ticket (mutex held)
+template <class Ctx>
+uint64_t issue_ticket(Ctx *c, int si) {
+    c->slots[si].state = 1;
+    c->slots[si].gen = c->next_gen++;
+    return (c->slots[si].gen << 8) | (uint64_t)si;
+}
+
+// the slot of a ticket whose job is submitted and not being waited for, else -1 (mutex held)
+template <class Ctx>
+int ticket_slot(Ctx *c, uint64_t ticket) {
+    const int si = (int)(ticket & 0xFF);
+    return si < kSlots && c->slots[si].state == 1 && c->slots[si].gen == (ticket >> 8) ? si : -1;
+}
+
+// ... which the calling thread now waits for
+template <class Ctx>
+int claim_ticket(Ctx *c, uint64_t ticket) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int si = ticket_slot(c, ticket);
+    if (si >= 0) c->slots[si].state = 2;
+    return si;
+}
+
+// A device job's buffers are ready once the caller's stream `after` has reached this point: `stream`, one of a
+// context's own, waits for it.  NULL is the legacy default stream (PyTorch's current stream unless told otherwise) --
+// the contexts' streams are non-blocking, so nothing orders them behind it implicitly.  Nothing to do for the stream
+// itself and for GZPX_STREAM_NONE.
+int order_behind(hipStream_t stream, hipStream_t after, hipEvent_t ev_dep) {
+    if (after == stream || after == (hipStream_t)GZPX_STREAM_NONE) return GZPX_OK;
+    HIP_TRY(hipEventRecord(ev_dep, after));
+    HIP_TRY(hipStreamWaitEvent(stream, ev_dep, 0));
+    return GZPX_OK;
+}
+
+// A call that fails may already have put copies and kernels on its streams: nothing of them may still be running
+// when the caller gets its buffers back, the next call reuses a slot's staging, or an owner frees what they work on.
+// Armed behind the points that return without having enqueued anything (BUSY, INVALID_ARG); disarmed on success.
+struct Drain {
+    hipStream_t s[4];
+    int n;
+    bool armed = true;
+    ~Drain() {
+        for (int i = 0; armed && i < n; i++) (void)hipStreamSynchronize(s[i]);
+    }
+};
+
 // One slab in flight.  Host-buffer jobs own a pair of device staging buffers per slot, so the H2D
 // copy of slab k+1 and the D2H copy of slab k-1 run (on their own streams) while the kernels of
 // slab k occupy the compute stream.
@@ -148,8 +210,7 @@ size_t snap_bound_per_block(size_t bs) { return 10 + bs + 8 * (size_t)snap_chunk
 
 size_t framed_bound_per_block(const gzpx_ctx *ctx) {
     if (ctx->cfg.format == GZPX_FORMAT_SNAP) return snap_bound_per_block(ctx->cfg.buffer_size);
-    const size_t hdr = ctx->cfg.format == GZPX_FORMAT_BGZF ? 18 : 20;
-    return hdr + ctx->cfg.buffer_size + extra_amount(ctx->cfg.buffer_size) + 8;
+    return header_bytes(ctx->cfg.format) + ctx->cfg.buffer_size + extra_amount(ctx->cfg.buffer_size) + 8;
 }
 
 uint64_t blocks_of(const gzpx_ctx *ctx, size_t in_len) {
@@ -487,40 +548,12 @@ int check_slab_args(const gzpx_ctx *ctx, const void *in, size_t in_len, int mode
 // through the slot's staging buffers; otherwise d_in / d_out are the caller's device buffers.
 int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, size_t in_len, int mode,
                    uint8_t *host_out, uint8_t *d_out, size_t out_cap, hipStream_t after, bool block_for_slot,
-                   std::unique_lock<std::mutex> &lk, uint64_t *ticket);
-
-// A submit that fails may already have put copies and kernels on the streams (the slot stays free):
-// nothing of them may still be running when the caller gets its buffers back or the next submit reuses
-// the slot's staging.
-int submit_locked(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, size_t in_len, int mode,
-                  uint8_t *host_out, uint8_t *d_out, size_t out_cap, hipStream_t after, bool block_for_slot,
-                  std::unique_lock<std::mutex> &lk, uint64_t *ticket) {
-    const int rc = submit_enqueue(ctx, host_in, d_in, in_len, mode, host_out, d_out, out_cap, after, block_for_slot,
-                                  lk, ticket);
-    if (rc != GZPX_OK && rc != GZPX_ERR_BUSY && rc != GZPX_ERR_INVALID_ARG) {
-        (void)hipStreamSynchronize(ctx->s_h2d);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->s_side);
-    }
-    return rc;
-}
-
-int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, size_t in_len, int mode,
-                   uint8_t *host_out, uint8_t *d_out, size_t out_cap, hipStream_t after, bool block_for_slot,
                    std::unique_lock<std::mutex> &lk, uint64_t *ticket) {
     if (ctx->crc_only) return GZPX_ERR_INVALID_ARG;
     const size_t caller_cap = out_cap;  // (host jobs: out_cap becomes the staging buffer's below)
-    int si = -1;
-    for (;;) {
-        for (int i = 0; i < kSlots; i++)
-            if (ctx->slots[i].state == 0) {
-                si = i;
-                break;
-            }
-        if (si >= 0) break;
-        if (!block_for_slot) return GZPX_ERR_BUSY;
-        ctx->cv_slot.wait(lk);
-    }
+    const int si = free_slot(ctx, lk, block_for_slot);
+    if (si < 0) return GZPX_ERR_BUSY;
+    Drain drain{{ctx->s_h2d, ctx->stream, ctx->s_side}, 3};  // (a failure leaves the slot free)
     Slot &sl = ctx->slots[si];
     if (!sl.ev_kernels) {
         GZPX_TRY(sl.ev_h2d.create());
@@ -546,11 +579,8 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
         d_in = sl.d_in;
         d_out = sl.d_out;
         out_cap = sl.d_out_cap;
-    } else if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {  // the slab is ready once `after` has reached this point; NULL is the
-        // legacy default stream (PyTorch's current stream unless told otherwise) -- the context's
-        // streams are non-blocking, so nothing orders them behind it implicitly
-        HIP_TRY(hipEventRecord(ctx->ev_dep, after));
-        HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_dep, 0));
+    } else {
+        GZPX_TRY(order_behind(stream, after, ctx->ev_dep));
     }
     memset(ctx->stage_ms, 0, sizeof(ctx->stage_ms));
     // profiling mode 2 on a one-batch slab: the job carries its own pair of events around the dominant stage and
@@ -571,10 +601,7 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
         else
             rc = enqueue_batch(ctx, d_in + in_begin, in_batch, nb, last_batch, d_out, out_cap, stream,
                                bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi, dom_b, dom_e);
-        if (rc != GZPX_OK) {
-            (void)hipStreamSynchronize(stream);
-            return rc;
-        }
+        if (rc != GZPX_OK) return rc;
         // the per-block sizes of this batch, before the next batch reuses the scratch
         HIP_TRY(hipMemcpyAsync(sl.h_sizes + b0, ctx->scratch.sizes, nb * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                stream));
@@ -588,9 +615,8 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
     sl.host_out_cap = host_out ? caller_cap : 0;
     sl.total_nb = total_nb;
     sl.n_batches = (uint32_t)n_batches;
-    sl.state = 1;
-    sl.gen = ctx->next_gen++;
-    *ticket = (sl.gen << 8) | (uint64_t)si;
+    *ticket = issue_ticket(ctx, si);
+    drain.armed = false;
     return GZPX_OK;
 }
 
@@ -601,17 +627,6 @@ struct Completion {
     int rc = GZPX_OK;
     size_t produced = 0, blocks_done = 0;
 };
-
-int claim_ticket(gzpx_ctx *ctx, uint64_t ticket, Slot **slot) {
-    const int si = (int)(ticket & 0xFF);
-    if (si >= kSlots) return GZPX_ERR_INVALID_ARG;
-    Slot &sl = ctx->slots[si];
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (sl.state != 1 || sl.gen != (ticket >> 8)) return GZPX_ERR_INVALID_ARG;
-    sl.state = 2;
-    *slot = &sl;
-    return GZPX_OK;
-}
 
 Completion kernels_done(gzpx_ctx *ctx, Slot &sl) {
     Completion c;
@@ -668,13 +683,12 @@ void release_slot(gzpx_ctx *ctx, Slot &sl) {
 // Complete a ticket: wait for its kernels, copy the stream out (host jobs), report.
 int wait_ticket(gzpx_ctx *ctx, uint64_t ticket, size_t *out_len, uint32_t *block_sizes, size_t max_blocks,
                 size_t *n_blocks) {
-    Slot *slp = nullptr;
-    int rc = claim_ticket(ctx, ticket, &slp);
-    if (rc != GZPX_OK) return rc;
-    Slot &sl = *slp;
+    const int si = claim_ticket(ctx, ticket);
+    if (si < 0) return GZPX_ERR_INVALID_ARG;
+    Slot &sl = ctx->slots[si];
     const size_t host_out_cap = sl.host_out_cap;  // (the slot is ours from the claim on: no other thread writes it)
     Completion c = kernels_done(ctx, sl);
-    rc = c.rc;
+    int rc = c.rc;
     if (rc == GZPX_OK && sl.host_out && c.produced > host_out_cap) rc = GZPX_ERR_INSUFFICIENT_SPACE;
     if (rc == GZPX_OK && block_sizes) {
         if (max_blocks < sl.total_nb) rc = GZPX_ERR_INVALID_ARG;
@@ -827,7 +841,7 @@ int gzpx_compress_slab_submit(gzpx_ctx *ctx, const uint8_t *in, size_t in_len, i
     if (rc != GZPX_OK) return rc;
     std::unique_lock<std::mutex> lk(ctx->mu);
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-    return submit_locked(ctx, in, nullptr, in_len, mode, out, nullptr, out_cap, nullptr, false, lk, ticket);
+    return submit_enqueue(ctx, in, nullptr, in_len, mode, out, nullptr, out_cap, nullptr, false, lk, ticket);
 }
 
 int gzpx_compress_slab_submit_device(gzpx_ctx *ctx, const void *d_in, size_t in_len, int mode, void *d_out,
@@ -837,26 +851,22 @@ int gzpx_compress_slab_submit_device(gzpx_ctx *ctx, const void *d_in, size_t in_
     if (rc != GZPX_OK) return rc;
     std::unique_lock<std::mutex> lk(ctx->mu);
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-    return submit_locked(ctx, nullptr, (const uint8_t *)d_in, in_len, mode, nullptr, (uint8_t *)d_out, out_cap,
-                         (hipStream_t)after_stream, false, lk, ticket);
+    return submit_enqueue(ctx, nullptr, (const uint8_t *)d_in, in_len, mode, nullptr, (uint8_t *)d_out, out_cap,
+                          (hipStream_t)after_stream, false, lk, ticket);
 }
 
 int gzpx_compress_slab_wait(gzpx_ctx *ctx, uint64_t ticket, size_t *out_len, uint32_t *block_sizes,
                             size_t max_blocks, size_t *n_blocks) {
     if (!ctx) return GZPX_ERR_INVALID_ARG;
-    const int si = (int)(ticket & 0xFF);
-    if (si >= kSlots) return GZPX_ERR_INVALID_ARG;
     return wait_ticket(ctx, ticket, out_len, block_sizes, max_blocks, n_blocks);
 }
 
 int gzpx_compress_slab_event(gzpx_ctx *ctx, uint64_t ticket, void **hip_event) {
     if (!ctx || !hip_event) return GZPX_ERR_INVALID_ARG;
-    const int si = (int)(ticket & 0xFF);
-    if (si >= kSlots) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    Slot &sl = ctx->slots[si];
-    if (sl.state != 1 || sl.gen != (ticket >> 8)) return GZPX_ERR_INVALID_ARG;
-    *hip_event = (void *)sl.ev_kernels;
+    const int si = ticket_slot(ctx, ticket);
+    if (si < 0) return GZPX_ERR_INVALID_ARG;
+    *hip_event = (void *)ctx->slots[si].ev_kernels;
     return GZPX_OK;
 }
 
@@ -871,8 +881,8 @@ int gzpx_compress_slab_device(gzpx_ctx *ctx, const void *d_in, size_t in_len, in
     {
         std::unique_lock<std::mutex> lk(ctx->mu);
         if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-        rc = submit_locked(ctx, nullptr, (const uint8_t *)d_in, in_len, mode, nullptr, (uint8_t *)d_out, out_cap,
-                           (hipStream_t)hip_stream, true, lk, &ticket);
+        rc = submit_enqueue(ctx, nullptr, (const uint8_t *)d_in, in_len, mode, nullptr, (uint8_t *)d_out, out_cap,
+                            (hipStream_t)hip_stream, true, lk, &ticket);
     }
     if (rc != GZPX_OK) return rc;
     return wait_ticket(ctx, ticket, out_len, block_sizes, max_blocks, n_blocks);
@@ -889,7 +899,7 @@ int gzpx_compress_slab(gzpx_ctx *ctx, const uint8_t *in, size_t in_len, int mode
     {
         std::unique_lock<std::mutex> lk(ctx->mu);
         if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-        rc = submit_locked(ctx, in, nullptr, in_len, mode, out, nullptr, out_cap, nullptr, true, lk, &ticket);
+        rc = submit_enqueue(ctx, in, nullptr, in_len, mode, out, nullptr, out_cap, nullptr, true, lk, &ticket);
     }
     if (rc != GZPX_OK) return rc;
     return wait_ticket(ctx, ticket, out_len, block_sizes, max_blocks, n_blocks);
@@ -1053,8 +1063,8 @@ int gzpx_multi_compress_slab_device(gzpx_multi *m, const void *const *d_in, size
         gzpx_multi::Stage &st = m->stage[g];
         rc = grow(st.mem, st.cap, need, need + need / 8 + 4096, [&](size_t cap) { return st.mem.dev(st.d, cap); });
         if (rc != GZPX_OK) break;
-        rc = submit_locked(ctx, nullptr, (const uint8_t *)d_in[g], p.r.n, owns_end ? mode : GZPX_SLAB_FULL_BLOCKS, nullptr,
-                           st.d, st.cap, (hipStream_t)GZPX_STREAM_NONE, true, lk, &p.ticket);  // (the caller's contract: the ranges are ready)
+        rc = submit_enqueue(ctx, nullptr, (const uint8_t *)d_in[g], p.r.n, owns_end ? mode : GZPX_SLAB_FULL_BLOCKS, nullptr,
+                            st.d, st.cap, (hipStream_t)GZPX_STREAM_NONE, true, lk, &p.ticket);  // (the caller's contract: the ranges are ready)
         p.submitted = rc == GZPX_OK;
     }
     // 2. shard sizes -> stream offsets
@@ -1062,11 +1072,13 @@ int gzpx_multi_compress_slab_device(gzpx_multi *m, const void *const *d_in, size
     for (size_t g = 0; g < G; g++) {
         Part &p = parts[g];
         if (!p.submitted) continue;
-        if (claim_ticket(m->ctxs[g], p.ticket, &p.slot) != GZPX_OK) {
+        const int si = claim_ticket(m->ctxs[g], p.ticket);
+        if (si < 0) {
             if (rc == GZPX_OK) rc = GZPX_ERR_DEVICE;
             p.submitted = false;
             continue;
         }
+        p.slot = &m->ctxs[g]->slots[si];
         p.c = kernels_done(m->ctxs[g], *p.slot);
         if (p.c.rc != GZPX_OK && rc == GZPX_OK) {  // the first failing block in stream order
             rc = p.c.rc;
@@ -1149,8 +1161,8 @@ int gzpx_multi_compress_slab(gzpx_multi *m, const uint8_t *in, size_t in_len, in
             break;
         }
         // (`out` is only a placeholder here: the real destination is known after the sizes are)
-        rc = submit_locked(ctx, in + p.lo, nullptr, p.n, owns_end ? mode : GZPX_SLAB_FULL_BLOCKS, out, nullptr, 0, nullptr,
-                           true, lk, &p.ticket);
+        rc = submit_enqueue(ctx, in + p.lo, nullptr, p.n, owns_end ? mode : GZPX_SLAB_FULL_BLOCKS, out, nullptr, 0, nullptr,
+                            true, lk, &p.ticket);
         p.submitted = rc == GZPX_OK;
     }
     // 2. sizes -> offsets; 3. all copies started; 4. all copies finished
@@ -1158,11 +1170,13 @@ int gzpx_multi_compress_slab(gzpx_multi *m, const uint8_t *in, size_t in_len, in
     for (size_t g = 0; g < G; g++) {
         Part &p = parts[g];
         if (!p.submitted) continue;
-        if (claim_ticket(m->ctxs[g], p.ticket, &p.slot) != GZPX_OK) {
+        const int si = claim_ticket(m->ctxs[g], p.ticket);
+        if (si < 0) {
             if (rc == GZPX_OK) rc = GZPX_ERR_DEVICE;
             p.submitted = false;
             continue;
         }
+        p.slot = &m->ctxs[g]->slots[si];
         p.c = kernels_done(m->ctxs[g], *p.slot);
         if (p.c.rc != GZPX_OK && rc == GZPX_OK) {  // the first failing block in stream order
             rc = p.c.rc;
@@ -1412,7 +1426,7 @@ struct DSlot : NoCopy {
     bool have_check = false;  // ev_t1 .. ev_tc hold the slot's last launch
     InflateScratch sc;  // match records / tile table of k_inflate_seg + k_lzcopy; sc.redo lives with the block tables
     uint64_t *h_total = nullptr;    // pinned
-    uint32_t *h_summary = nullptr;  // pinned: k_dsummary's record (the first failing member, its checksums)
+    uint32_t *h_summary = nullptr;  // pinned: the host's words of the launch record (kDs*, kWrRec*)
     Allocs once;  // h_total, h_summary, sc.summary: 64 bytes each, made with the events
     size_t cap_blocks = 0;
     uint64_t *d_offsets = nullptr, *d_out_off = nullptr;
@@ -1440,9 +1454,9 @@ int dslot_reserve(DSlot &c, size_t nb) {
         GZPX_TRY(c.ev_done.create());
         for (Event *e : {&c.ev_t0, &c.ev_t1, &c.ev_tm, &c.ev_tc}) GZPX_TRY(e->create(true));
         GZPX_TRY(c.once.pinned(c.h_total, 64));
-        GZPX_TRY(c.once.pinned(c.h_summary, 64));
-        GZPX_TRY(c.once.dev(c.sc.summary, 64));
-        HIP_TRY(hipMemset(c.sc.summary, 0, 64));  // (word 15: k_inflate_seg's first-block hint, kept from launch to launch)
+        GZPX_TRY(c.once.pinned(c.h_summary, kDsWords * 4));
+        GZPX_TRY(c.once.dev(c.sc.summary, kDsWords * 4));
+        HIP_TRY(hipMemset(c.sc.summary, 0, kDsWords * 4));  // (kDsSegHint is kept from launch to launch)
     }
     Allocs &t = c.tables;
     return grow(t, c.cap_blocks, nb, nb + nb / 4 + 64, [&](size_t cap) -> int {
@@ -1515,12 +1529,8 @@ struct ScanResult {
     size_t n_members = 0;  // whole members in front of the walk's end
     size_t consumed = 0;   // where it ended
     bool invalid = false;  // ... at a header that fails the checks (a cap below n_members stops the walk before it sees that)
+    int slot = -1;         // the free slot dscan_run waited for in front of the walk, for the caller that goes on to use one
 };
-
-int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, size_t in_len,
-                    const uint64_t *offsets, const uint32_t *sizes, size_t nb, uint8_t *host_out, uint8_t *d_out,
-                    size_t out_cap, hipStream_t after, bool block_for_slot, std::unique_lock<std::mutex> &lk,
-                    uint64_t *ticket, const ScanResult *scan = nullptr);
 
 // k_inflate_seg + k_lzcopy's match records and tile table for nb members that inflate to at most out_cap bytes
 int dslot_seg_scratch(DSlot &sl, size_t out_cap, size_t nb) {
@@ -1531,49 +1541,39 @@ int dslot_seg_scratch(DSlot &sl, size_t out_cap, size_t nb) {
                 [&](size_t cap) { return sl.tfirst_mem.dev(sl.sc.tfirst, cap); });
 }
 
-// As on the compress side (submit_locked): a submit that fails may already have put copies and kernels on the
-// streams -- the copy-in still reads the caller's `in`, the copy-out may still write the caller's `out` -- and
-// the slot stays free; nothing of them may still be running when the caller gets its buffers back.
-int dsubmit_locked(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, size_t in_len,
-                   const uint64_t *offsets, const uint32_t *sizes, size_t nb, uint8_t *host_out, uint8_t *d_out,
-                   size_t out_cap, hipStream_t after, bool block_for_slot, std::unique_lock<std::mutex> &lk,
-                   uint64_t *ticket, const ScanResult *scan = nullptr) {
-    const int rc = dsubmit_enqueue(c, host_in, d_in, in_len, offsets, sizes, nb, host_out, d_out, out_cap, after,
-                                   block_for_slot, lk, ticket, scan);
-    if (rc != GZPX_OK && rc != GZPX_ERR_BUSY && rc != GZPX_ERR_INVALID_ARG) {
-        (void)hipStreamSynchronize(c->s_h2d);
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipStreamSynchronize(c->s_d2h);
-    }
-    return rc;
+// A slot made ready for an inflate launch of nb members on `route`: what the launch reads from it, what the getters
+// read after it, and on the decode / copy route that pair's scratch for `cap` bytes of output.  `in_bytes`: the
+// compressed bytes that stand for the members' total (InflateScratch).  The slot then holds no member records and no
+// check time: the caller that brings the records back, or runs a check kernel, says so itself.
+int dslot_prepare(gzpx_dctx *c, DSlot &sl, size_t nb, int route, size_t cap, uint64_t in_bytes) {
+    sl.nb = nb;
+    sl.route = route;
+    sl.have_blk = sl.have_check = false;
+    sl.sc.n_cu = c->n_cu;
+    sl.sc.in_bytes = in_bytes;
+    return route == kInflateRouteSeg ? dslot_seg_scratch(sl, cap, nb) : GZPX_OK;
 }
 
+// Enqueue the inflate of one slab (c->mu held): copies in, kernels, copies out, as the compress side's submit_enqueue.
+// `scan`: the members are the first nb of the walk dscan_run has just made over d_in, in the slot it waited for (the
+// table is still in the context's scratch); what the loop below checks of a caller's table, the walk guarantees of
+// its own.
 int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, size_t in_len,
                     const uint64_t *offsets, const uint32_t *sizes, size_t nb, uint8_t *host_out, uint8_t *d_out,
                     size_t out_cap, hipStream_t after, bool block_for_slot, std::unique_lock<std::mutex> &lk,
-                    uint64_t *ticket, const ScanResult *scan) {
-    // `scan`: the members are the first nb of the walk dscan_run has just made over d_in (the table is still in the
-    // context's scratch); what the loop below checks of a caller's table, the walk guarantees of its own
+                    uint64_t *ticket, const ScanResult *scan = nullptr) {
     if (nb && ((!scan && (!offsets || !sizes)) || (!host_in && !d_in) || (scan && !d_in))) return GZPX_ERR_INVALID_ARG;
     if (nb > 0xFFFFFFFFull) return GZPX_ERR_INVALID_ARG;
-    const uint32_t hdr_len = c->format == GZPX_FORMAT_BGZF ? 18 : 20;
+    const uint32_t hdr_len = header_bytes(c->format);
     for (size_t b = 0; b < nb && !scan; b++)
         if (sizes[b] < hdr_len + 8 || offsets[b] > in_len || sizes[b] > in_len - offsets[b]) return GZPX_ERR_INVALID_ARG;
-    int si = -1;
-    for (;;) {
-        for (int i = 0; i < kSlots; i++)
-            if (c->slots[i].state == 0) {
-                si = i;
-                break;
-            }
-        if (si >= 0) break;
-        if (!block_for_slot) return GZPX_ERR_BUSY;
-        c->cv_slot.wait(lk);
-    }
+    const int si = scan ? scan->slot : free_slot(c, lk, block_for_slot);
+    if (si < 0) return GZPX_ERR_BUSY;
+    // (the copy-in still reads the caller's `in`, the copy-out may still write the caller's `out`; the slot stays free)
+    Drain drain{{c->s_h2d, c->stream, c->s_d2h}, 3};
     DSlot &sl = c->slots[si];
-    int rc = dslot_reserve(sl, nb ? nb : 1);
-    if (rc != GZPX_OK) return rc;
-    sl.nb = nb;
+    GZPX_TRY(dslot_reserve(sl, nb ? nb : 1));
+    sl.nb = nb;  // (no members: a ticket all the same, with nothing behind it)
     hipStream_t stream = c->stream;
     if (nb) {
         if (host_in) {  // staging
@@ -1584,12 +1584,13 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
             HIP_TRY(hipMemcpyAsync(sl.d_in, host_in, in_len, hipMemcpyHostToDevice, c->s_h2d));
             d_in = sl.d_in;
             d_out = sl.d_out;
-        } else if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {  // (NULL = the legacy default stream, as on the compress side)
-            HIP_TRY(hipEventRecord(c->ev_dep, after));
-            HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
+        } else {
+            GZPX_TRY(order_behind(stream, after, c->ev_dep));
         }
+        uint64_t csum = 0;  // the members' compressed bytes
         if (scan) {  // the table goes from the scan's scratch to the slot's on the device
             launch_member_emit(c->ms, (uint32_t)nb, sl.d_offsets, sl.d_sizes, stream);
+            csum = scan->consumed;  // (the members of a walk lie back to back from offset 0)
         } else {
             memcpy(sl.h_offsets, offsets, nb * 8);
             memcpy(sl.h_sizes, sizes, nb * 4);
@@ -1597,27 +1598,20 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
             HIP_TRY(hipMemcpyAsync(sl.d_sizes, sl.h_sizes, nb * 4, hipMemcpyHostToDevice, c->s_h2d));
             HIP_TRY(hipEventRecord(sl.ev_h2d, c->s_h2d));
             HIP_TRY(hipStreamWaitEvent(stream, sl.ev_h2d, 0));
+            for (size_t b = 0; b < nb; b++) csum += sizes[b];
         }
-        sl.sc.n_cu = c->n_cu;
-        {
-            uint64_t csum = scan ? scan->consumed : 0;  // (the members of a walk lie back to back from offset 0)
-            for (size_t b = 0; b < nb && !scan; b++) csum += sizes[b];
-            sl.sc.big_members = nb && csum / nb >= 131072u ? 1 : 0;
-        }
-        sl.route = c->route;
-        if (c->route == kInflateRouteSeg) {  // scratch of the decode / copy pair, sized by what the caller can take
-            rc = dslot_seg_scratch(sl, out_cap, nb);
-            if (rc != GZPX_OK) return rc;
-        }
+        // (the pair's scratch is sized by what the caller can take)
+        GZPX_TRY(dslot_prepare(c, sl, nb, c->route, out_cap, csum));
         launch_inflate(hdr_len, d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nb, sl.d_blk, sl.d_out_off, d_out, out_cap,
-                       sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, c->route, sl.ev_tm);
+                       sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, sl.ev_tm);
         HIP_TRY(hipGetLastError());
         // what the host needs of the members' records is k_dsummary's 48 bytes; the records themselves only for the
         // debug counters
-        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, 48, hipMemcpyDeviceToHost, stream));
-        sl.have_blk = c->debug != 0;
-        sl.have_check = false;
-        if (c->debug) HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, nb * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
+        if (c->debug) {
+            HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, nb * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
+            sl.have_blk = true;
+        }
         HIP_TRY(hipMemcpyAsync(sl.h_total, sl.d_out_off + nb, 8, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipEventRecord(sl.ev_kernels, stream));
         if (host_out) {
@@ -1637,44 +1631,44 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
             HIP_TRY(hipEventRecord(sl.ev_done, stream));
         }
     }
-    sl.state = 1;
-    sl.gen = c->next_gen++;
-    *ticket = (sl.gen << 8) | (uint64_t)si;
+    *ticket = issue_ticket(c, si);
+    drain.armed = false;
     return GZPX_OK;
+}
+
+// The launch record of the framed paths (k_dsummary's, kDs*) as the call's return code; a failure names the first
+// failing member of the launch, by its index in the launch, and the two checksums.  `lenient`: the libdeflate-shaped
+// call's rule, under which fewer bytes than ISIZE are no failure.
+int summary_verdict(const uint32_t *rec, bool lenient, gzpx_check_info *info) {
+    const uint32_t *q = rec + (lenient ? kDsLenient : kDsStrict);
+    if (q[kDsFirst] == 0xFFFFFFFFu) return GZPX_OK;
+    if (info) {
+        info->block = q[kDsFirst];
+        info->found = q[kDsFound];
+        info->expected = q[kDsExpected];
+    }
+    const uint32_t st = q[kDsStatus];
+    return st == kInfBadData ? GZPX_ERR_BAD_DATA
+           : st == kInfInsufficientSpace ? GZPX_ERR_INSUFFICIENT_SPACE
+           : (st != kInfOk && !lenient) ? GZPX_ERR_BAD_DATA  // kInfShortOutput
+                                        : GZPX_ERR_INVALID_CHECK;
 }
 
 // `short_ok`: the libdeflate-shaped call offers its capacity as ISIZE and accepts fewer bytes (libdeflate
 // with actual_out_nbytes_ret); a framed member that inflates to fewer bytes than its footer says is
 // BadData (libdeflate SHORT_OUTPUT through decode_block, src/par/decompress.rs:162-186).
 int dwait_ticket(gzpx_dctx *c, uint64_t ticket, size_t *out_len, gzpx_check_info *info, bool short_ok = false) {
-    const int si = (int)(ticket & 0xFF);
-    if (si >= kSlots) return GZPX_ERR_INVALID_ARG;
+    const int si = claim_ticket(c, ticket);
+    if (si < 0) return GZPX_ERR_INVALID_ARG;
     DSlot &sl = c->slots[si];
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (sl.state != 1 || sl.gen != (ticket >> 8)) return GZPX_ERR_INVALID_ARG;
-        sl.state = 2;
-    }
     int rc = GZPX_OK;
     size_t produced = 0;
     if (sl.nb) {
         if (hipSetDevice(c->device) != hipSuccess || hipEventSynchronize(sl.ev_done) != hipSuccess) {
             rc = GZPX_ERR_DEVICE;
         } else {
-            // the first failing block in stream order (src/par/decompress.rs:162-186), found on the device (k_dsummary)
-            const uint32_t *q = sl.h_summary + (short_ok ? 4 : 0);
-            if (q[0] != 0xFFFFFFFFu) {
-                const uint32_t st = q[1];
-                rc = st == 1 ? GZPX_ERR_BAD_DATA
-                     : st == 2 ? GZPX_ERR_INSUFFICIENT_SPACE
-                     : (st != 0 && !short_ok) ? GZPX_ERR_BAD_DATA  // 3: fewer bytes than ISIZE
-                                              : GZPX_ERR_INVALID_CHECK;
-                if (info) {
-                    info->block = q[0];
-                    info->found = q[2];
-                    info->expected = q[3];
-                }
-            }
+            // the first failing block in stream order (src/par/decompress.rs:162-186), found on the device
+            rc = summary_verdict(sl.h_summary, short_ok, info);
             if (rc == GZPX_OK) produced = (size_t)*sl.h_total;
         }
     }
@@ -1714,17 +1708,17 @@ int dscan_reserve(gzpx_dctx *c, size_t n_seg, size_t cap) {
 
 // gzpx_scan_blocks over d_in[0..in_len) on the device, without the cap: how many members the walk from offset 0
 // records and where it stops.  Returns synchronised; the table stays in c->ms (launch_member_emit) until the next
-// scan of this context.  Called with c->mu held.
-int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t after, ScanResult *r) {
+// scan of this context.  Called with c->mu held.  `slot_lk`: the caller goes on to use a slot and holds c->mu from
+// the scan until it is done with the table: a free slot is waited for first (the wait lets go of the mutex), r->slot.
+int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t after, ScanResult *r,
+              std::unique_lock<std::mutex> *slot_lk = nullptr) {
     *r = ScanResult();
+    if (slot_lk) r->slot = free_slot(c, *slot_lk, true);
     c->have_scan = false;
-    const size_t hdr = c->format == GZPX_FORMAT_BGZF ? 18 : 20;
+    const size_t hdr = header_bytes(c->format);
     if (in_len < hdr) return GZPX_OK;  // read_exact(header) finds nothing to read
     hipStream_t stream = c->stream;
-    if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {
-        HIP_TRY(hipEventRecord(c->ev_dep, after));
-        HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
-    }
+    GZPX_TRY(order_behind(stream, after, c->ev_dep));
     // one wave per segment; 16 KiB each, larger where that keeps the single-workgroup scan of their counts short
     const size_t span = ((uintptr_t)d_in & 15u) + in_len;
     size_t seg_bytes = 16384;
@@ -1765,8 +1759,6 @@ int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t afte
     return GZPX_OK;
 }
 
-// the calls that scan and then use a slot hold c->mu from the scan to the submit (the scan's scratch is the
-// context's): they wait for the slot first
 int rr_reserve(gzpx_dctx *c, size_t n_ranges, size_t n_members) {
     RangeScratch &r = c->rr;
     if (!r.rec) {
@@ -1789,14 +1781,6 @@ int rr_reserve(gzpx_dctx *c, size_t n_ranges, size_t n_members) {
         GZPX_TRY(b.dev(r.map, cap * 4));
         return b.dev(r.soff, cap * 8);
     });
-}
-
-void dwait_free_slot(gzpx_dctx *c, std::unique_lock<std::mutex> &lk) {
-    for (;;) {
-        for (int i = 0; i < kSlots; i++)
-            if (c->slots[i].state == 0) return;
-        c->cv_slot.wait(lk);
-    }
 }
 
 }  // namespace
@@ -1842,7 +1826,7 @@ void gzpx_dctx_destroy(gzpx_dctx *c) {
 int gzpx_scan_blocks(int format, const uint8_t *in, size_t in_len, uint64_t *offsets, uint32_t *sizes,
                      size_t max_blocks, size_t *n_blocks, size_t *consumed) {
     if ((!in && in_len) || !n_blocks || !consumed) return GZPX_ERR_INVALID_ARG;
-    const size_t hdr = format == GZPX_FORMAT_BGZF ? 18 : 20;  // BlockFormatSpec::HEADER_SIZE
+    const size_t hdr = header_bytes(format);
     size_t pos = 0, nb = 0;
     *n_blocks = 0;
     *consumed = 0;
@@ -1875,8 +1859,8 @@ int gzpx_decompress_blocks_submit(gzpx_dctx *c, const uint8_t *in, size_t in_len
     if (!c || (!in && in_len) || (!out && out_cap) || !ticket) return GZPX_ERR_INVALID_ARG;
     std::unique_lock<std::mutex> lk(c->mu);
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    return dsubmit_locked(c, in, nullptr, in_len, offsets, sizes, n_blocks, out, nullptr, out_cap, nullptr, false,
-                          lk, ticket);
+    return dsubmit_enqueue(c, in, nullptr, in_len, offsets, sizes, n_blocks, out, nullptr, out_cap, nullptr, false,
+                           lk, ticket);
 }
 
 int gzpx_decompress_blocks_wait(gzpx_dctx *c, uint64_t ticket, size_t *out_len, gzpx_check_info *info) {
@@ -1895,8 +1879,8 @@ int gzpx_decompress_blocks_device(gzpx_dctx *c, const void *d_in, size_t in_len,
     {
         std::unique_lock<std::mutex> lk(c->mu);
         if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-        rc = dsubmit_locked(c, nullptr, (const uint8_t *)d_in, in_len, offsets, sizes, n_blocks, nullptr,
-                            (uint8_t *)d_out, out_cap, (hipStream_t)hip_stream, true, lk, &ticket);
+        rc = dsubmit_enqueue(c, nullptr, (const uint8_t *)d_in, in_len, offsets, sizes, n_blocks, nullptr,
+                             (uint8_t *)d_out, out_cap, (hipStream_t)hip_stream, true, lk, &ticket);
     }
     if (rc != GZPX_OK) return rc;
     return dwait_ticket(c, ticket, out_len, info);
@@ -1950,16 +1934,15 @@ int gzpx_decompress_stream_device(gzpx_dctx *c, const void *d_in, size_t in_len,
     {
         std::unique_lock<std::mutex> lk(c->mu);
         if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-        dwait_free_slot(c, lk);
         ScanResult r;
-        rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r);
+        rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r, &lk);
         if (rc != GZPX_OK) return rc;
         if (r.invalid) return GZPX_ERR_INVALID_HEADER;
         *n_blocks = r.n_members;
         *consumed = r.consumed;
         if (r.n_members == 0) return GZPX_OK;
-        rc = dsubmit_locked(c, nullptr, (const uint8_t *)d_in, in_len, nullptr, nullptr, r.n_members, nullptr,
-                            (uint8_t *)d_out, out_cap, (hipStream_t)hip_stream, true, lk, &ticket, &r);
+        rc = dsubmit_enqueue(c, nullptr, (const uint8_t *)d_in, in_len, nullptr, nullptr, r.n_members, nullptr,
+                             (uint8_t *)d_out, out_cap, (hipStream_t)hip_stream, true, lk, &ticket, &r);
     }
     if (rc != GZPX_OK) return rc;
     return dwait_ticket(c, ticket, out_len, info);
@@ -1973,19 +1956,15 @@ int gzpx_index_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx_index_
     if (inflated_len) *inflated_len = 0;
     std::unique_lock<std::mutex> lk(c->mu);
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    dwait_free_slot(c, lk);
     ScanResult r;
-    const int rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r);
+    const int rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r, &lk);
     if (rc != GZPX_OK) return rc;
     if (r.invalid) return GZPX_ERR_INVALID_HEADER;
     *n_entries = r.n_members;
     *consumed = r.consumed;
     if (r.n_members == 0) return GZPX_OK;
     if (r.n_members > 0xFFFFFFFFull) return GZPX_ERR_INVALID_ARG;
-    DSlot *slp = nullptr;
-    for (DSlot &s : c->slots)
-        if (s.state == 0 && !slp) slp = &s;
-    DSlot &sl = *slp;  // (its tables only; the slot stays free, the call returns synchronised under the lock)
+    DSlot &sl = c->slots[r.slot];  // (its tables only; the slot stays free, the call returns synchronised under the lock)
     const int rr = dslot_reserve(sl, r.n_members);
     if (rr != GZPX_OK) return rr;
     const uint32_t nb = (uint32_t)r.n_members;
@@ -2025,17 +2004,6 @@ struct gzpx_dindex : NoCopy {
     Allocs mem;
 };
 
-namespace {
-// what follows a failure may still be running when the caller gets its buffers back otherwise
-struct Drain {
-    hipStream_t s;
-    bool armed = true;
-    ~Drain() {
-        if (armed) (void)hipStreamSynchronize(s);
-    }
-};
-}  // namespace
-
 extern "C" {
 
 void gzpx_dindex_destroy(gzpx_dindex *ix) {
@@ -2053,9 +2021,8 @@ int gzpx_dindex_build_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx
     if (inflated_len) *inflated_len = 0;
     std::unique_lock<std::mutex> lk(c->mu);
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    dwait_free_slot(c, lk);
     ScanResult r;
-    int rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r);
+    int rc = dscan_run(c, (const uint8_t *)d_in, in_len, (hipStream_t)hip_stream, &r, &lk);
     if (rc != GZPX_OK) return rc;
     if (r.invalid) return GZPX_ERR_INVALID_HEADER;
     if (r.n_members > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
@@ -2066,7 +2033,7 @@ int gzpx_dindex_build_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx
     ix->n = r.n_members;
     ix->consumed = r.consumed;
     const size_t n = r.n_members;
-    Drain drain{c->stream};  // (a failure: nothing still runs on the arrays when they are freed)
+    Drain drain{{c->stream}, 1};  // (a failure: nothing still runs on the arrays when they are freed)
     GZPX_TRY(ix->mem.dev(ix->d_off, (n ? n : 1) * 8));
     GZPX_TRY(ix->mem.dev(ix->d_size, (n ? n : 1) * 4));
     GZPX_TRY(ix->mem.dev(ix->d_ustart, (n + 1) * 8));
@@ -2074,10 +2041,7 @@ int gzpx_dindex_build_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx
         HIP_TRY(hipMemsetAsync(ix->d_ustart, 0, 8, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     } else {
-        DSlot *slp = nullptr;
-        for (DSlot &s : c->slots)
-            if (s.state == 0 && !slp) slp = &s;
-        DSlot &sl = *slp;  // (its member records only; the slot stays free, the call returns synchronised under the lock)
+        DSlot &sl = c->slots[r.slot];  // (its member records only; the slot stays free, the call returns synchronised under the lock)
         GZPX_TRY(dslot_reserve(sl, n));
         launch_member_emit(c->ms, (uint32_t)n, ix->d_off, ix->d_size, c->stream);
         launch_member_index((const uint8_t *)d_in, ix->d_off, ix->d_size, (uint32_t)n, sl.d_blk, ix->d_ustart, c->stream);
@@ -2127,20 +2091,13 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
         return GZPX_OK;
     }
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    dwait_free_slot(c, lk);
-    int si = 0;
-    while (c->slots[si].state != 0) si++;
+    const int si = free_slot(c, lk, true);
     DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
-    int rc = dslot_reserve(sl, ix->n ? ix->n : 1);
-    if (rc != GZPX_OK) return rc;
-    rc = rr_reserve(c, n_ranges, ix->n);
-    if (rc != GZPX_OK) return rc;
-    hipStream_t stream = c->stream, after = (hipStream_t)hip_stream;
-    if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {
-        HIP_TRY(hipEventRecord(c->ev_dep, after));
-        HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
-    }
-    Drain drain{stream};
+    GZPX_TRY(dslot_reserve(sl, ix->n ? ix->n : 1));
+    GZPX_TRY(rr_reserve(c, n_ranges, ix->n));
+    hipStream_t stream = c->stream;
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    Drain drain{{stream}, 1};
     RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
     memcpy(c->h_ranges, ranges, n_ranges * sizeof(gzpx_range));
     HIP_TRY(hipMemcpyAsync(c->rr.ranges, c->h_ranges, n_ranges * 16, hipMemcpyHostToDevice, stream));
@@ -2174,22 +2131,15 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
     }
     GZPX_TRY(grow(c->stage_mem, c->stage_cap, (size_t)(stage_bytes + 64), (size_t)(stage_bytes + stage_bytes / 8 + 4096),
                   [&](size_t cap) { return c->stage_mem.dev(c->d_stage, cap); }));
-    const uint32_t hdr_len = c->format == GZPX_FORMAT_BGZF ? 18 : 20;
-    sl.nb = nsel;
-    sl.route = c->route;
-    sl.have_blk = false;
-    sl.have_check = false;
-    sl.sc.n_cu = c->n_cu;
-    sl.sc.big_members = ix->consumed / ix->n >= 131072u ? 1 : 0;  // (the stream's average stands for the selection's)
-    if (c->route == kInflateRouteSeg) {
-        rc = dslot_seg_scratch(sl, (size_t)stage_bytes, nsel);
-        if (rc != GZPX_OK) return rc;
-    }
+    // (the pair's scratch is sized by the staging; the stream's average member stands for the selection's.  The
+    // members' records stay on the device, under gzpx_debug_inflate too.)
+    GZPX_TRY(dslot_prepare(c, sl, nsel, c->route, (size_t)stage_bytes, (uint64_t)(ix->consumed / ix->n) * nsel));
     HIP_TRY(hipEventRecord(c->ev_r[2], stream));
-    launch_inflate(hdr_len, (const uint8_t *)d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nsel, sl.d_blk, sl.d_out_off,
-                   c->d_stage, stage_bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, c->route, sl.ev_tm);
+    launch_inflate(header_bytes(c->format), (const uint8_t *)d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nsel, sl.d_blk,
+                   sl.d_out_off, c->d_stage, stage_bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route,
+                   sl.ev_tm);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, 48, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipEventRecord(c->ev_r[3], stream));
     // (enqueued behind the inflate without asking how it went: after a failed check d_out holds nothing of use)
     launch_ranges_gather(c->d_stage, (uint32_t)n_ranges, c->rr, (uint8_t *)d_out, total, stream);
@@ -2200,17 +2150,14 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
     c->rr_stages = true;
     c->last_slot = si;
     c->last_nb = nsel;
-    const uint32_t *q = sl.h_summary;  // the first failing member of the selection, in stream order (k_dsummary)
-    if (q[0] != 0xFFFFFFFFu) {
-        const uint32_t st = q[1];
+    gzpx_check_info failed = {0, 0, 0};  // the first failing member of the selection, in stream order
+    const int verdict = summary_verdict(sl.h_summary, false, &failed);
+    if (verdict != GZPX_OK) {
         uint32_t member = 0;  // its index in the stream, through the rank map
-        HIP_TRY(hipMemcpy(&member, c->rr.map + q[0], 4, hipMemcpyDeviceToHost));
-        if (info) {
-            info->block = member;
-            info->found = q[2];
-            info->expected = q[3];
-        }
-        return st == 1 ? GZPX_ERR_BAD_DATA : st == 2 ? GZPX_ERR_INSUFFICIENT_SPACE : st != 0 ? GZPX_ERR_BAD_DATA : GZPX_ERR_INVALID_CHECK;
+        HIP_TRY(hipMemcpy(&member, c->rr.map + failed.block, 4, hipMemcpyDeviceToHost));
+        failed.block = member;
+        if (info) *info = failed;
+        return verdict;
     }
     *out_len = (size_t)total;
     return GZPX_OK;
@@ -2234,7 +2181,7 @@ int gzpx_inflate_batch_device(gzpx_dctx *c, int wrap, unsigned flags, const void
     if (n > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
     std::unique_lock<std::mutex> lk(c->mu);
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    hipStream_t stream = c->stream, after = (hipStream_t)hip_stream;
+    hipStream_t stream = c->stream;
     if (n == 0) {
         if (d_out_offsets) {
             HIP_TRY(hipMemsetAsync(d_out_offsets, 0, 8, stream));
@@ -2242,49 +2189,39 @@ int gzpx_inflate_batch_device(gzpx_dctx *c, int wrap, unsigned flags, const void
         }
         return GZPX_OK;
     }
-    dwait_free_slot(c, lk);
-    int si = 0;
-    while (c->slots[si].state != 0) si++;
+    const int si = free_slot(c, lk, true);
     DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
-    int rc = dslot_reserve(sl, n);
-    if (rc != GZPX_OK) return rc;
-    if (after != stream && after != (hipStream_t)GZPX_STREAM_NONE) {
-        HIP_TRY(hipEventRecord(c->ev_dep, after));
-        HIP_TRY(hipStreamWaitEvent(stream, c->ev_dep, 0));
-    }
-    Drain drain{stream};
-    sl.nb = n;
-    sl.route = short_ok ? (int)kInflateRouteWave : c->route;
-    sl.have_blk = c->debug != 0;
-    sl.sc.n_cu = c->n_cu;
-    sl.sc.big_members = in_len / n >= 131072u ? 1 : 0;  // (the sizes are on the device: the input's average stands for them)
-    if (sl.route == kInflateRouteSeg) {
-        rc = dslot_seg_scratch(sl, out_cap, n);
-        if (rc != GZPX_OK) return rc;
-    }
+    GZPX_TRY(dslot_reserve(sl, n));
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    Drain drain{{stream}, 1};
+    // (fewer bytes than the slot are k_inflate's to see; the sizes are on the device: the input stands for their sum)
+    GZPX_TRY(dslot_prepare(c, sl, n, short_ok ? (int)kInflateRouteWave : c->route, out_cap, in_len));
     // the slot's own size table is free here (the caller's is read where it lies): it holds the members' slots
     launch_inflate_batch(wrap, short_ok ? 1 : 0, (const uint8_t *)d_in, in_len, d_in_offsets, d_in_sizes, d_out_sizes,
                          (uint32_t)n, sl.d_blk, sl.d_sizes, sl.d_out_off, (uint8_t *)d_out, out_cap, sl.d_crc, c->cc,
                          c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, d_out_offsets, d_results, sl.ev_tm,
                          sl.ev_tc);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, 32, hipMemcpyDeviceToHost, stream));
-    if (c->debug) HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, n * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
+    if (c->debug) {
+        HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, n * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
+        sl.have_blk = true;
+    }
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
     sl.have_check = true;
     c->last_slot = si;
     c->last_nb = n;
     const uint32_t *q = sl.h_summary;  // k_dresult's record
-    *out_len = (size_t)((uint64_t)q[6] | ((uint64_t)q[7] << 32));
-    *n_failed = q[4];
-    if (q[0] == 0xFFFFFFFFu) return GZPX_OK;
+    *out_len = (size_t)((uint64_t)q[kWrRecTotal] | ((uint64_t)q[kWrRecTotal + 1] << 32));
+    *n_failed = q[kWrRecFailed];
+    if (q[kWrRecFirst] == 0xFFFFFFFFu) return GZPX_OK;
     if (info) {
-        info->block = q[0];
-        info->found = q[2];
-        info->expected = q[3];
+        info->block = q[kWrRecFirst];
+        info->found = q[kWrRecFound];
+        info->expected = q[kWrRecExpected];
     }
-    return (int)q[1];
+    return (int)q[kWrRecStatus];
 }
 
 int gzpx_dctx_last_check_ms(gzpx_dctx *ctx, float *ms) {
@@ -2329,8 +2266,8 @@ int gzpx_decompress_blocks(gzpx_dctx *c, const uint8_t *in, size_t in_len, const
         std::unique_lock<std::mutex> lk(c->mu);
         if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
         uint8_t dummy = 0;
-        rc = dsubmit_locked(c, in, nullptr, in_len, offsets, sizes, n_blocks, out ? out : &dummy, nullptr, out_cap,
-                            nullptr, true, lk, &ticket);
+        rc = dsubmit_enqueue(c, in, nullptr, in_len, offsets, sizes, n_blocks, out ? out : &dummy, nullptr, out_cap,
+                             nullptr, true, lk, &ticket);
     }
     if (rc != GZPX_OK) return rc;
     return dwait_ticket(c, ticket, out_len, info);
@@ -2377,8 +2314,8 @@ int gzpx_deflate_decompress(gzpx_decompressor *d, const void *in, size_t n, void
     {
         std::unique_lock<std::mutex> lk(c->mu);
         if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-        rc = dsubmit_locked(c, d->framed.data(), nullptr, d->framed.size(), &off, &size, 1, tmp.data(), nullptr, room,
-                            nullptr, true, lk, &ticket);
+        rc = dsubmit_enqueue(c, d->framed.data(), nullptr, d->framed.size(), &off, &size, 1, tmp.data(), nullptr, room,
+                             nullptr, true, lk, &ticket);
     }
     if (rc != GZPX_OK) return rc;
     const DSlot &sl = c->slots[ticket & 0xFF];
@@ -2388,7 +2325,7 @@ int gzpx_deflate_decompress(gzpx_decompressor *d, const void *in, size_t n, void
     if (rc != GZPX_OK) return rc;
     {
         std::lock_guard<std::mutex> lk(c->mu);  // (this handle is single-threaded like libdeflate's: the
-        got = sl.h_summary[8];                  //  slot has not been reused since the wait)
+        got = sl.h_summary[kDsProduced0];       //  slot has not been reused since the wait)
     }
     if (got > cap) return GZPX_ERR_INSUFFICIENT_SPACE;  // cap == 0 and the stream has output
     if (got) memcpy(out, tmp.data(), got);

@@ -1,4 +1,6 @@
-// gzpx_device.h -- data layout shared by the HIP kernels and the host pipeline.
+// gzpx_device.h -- data layout shared by the HIP kernels and the host pipeline.  Included by gzpx_kernels.hip and
+// gzpx_nearopt.hip (the kernels and their launchers), gzpx_api.cpp (the C ABI over them) and gzpx_par.cpp (the
+// members' header length), each behind hip/hip_runtime.h.
 //
 // Vocabulary (follows the reference): a *block* is one BGZF/Mgzip member = one `buffer_size`
 // cut of the caller's stream (src/par/compress.rs:415-416); a *sub-block* is one DEFLATE block
@@ -19,6 +21,9 @@ constexpr unsigned kNumOffset = 32;
 constexpr unsigned kHistStride = kNumLitlen + kNumOffset;  // 320 u32 per sub-block
 constexpr unsigned kHdrWords = 160;                        // dynamic header bit string, <= 4554 bits
 constexpr unsigned kCodeWords = kNumLitlen + kNumOffset;   // (codeword | len << 16) per symbol
+
+// bytes in front of a member's DEFLATE payload (BlockFormatSpec::HEADER_SIZE); `format` as in Config: 0 BGZF, 1 Mgzip
+constexpr uint32_t header_bytes(uint32_t format) { return format == 0 ? 18u : 20u; }
 
 constexpr uint32_t kTokMatch = 0x80000000u;  // token = kTokMatch | offset << 9 | length
 
@@ -184,16 +189,31 @@ struct DBlockHost {
     uint32_t pay_off, pay_len;  // the DEFLATE payload inside the member
     uint32_t cyc[8];  // debug launches: see DBlock in gzpx_kernels.hip
 };
+// DBlockHost.status of a member that was inflated (kInfShortOutput: fewer bytes than its ISIZE)
+enum InflateStatus : uint32_t { kInfOk = 0, kInfBadData = 1, kInfInsufficientSpace = 2, kInfShortOutput = 3 };
 // Scratch of the two-kernel inflate (gzpx_inflate_seg.h): the members' match records, the first record of every
 // 32 KiB output tile, and the list of members handed back to k_inflate ([0] = how many).
 struct InflateScratch {
     void *mlist = nullptr;       // inflate_mlist_bytes(out_cap, nb)
     uint32_t *tfirst = nullptr;  // inflate_tfirst_bytes(out_cap, nb)
     uint32_t *redo = nullptr;    // [1 + nb] the list, [1 + nb] behind it k_inflate_seg's ticket counter
-    uint32_t *summary = nullptr; // [12] k_dsummary: the first failing member and its checksums (both routes); [15] k_inflate_seg's first-block hint
+    uint32_t *summary = nullptr; // [kDsWords] the launch record below
     int n_cu = 0;                // compute units of the device (the size of the persistent launch)
-    int big_members = 0;         // the slab's members average >= 128 KiB compressed: several waves work on each
+    uint64_t in_bytes = 0;       // compressed bytes that stand for the members' total: launch_inflate_members takes their
+                                 // average per member to choose k_inflate_seg's launch form (kSegBigBytes)
 };
+// The record of a launch (InflateScratch.summary, u32 words), 64 bytes of which the host reads the first 48 or 32.
+// k_dsummary (the framed paths): the first failing member in stream order as a quadruple -- its index (0xFFFFFFFF:
+// none), its InflateStatus, the CRC found, the CRC expected -- once under the framed rule (strict: fewer bytes than
+// ISIZE is a failure) and once under the libdeflate-shaped call's (lenient); then the bytes member 0 produced.
+enum { kDsFirst = 0, kDsStatus = 1, kDsFound = 2, kDsExpected = 3 };  // the fields of a quadruple
+enum { kDsStrict = 0, kDsLenient = 4, kDsProduced0 = 8, kDsHostWords = 12 };
+// k_dresult (a batch, gzpx_wrap.h): the first failing member (0xFFFFFFFF: none), its GZPX_* status, found, expected,
+// how many failed, [6..7] the sum of the slots
+enum { kWrRecFirst = 0, kWrRecStatus = 1, kWrRecFound = 2, kWrRecExpected = 3, kWrRecFailed = 4, kWrRecTotal = 6, kWrRecHostWords = 8 };
+// behind both, and nobody's to read on the host: where a member's first block ended, per mille -- k_inflate_seg's
+// guess for the next members, kept from launch to launch
+enum { kDsSegHint = 15, kDsWords = 16 };
 enum { kInflateRouteSeg = 0, kInflateRouteWave = 1 };  // k_inflate_seg + k_lzcopy (default) | k_inflate for every member
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb);
 size_t inflate_tfirst_bytes(uint64_t out_cap, uint64_t nb);
@@ -203,7 +223,7 @@ void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_off
                     hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc, int route, hipEvent_t ev_mid = nullptr);
 
 // A batch of independent members in a raw / zlib / gzip wrapper (gzpx_wrap.h): the table and every result in device
-// memory; sc.summary gets k_dresult's record (kWrRec*: first failing member, its status and values, failures, total).
+// memory; sc.summary gets k_dresult's record (kWrRec*).
 void launch_inflate_batch(int wrap, int short_ok, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets,
                           const uint32_t *d_sizes, const uint32_t *d_out_sizes, uint32_t nb, void *d_blk, uint32_t *d_slot,
                           uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap, uint32_t *d_check, const CrcConsts &cc,

@@ -207,7 +207,6 @@ __device__ __forceinline__ void offset_slot(uint32_t off, uint32_t &slot, uint32
     }
 }
 
-__device__ __forceinline__ uint32_t hdr_len_of(uint32_t format) { return format == 0 ? 18u : 20u; }
 
 // RFC 1951's order of the code length code lengths (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13,
 // 2, 14, 1, 15), five bits each in two constants: a table indexed by a lane or a loop counter would be an
@@ -3799,7 +3798,7 @@ __global__ __launch_bounds__(64, GZPX_HUFF_WAVES) void k_huffman(Config cfg, Blo
     BlockMeta *meta = meta_all + b;
     SubMeta *sub = sub_all + (uint64_t)b * cfg.max_sub;
     const uint32_t n = meta->n;
-    const uint32_t hdr_len = hdr_len_of(cfg.format);
+    const uint32_t hdr_len = header_bytes(cfg.format);
     const uint32_t eof_len = (meta->is_last && cfg.format == 0) ? 28u : 0u;
 
     if (n <= cfg.passthrough) {
@@ -4483,7 +4482,7 @@ __device__ __forceinline__ void emit_block(const Config &cfg, const uint8_t *__r
     const uint64_t dst_off = out_off[b];
     if (meta->status != kStatusOk || dst_off + framed > out_cap) return;  // host reports the error
     const uint8_t *in = slab + (uint64_t)b * cfg.block_size;
-    const uint32_t hdr_len = hdr_len_of(cfg.format);
+    const uint32_t hdr_len = header_bytes(cfg.format);
     // "aligned coordinates": byte i of the framed block lives at lead + i, so that dword
     // boundaries of the stage are dword boundaries of the output address
     const uint32_t lead = (uint32_t)(((uintptr_t)out + dst_off) & 3u);
@@ -4718,9 +4717,9 @@ __global__ __launch_bounds__(kEmitThreads, 8) void k_emit(Config cfg, const uint
 // member, so a slab of blocks is inflated by one launch.
 //   k_dinit    footer (CRC32, ISIZE) of every block -> DBlock
 //   k_dscan    exclusive scan of ISIZE -> output offsets
-//   k_inflate  libdeflate_deflate_decompress for every block: one wave per block.  The wave keeps
-//              the last 32 KiB of output in an LDS ring (the DEFLATE window) and streams finished
-//              output to HBM in coalesced pieces; compressed dwords come through a 1 KiB LDS ring
+//   k_inflate  libdeflate_deflate_decompress for every block: one wave per block.  The wave writes
+//              its output straight to HBM and reads match sources back from there (the DEFLATE
+//              window is the block's own output); compressed dwords come through a 1 KiB LDS ring
 //              with one 256-byte piece prefetched in registers; Huffman decode tables (10-bit /
 //              8-bit direct lookup + canonical fallback) are rebuilt in LDS for every dynamic
 //              sub-block by all 64 lanes.  Symbols are decoded 128 bit positions per round: every
@@ -4728,14 +4727,13 @@ __global__ __launch_bounds__(kEmitThreads, 8) void k_emit(Config cfg, const uint
 //              the real ones, a prefix sum places them, and each output pass writes 64 bytes.
 //   k_crc32    (shared with the compressor) CRC-32 of the inflated bytes, checked against the footer
 // ------------------------------------------------------------------------------------------
-template <bool GWIN>
-struct InfLdsT {
-    // GWIN = false: a 32 KiB ring of the most recent output bytes (the DEFLATE window) lives here and
-    // is flushed to HBM in dwords.  GWIN = true: no ring -- output bytes go straight to the block's
-    // place in HBM and matches read them back from there (L2-hot); what is left is ~7.7 KiB, so 20
-    // waves share a CU instead of 4 and hide each other's latencies (measured: 2 / 3 / 4 / 5 / 6 waves per SIMD
-    // = 52 / 58 / 58 / 65 / 62 GiB/s on the bench stream; the LDS-ring version with 1: 23).
-    uint32_t win[GWIN ? 1 : 8192];
+struct InfLds {
+    // No window here: output bytes go straight to the block's place in HBM and matches read them back from
+    // there (L2-hot).  An earlier version kept a 32 KiB ring of the most recent output bytes (the DEFLATE window)
+    // in LDS and flushed it to HBM in dwords; without it ~7.7 KiB are left, so 20 waves share a CU instead of 4
+    // and hide each other's latencies (measured: 2 / 3 / 4 / 5 / 6 waves per SIMD = 52 / 58 / 58 / 65 / 62 GiB/s
+    // on the bench stream; the LDS-ring version with 1: 23).
+    uint32_t ring_was_here;  // (one word where the ring began: every offset below, and with them k_inflate's instructions, stay as measured)
     uint32_t lfast[1024];   // litlen entries for codes of <= 10 bits, 0 = longer code
     uint32_t ofast[256];    // offset entries for codes of <= 8 bits (and the 7-bit precode table)
     uint32_t inr[256];      // ring of compressed dwords (absolute dword index & 255)
@@ -4751,8 +4749,6 @@ struct InfLdsT {
 #define GZPX_INF_R 2
 #endif
 constexpr uint32_t kInfR = GZPX_INF_R;  // groups of 64 bit positions decoded per round
-
-enum InflateStatus : uint32_t { kInfOk = 0, kInfBadData = 1, kInfInsufficientSpace = 2, kInfShortOutput = 3 };
 
 // Decode-table entries (32 bit).  bits 0-3: codeword length (0 = not in the fast table);
 //   litlen: bits 4-5 type (0 literal, 1 length, 2 end of block), bits 8-15 the
@@ -4895,7 +4891,7 @@ struct DBlock {
     uint32_t pay_len;   // its length; the member's bytes behind it (the trailer) are readable, nothing behind the member is
     uint32_t cyc[8];    // debug launches only: shader-clock cycles [0] whole block, [1] headers + table
                         // builds, [2] round set-up (input bits + table gathers), [3] literal stores +
-                        // match copies; counts [4] rounds, [5] literals, [6] matches, [7] window flushes
+                        // match copies; counts [4] rounds, [5] literals, [6] matches, [7] unused (the LDS ring's flushes)
 };
 
 __global__ void k_dinit(uint32_t hdr_len, uint32_t nb, const uint8_t *__restrict__ in, const uint64_t *__restrict__ offsets,
@@ -4951,15 +4947,13 @@ __global__ __launch_bounds__(256) void k_dscan(uint32_t nb, const DBlock *__rest
 // memory latency per symbol.  Literals of a round are stored together (one ds_write_b8, each marked
 // lane at o + its rank); a match first commits the literals before it, then copies with the wave.
 #ifndef GZPX_INF_WAVES
-#define GZPX_INF_WAVES 5  // waves per SIMD the global-window k_inflate is compiled for (VGPR budget 512 / n)
+#define GZPX_INF_WAVES 5  // waves per SIMD k_inflate is compiled for (VGPR budget 512 / n)
 #endif
-template <bool DBG, bool GWIN>
-__global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const uint8_t *__restrict__ in_all,
-                                                              DBlock *__restrict__ blk_all,
-                                                              const uint64_t *__restrict__ out_off,
-                                                              uint8_t *out_all, uint64_t out_cap,
-                                                              const uint32_t *__restrict__ redo) {
-    __shared__ InfLdsT<GWIN> h;
+template <bool DBG>
+__global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *__restrict__ in_all, DBlock *__restrict__ blk_all,
+                                                                const uint64_t *__restrict__ out_off, uint8_t *out_all,
+                                                                uint64_t out_cap, const uint32_t *__restrict__ redo) {
+    __shared__ InfLds h;
     const uint32_t lane = threadIdx.x;
     // with a redo list (k_inflate_seg / k_lzcopy): the members on it, which those kernels left for this one
     uint32_t bidx = blockIdx.x;
@@ -4978,7 +4972,6 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
     uint8_t *out = out_all + ooff;
     const uint8_t *pay = in_all + blk->in_off + blk->pay_off;
     const uint32_t pay_len = blk->pay_len;
-    uint8_t *win8 = (uint8_t *)h.win;
     const long long t_begin = DBG ? clock64() : 0;
     uint32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -5027,45 +5020,21 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
 
     uint32_t bp = bit0;
     uint32_t o = 0;        // bytes produced
-    uint32_t flushed = 0;  // bytes already written to HBM
     uint32_t status = kInfOk;
-    // the window: byte `pos` of the block's output (GWIN: in HBM, where a wave reads its own earlier
-    // stores back in program order; otherwise the LDS ring)
-    auto win_load = [&](uint32_t pos) -> uint32_t { return GWIN ? (uint32_t)out[pos] : (uint32_t)win8[pos & 32767u]; };
-    auto win_store = [&](uint32_t pos, uint32_t v) {
-        if (GWIN) out[pos] = (uint8_t)v;
-        else win8[pos & 32767u] = (uint8_t)v;
-    };
-    // write ring bytes [flushed, upto) to HBM: whole dwords where the destination is aligned
-    auto flush = [&](uint32_t upto) {
-        if (GWIN) {
-            flushed = upto;
-            return;
-        }
-        wave_sync();
-        if (DBG) dbg[7]++;
-        uint32_t q = flushed;
-        while (q < upto && (((uintptr_t)(out + q)) & 3u)) {  // head bytes (uniform loop)
-            if (lane == 0) out[q] = win8[q & 32767u];
-            q++;
-        }
-        const uint32_t nw = (upto - q) >> 2;
-        for (uint32_t k = lane; k < nw; k += 64) {
-            const uint32_t r = (q + 4 * k) & 32767u;
-            const uint32_t lo = h.win[r >> 2], hi = h.win[((r >> 2) + 1) & 8191u];
-            *(uint32_t *)(out + q + 4 * k) = __builtin_amdgcn_alignbyte(hi, lo, r & 3u);
-        }
-        q += 4 * nw;
-        if (q + lane < upto) out[q + lane] = win8[(q + lane) & 32767u];
-        flushed = upto;
-        wave_sync();
+    // the window: byte `pos` of the block's output, in HBM, where a wave reads its own earlier stores back in
+    // program order
+    auto win_load = [&](uint32_t pos) -> uint32_t { return (uint32_t)out[pos]; };
+    auto win_store = [&](uint32_t pos, uint32_t v) { out[pos] = (uint8_t)v; };
+    // one more of the events dbg[k] counts.  (A lambda that holds dbg by reference, as the ring's flush did: with it the
+    // instrumented kernel compiles to the instructions its clocks have been read with; the plain one has no dbg.)
+    auto tick = [&](uint32_t k) {
+        if (DBG) dbg[k]++;
     };
 
     bool final_block = false;
     while (!final_block && status == kInfOk) {
         bp = uniform(bp);
         o = uniform(o);
-        flushed = uniform(flushed);
         hi_w = uniform(hi_w);
         status = uniform(status);
         if (bp > bit_end) {
@@ -5098,33 +5067,23 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
                 status = kInfInsufficientSpace;
                 break;
             }
-            if (GWIN) {
-                // straight from the payload to the output: head bytes up to a dword boundary of the
-                // destination, then dwords (the source is read as aligned dword pairs), then the tail
-                const uint8_t *sp = pay + src;
-                uint8_t *dp = out + o;
-                uint32_t head = (uint32_t)((4u - ((uintptr_t)dp & 3u)) & 3u);
-                if (head > len) head = len;
-                if (lane < head) dp[lane] = sp[lane];
-                const uint32_t nw = (len - head) >> 2;
-                const uint32_t smis = (uint32_t)((uintptr_t)(sp + head) & 3u);
-                const uint32_t *s32 = (const uint32_t *)(sp + head - smis);
-                for (uint32_t k = lane; k < nw; k += 64) {
-                    const uint32_t lo = s32[k], hi = smis ? s32[k + 1] : 0u;  // (hi: inside the member, the footer follows)
-                    *(uint32_t *)(dp + head + 4 * k) = __builtin_amdgcn_alignbyte(hi, lo, smis);
-                }
-                const uint32_t donew = head + 4 * nw;
-                if (donew + lane < len) dp[donew + lane] = sp[donew + lane];
-                o += len;
-            } else {
-                for (uint32_t done = 0; done < len; done += 16384u) {
-                    const uint32_t piece = len - done < 16384u ? len - done : 16384u;
-                    if (o + piece - flushed > 32768u - 16u) flush(o);
-                    wave_sync();
-                    for (uint32_t i = lane; i < piece; i += 64) win8[(o + i) & 32767u] = pay[src + done + i];
-                    o += piece;
-                }
+            // straight from the payload to the output: head bytes up to a dword boundary of the
+            // destination, then dwords (the source is read as aligned dword pairs), then the tail
+            const uint8_t *sp = pay + src;
+            uint8_t *dp = out + o;
+            uint32_t head = (uint32_t)((4u - ((uintptr_t)dp & 3u)) & 3u);
+            if (head > len) head = len;
+            if (lane < head) dp[lane] = sp[lane];
+            const uint32_t nw = (len - head) >> 2;
+            const uint32_t smis = (uint32_t)((uintptr_t)(sp + head) & 3u);
+            const uint32_t *s32 = (const uint32_t *)(sp + head - smis);
+            for (uint32_t k = lane; k < nw; k += 64) {
+                const uint32_t lo = s32[k], hi = smis ? s32[k + 1] : 0u;  // (hi: inside the member, the footer follows)
+                *(uint32_t *)(dp + head + 4 * k) = __builtin_amdgcn_alignbyte(hi, lo, smis);
             }
+            const uint32_t donew = head + 4 * nw;
+            if (donew + lane < len) dp[donew + lane] = sp[donew + lane];
+            o += len;
             bp += 8u * len;
             continue;
         }
@@ -5243,7 +5202,6 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
             // (these are wave-uniform by construction; saying so keeps the loop on the scalar unit)
             bp = uniform(bp);
             o = uniform(o);
-            flushed = uniform(flushed);
             hi_w = uniform(hi_w);
             status = uniform(status);
             ensure(bp + 64 * kInfR - 64);
@@ -5362,14 +5320,13 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
                     status = kInfInsufficientSpace;
                     break;
                 }
-                if (o + tout - flushed > 32768u) flush(o & ~3u);
                 // A round whose symbols are all literals (nearly every round of an incompressible member: configs[2]'s
                 // printable noise is literals of 7-8 bits, ~15 per round) needs no owners, no window and no order:
                 // every marked lane stores its byte where the prefix sum put it.
                 bool any_match = false;
 #pragma unroll
                 for (uint32_t g = 0; g < kInfR; g++) any_match = any_match || (mine[g] && is_match[g]);
-                if (GWIN && __ballot(any_match) == 0) {
+                if (__ballot(any_match) == 0) {
 #pragma unroll
                     for (uint32_t g = 0; g < kInfR; g++)
                         if (mine[g]) out[o + opos[g]] = (uint8_t)(le[g] >> 8);
@@ -5421,41 +5378,26 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
                     const uint32_t srcrel = (p1 & 0xFFFFu) - sdist + r;  // relative to o; "negative" = older
                     uint64_t done = __ballot(!active);
                     bool pending = active;
-                    if (GWIN) {
-                        // sources older than this pass come from HBM (one gather for all of them, issued
-                        // before the loop); sources inside the pass are handed over between lanes
-                        const bool in_pass = m && (int32_t)(srcrel - pass) >= 0;
-                        uint32_t myv = (p1 >> 16) & 0xFFu;  // the literal
-                        if (active && m && !in_pass) myv = out[o + srcrel];
-                        bool have = active && (!m || !in_pass);
-                        if (have) out[o + prel] = (uint8_t)myv;
-                        done |= __ballot(have);
-                        pending = pending && !have;
-                        while (__ballot(pending) != 0) {
-                            const uint32_t sl = (srcrel - pass) & 63u;
-                            const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(sl << 2), (int)myv);
-                            const bool ready = pending && ((done >> sl) & 1ull) != 0;
-                            if (ready) {
-                                myv = got;
-                                out[o + prel] = (uint8_t)myv;
-                            }
-                            done |= __ballot(ready);
-                            pending = pending && !ready;
-                            if (DBG) dbg[6]++;
+                    // sources older than this pass come from HBM (one gather for all of them, issued
+                    // before the loop); sources inside the pass are handed over between lanes
+                    const bool in_pass = m && (int32_t)(srcrel - pass) >= 0;
+                    uint32_t myv = (p1 >> 16) & 0xFFu;  // the literal
+                    if (active && m && !in_pass) myv = out[o + srcrel];
+                    bool have = active && (!m || !in_pass);
+                    if (have) out[o + prel] = (uint8_t)myv;
+                    done |= __ballot(have);
+                    pending = pending && !have;
+                    while (__ballot(pending) != 0) {
+                        const uint32_t sl = (srcrel - pass) & 63u;
+                        const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(sl << 2), (int)myv);
+                        const bool ready = pending && ((done >> sl) & 1ull) != 0;
+                        if (ready) {
+                            myv = got;
+                            out[o + prel] = (uint8_t)myv;
                         }
-                    } else {
-                        do {
-                            const bool in_pass = m && (int32_t)(srcrel - pass) >= 0;
-                            const bool ready = pending && (!in_pass || ((done >> ((srcrel - pass) & 63u)) & 1ull) != 0);
-                            uint32_t v = (p1 >> 16) & 0xFFu;
-                            if (ready && m) v = win8[(o + srcrel) & 32767u];
-                            wave_sync();
-                            if (ready) win8[(o + prel) & 32767u] = (uint8_t)v;
-                            wave_sync();
-                            done |= __ballot(ready);
-                            pending = pending && !ready;
-                            if (DBG) dbg[6]++;
-                        } while (__ballot(pending) != 0);
+                        done |= __ballot(ready);
+                        pending = pending && !ready;
+                        tick(6);
                     }
                 }
                 o += tout;
@@ -5495,7 +5437,6 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
                     status = kInfInsufficientSpace;
                     break;
                 }
-                if (o + 1 - flushed > 32768u) flush(o & ~3u);
                 wave_sync();
                 if (lane == 0) win_store(o, e >> 8);
                 wave_sync();
@@ -5529,7 +5470,6 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
                 status = kInfInsufficientSpace;
                 break;
             }
-            if (o + len - flushed > 32768u) flush(o & ~3u);
             // out[o + i] = out[o - dist + (i mod dist)]: every source byte is older than o
             wave_sync();
             const uint32_t src0 = o - dist;
@@ -5554,7 +5494,6 @@ __global__ __launch_bounds__(64, GWIN ? GZPX_INF_WAVES : 1) void k_inflate(const
     // padding behind a truncated payload -> BadData
     if (status == kInfOk && bp > bit_end) status = kInfBadData;
     if (status == kInfOk && o != isize) status = kInfShortOutput;
-    flush(o);
     // libdeflater hands back a zero-initialised Vec of orig_size bytes: a short block stays zero
     for (uint32_t i = o + lane; i < isize; i += 64) out[i] = 0;
     if (lane == 0) {
@@ -5590,10 +5529,10 @@ __global__ __launch_bounds__(kCrcThreads, 8) void k_dcrc32(const uint8_t *__rest
 // What the host wants to know of a launch: the first failing member in stream order (src/par/decompress.rs:162-186),
 // once under the framed rule (a member that inflates to fewer bytes than its footer says is BadData) and once under
 // the libdeflate-shaped call's (fewer bytes are accepted), with its status and the two checksums -- 48 bytes instead
-// of a record per member.  DSummary: [0] first failing member, strict (0xFFFFFFFF: none), [1] its status, [2] CRC
-// found, [3] CRC expected, [4..7] the same under the lenient rule, [8] bytes member 0 produced.
+// of a record per member (kDs*, gzpx_device.h).
 __global__ __launch_bounds__(256) void k_dsummary(uint32_t nb, const DBlock *__restrict__ blk, const uint32_t *__restrict__ crc_found,
                                                   uint32_t *__restrict__ sum) {
+    static_assert(kDsStrict == 0 && kDsLenient == 4, "thread 0 writes the strict quadruple, thread 1 the lenient one");
     __shared__ uint32_t first[2];
     const uint32_t tid = threadIdx.x;
     if (tid < 2) first[tid] = 0xFFFFFFFFu;
@@ -5601,18 +5540,19 @@ __global__ __launch_bounds__(256) void k_dsummary(uint32_t nb, const DBlock *__r
     for (uint32_t b = tid; b < nb; b += 256) {
         const uint32_t st = blk[b].status;
         const bool crc_bad = crc_found[b] != blk[b].crc;
-        if (st != 0 || crc_bad) atomicMin(&first[0], b);
-        if (st == 1 || st == 2 || crc_bad) atomicMin(&first[1], b);
+        if (st != kInfOk || crc_bad) atomicMin(&first[0], b);
+        if (st == kInfBadData || st == kInfInsufficientSpace || crc_bad) atomicMin(&first[1], b);
     }
     __syncthreads();
     if (tid < 2) {
         const uint32_t b = first[tid];
-        sum[4 * tid + 0] = b;
-        sum[4 * tid + 1] = b != 0xFFFFFFFFu ? blk[b].status : 0u;
-        sum[4 * tid + 2] = b != 0xFFFFFFFFu ? crc_found[b] : 0u;
-        sum[4 * tid + 3] = b != 0xFFFFFFFFu ? blk[b].crc : 0u;
+        uint32_t *q = sum + kDsLenient * tid;
+        q[kDsFirst] = b;
+        q[kDsStatus] = b != 0xFFFFFFFFu ? blk[b].status : 0u;
+        q[kDsFound] = b != 0xFFFFFFFFu ? crc_found[b] : 0u;
+        q[kDsExpected] = b != 0xFFFFFFFFu ? blk[b].crc : 0u;
     }
-    if (tid == 0) sum[8] = nb ? blk[0].produced : 0u;
+    if (tid == 0) sum[kDsProduced0] = nb ? blk[0].produced : 0u;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -5809,54 +5749,47 @@ void launch_emit(const Config &cfg, const uint8_t *slab, uint64_t, uint32_t nb, 
 }
 
 // The decode of nb members whose records and output offsets are in place (k_dinit + k_dscan, or k_dinit_wrap +
-// k_dscan_slots): k_inflate_seg + k_lzcopy + k_inflate over the redo list, or k_inflate for every member.
+// k_dscan_slots): k_inflate_seg + k_lzcopy + k_inflate over the redo list, or k_inflate for every member.  The
+// template arguments say which of the three kernels carries its clocks.
+template <bool SEG_DBG, bool LC_DBG, bool INF_DBG>
+static void launch_inflate_members_as(const uint8_t *d_in, uint32_t nb, DBlock *blk, uint64_t *d_out_off, uint8_t *d_out,
+                                      uint64_t out_cap, uint32_t *d_crc_found, const CrcConsts &cc, hipStream_t stream,
+                                      const InflateScratch &sc, bool seg, hipEvent_t ev_mid) {
+    if (!seg) {
+        hipLaunchKernelGGL((k_inflate<INF_DBG>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)d_out_off, d_out,
+                           out_cap, (const uint32_t *)nullptr);
+        return;
+    }
+    // decode (literals + match records), LZ copy, then k_inflate over whatever the two left on the redo list
+    LzMatch *ml = (LzMatch *)sc.mlist;
+    const bool big = nb && sc.in_bytes / nb >= kSegBigBytes;  // Mgzip-sized members: kSegBigW waves each
+    const uint32_t seg_wgs = (uint32_t)(sc.n_cu > 0 ? sc.n_cu : 256) * 4u * GZPX_SEG_WAVES / (big ? (uint32_t)kSegBigW : (uint32_t)kSegSmallW);  // resident workgroups
+    const uint32_t seg_grid = nb < seg_wgs ? nb : seg_wgs;
+    uint32_t *seg_hint = sc.summary ? sc.summary + kDsSegHint : nullptr;
+    if (big)
+        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegBigW>), dim3(seg_grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
+                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint);
+    else
+        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegSmallW>), dim3(seg_grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
+                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint);
+    if (ev_mid) (void)hipEventRecord(ev_mid, stream);
+    hipLaunchKernelGGL((k_lzcopy<LC_DBG>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off, d_out,
+                       (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
+    hipLaunchKernelGGL((k_inflate<INF_DBG>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)d_out_off, d_out,
+                       out_cap, (const uint32_t *)sc.redo);
+}
+
+// debug 1: k_inflate_seg's and k_inflate's clocks; 2: k_lzcopy's instead.  The k_inflate route has one kernel to
+// instrument and does so for any non-zero value.
 static void launch_inflate_members(const uint8_t *d_in, uint32_t nb, DBlock *blk, uint64_t *d_out_off, uint8_t *d_out,
                                    uint64_t out_cap, uint32_t *d_crc_found, const CrcConsts &cc, int debug,
                                    hipStream_t stream, const InflateScratch &sc, bool seg, hipEvent_t ev_mid) {
-    if (seg) {
-        // decode (literals + match records), LZ copy, then k_inflate over whatever the two left on the redo list
-        LzMatch *ml = (LzMatch *)sc.mlist;
-        const bool big = sc.big_members != 0;  // Mgzip-sized members: kSegBigW waves each
-        const uint32_t seg_wgs = (uint32_t)(sc.n_cu > 0 ? sc.n_cu : 256) * 4u * GZPX_SEG_WAVES / (big ? (uint32_t)kSegBigW : (uint32_t)kSegSmallW);  // resident workgroups
-        const uint32_t seg_grid = nb < seg_wgs ? nb : seg_wgs;
-        uint32_t *seg_hint = sc.summary ? sc.summary + 15 : nullptr;  // (where a member's first block ended, per mille: the next members' guess)
-#define GZPX_LAUNCH_SEG(DBG_)                                                                                              \
-    do {                                                                                                                   \
-        if (big)                                                                                                           \
-            hipLaunchKernelGGL((k_inflate_seg<DBG_, kSegBigW>), dim3(seg_grid), dim3(64 * kSegBigW), 0, stream,            \
-                               d_in, blk, (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint); \
-        else                                                                                                               \
-            hipLaunchKernelGGL((k_inflate_seg<DBG_, kSegSmallW>), dim3(seg_grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk, \
-                               (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint);         \
-        if (ev_mid) (void)hipEventRecord(ev_mid, stream);                                                                  \
-    } while (0)
-        if (debug == 1) {
-            GZPX_LAUNCH_SEG(true);
-            hipLaunchKernelGGL((k_lzcopy<false>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off,
-                               d_out, (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
-            hipLaunchKernelGGL((k_inflate<true, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
-                               (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)sc.redo);
-        } else if (debug == 2) {  // k_lzcopy's clocks instead of k_inflate_seg's
-            GZPX_LAUNCH_SEG(false);
-            hipLaunchKernelGGL((k_lzcopy<true>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off,
-                               d_out, (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
-            hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
-                               (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)sc.redo);
-        } else {
-            GZPX_LAUNCH_SEG(false);
-            hipLaunchKernelGGL((k_lzcopy<false>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off,
-                               d_out, (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
-            hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
-                               (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)sc.redo);
-        }
-#undef GZPX_LAUNCH_SEG
-    } else if (debug) {
-        hipLaunchKernelGGL((k_inflate<true, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
-                           (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)nullptr);
-    } else {
-        hipLaunchKernelGGL((k_inflate<false, true>), dim3(nb), dim3(64), 0, stream, d_in, blk,
-                           (const uint64_t *)d_out_off, d_out, out_cap, (const uint32_t *)nullptr);
-    }
+    if (debug == 1 || (debug && !seg))
+        launch_inflate_members_as<true, false, true>(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, stream, sc, seg, ev_mid);
+    else if (debug == 2)
+        launch_inflate_members_as<false, true, false>(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, stream, sc, seg, ev_mid);
+    else
+        launch_inflate_members_as<false, false, false>(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, stream, sc, seg, ev_mid);
 }
 
 void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes,
@@ -5922,7 +5855,7 @@ void launch_member_scan(int format, const uint8_t *d_in, uint64_t in_len, uint32
     s.in = d_in;
     s.len = in_len;
     s.lead = (uint32_t)((uintptr_t)d_in & 15u);
-    s.hdr = format == 0 ? 18u : 20u;
+    s.hdr = header_bytes((uint32_t)format);
     s.sid = format == 0 ? ('B' | ('C' << 8)) : ('I' | ('G' << 8));
     s.seg_words = seg_bytes / 16u;
     const uint32_t cand_grid = (n_seg + kMsThreads / 64u - 1u) / (kMsThreads / 64u);

@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gzpx_device.h"
+
 #include <pthread.h>
 #include <sched.h>
 
@@ -553,7 +555,7 @@ ParDecompress::SlabPtr ParDecompress::recycle() {
 // headers, hand whole blocks on.
 void ParDecompress::reader_main() {
     (void)hipSetDevice(cfg_.device);
-    const size_t hdr = cfg_.format == GZPX_FORMAT_BGZF ? 18 : 20;
+    const size_t hdr = gzpx::header_bytes(cfg_.format);
     std::vector<uint8_t> carry;  // the partial block at the end of the previous slab
     bool eof = false;
     for (;;) {

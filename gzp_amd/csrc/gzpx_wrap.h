@@ -11,11 +11,11 @@
 //   (k_inflate_seg + k_lzcopy + k_inflate, or k_inflate alone: launch_inflate_members)
 //   k_dadler32     zlib: Adler-32 of the bytes every member produced, a workgroup per member.
 //   (k_dcrc32      gzip: as for BGZF; k_lzcopy's in-tile CRC serves too.  Raw: neither.)
-//   k_dresult      per-member status / produced / check values, the caller's offsets, and the record for the host:
-//                  first failing member, its status and two values, how many failed, the total.
+//   k_dresult      per-member status / produced / check values, the caller's offsets, and the record for the host
+//                  (kWrRec*, gzpx_device.h): first failing member, its status and two values, how many failed, the total.
 #pragma once
 
-// DBlock.status of a member that the wrapper kernels took out (never decoded; InflateStatus and kInfRedo are below)
+// DBlock.status of a member that the wrapper kernels took out (never decoded; InflateStatus: gzpx_device.h, kInfRedo: gzpx_inflate_seg.h)
 constexpr uint32_t kWrapArg = 0x10u;     // the table entry reaches outside the input, or is shorter than its wrapper
 constexpr uint32_t kWrapHeader = 0x11u;  // the wrapper's header is invalid
 constexpr uint32_t kWrapSpace = 0x12u;   // the slot ends behind out_cap
@@ -286,9 +286,7 @@ struct WrapResult {
 };
 constexpr uint32_t kWrOk = 0, kWrInvalidArg = 1, kWrInsufficientSpace = 4, kWrInvalidHeader = 12, kWrInvalidCheck = 13,
                    kWrBadData = 14;
-// the record (u32 words): the first failing member (0xFFFFFFFF: none), its status, found, expected, how many failed,
-// [6..7] the sum of the slots
-enum { kWrRecFirst = 0, kWrRecStatus = 1, kWrRecFound = 2, kWrRecExpected = 3, kWrRecFailed = 4, kWrRecTotal = 6 };
+// (the record k_dresult leaves for the host: kWrRec*, gzpx_device.h)
 
 __device__ __forceinline__ WrapResult wrap_verdict(const DBlock &d, uint32_t slot, uint32_t check, uint32_t wrap, bool short_ok) {
     WrapResult r;

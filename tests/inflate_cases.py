@@ -25,9 +25,9 @@ from gzp_amd import _native, synth
 VERDICTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "inflate_verdicts.json")
 ROUTES = {"seg": _native.INFLATE_SEG, "wave": _native.INFLATE_WAVE}
 LD_OK, LD_BAD_DATA, LD_SHORT_OUTPUT, LD_INSUFFICIENT_SPACE = 0, 1, 2, 3
-# The launch form of k_inflate_seg for large members (kSegBigW waves a member) is chosen in launch_inflate
-# (gzpx_kernels.hip) from DSlot.big_members, which dsubmit (gzpx_api.cpp) sets when the slab's compressed bytes per
-# member reach kSegBigBytes (gzpx_inflate_seg.h): the AVERAGE over the slab, so a one-member slab switches at this size.
+# kSegBigBytes (gzpx_inflate_seg.h): launch_inflate_members (gzpx_kernels.hip) takes the launch form of k_inflate_seg for
+# large members (kSegBigW waves a member) when the compressed bytes the host hands it (InflateScratch.in_bytes) reach
+# this much per member: the AVERAGE over the launch, so a one-member slab switches at this size.
 SEG_BIG_BYTES = 131072
 
 

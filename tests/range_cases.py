@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from gzp_amd import _native, synth
+from inflate_cases import SEG_BIG_BYTES
 from scan_cases import BGZF, MGZIP, HDR, EOF, Mem, member, our_streams
 
 ROUTES = (_native.INFLATE_SEG, _native.INFLATE_WAVE)
@@ -358,3 +359,28 @@ def touched(lib):
                 with pytest.raises(_native.GzpxError) as e:
                     read(mem, d, ix, ptr, len(m), [(u[2], u[2] + 5)])
                 assert (e.value.code, e.value.block) == (_native.ERR_INSUFFICIENT_SPACE, 2)
+
+
+# ------------------------------------------------------------------------------------------------ 6. large members
+def big_members(lib):
+    """The launch form of k_inflate_seg with several waves a member, through a read: Mgzip streams of zlib-made members
+    whose compressed average -- the index's consumed // n, which the read hands to the launch -- lies on either side
+    of SEG_BIG_BYTES, one of them with a member far below it.  A chunk is three quarters random bytes and then the tail of
+    a text buffer of its size, so that real Huffman blocks stand beside the stored ones."""
+    mem = Mem(lib)
+    for sizes, big in (((146000, 147000), False), ((156000, 158000, 165000), True), ((60000, 260000), True)):
+        chunks = [synth.make("random", 3 * n // 4, n).tobytes() + synth.make("text", n, n).tobytes()[3 * n // 4:] for n in sizes]
+        s = b"".join(member(MGZIP, c, 1) for c in chunks)
+        pl = Plain(MGZIP, s)
+        assert pl.plain == b"".join(chunks) and pl.consumed == len(s)
+        assert (pl.consumed // pl.n >= SEG_BIG_BYTES) == big, (sizes, pl.size)
+        keep, ptr = mem.put(s, shift=len(sizes))
+        u, t = pl.ustart, pl.total
+        reads = (("whole", [(0, t)]), ("across the first boundary", [(u[1] - 3, u[1] + 70000)]), ("last byte", [(t - 1, t)]),
+                 ("empty", [(u[1], u[1])]))
+        for route in ROUTES:
+            with _native.DContext(format=MGZIP, lib=lib) as d, d.build_index_device(ptr, len(s)) as ix:
+                assert (ix.consumed // ix.n_members >= SEG_BIG_BYTES) == big, (sizes, ix.consumed)
+                d.set_route(route)
+                for what, rs in reads:
+                    check_read(mem, d, ix, pl, ptr, len(s), rs, (sizes, route, what))

@@ -25,3 +25,7 @@ def test_errors(emu_lib):
 
 def test_only_needed_members_are_touched(emu_lib):
     range_cases.touched(emu_lib)
+
+
+def test_members_around_the_several_waves_size(emu_lib):
+    range_cases.big_members(emu_lib)

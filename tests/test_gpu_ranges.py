@@ -35,6 +35,10 @@ def test_only_needed_members_are_touched(hip_lib):
     range_cases.touched(hip_lib)
 
 
+def test_members_around_the_several_waves_size(hip_lib):
+    range_cases.big_members(hip_lib)
+
+
 # ---------------------------------------------------------------------------------------------------- full size
 def _device_compress(lib, fmt, level, bs, d_in, n):
     with _native.Context(format=fmt, level=level, buffer_size=bs, lib=lib, max_slab_bytes=n) as ctx:

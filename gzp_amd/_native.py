@@ -67,7 +67,7 @@ EXPORTS = [
     "gzpx_scan_blocks_device", "gzpx_decompress_stream_device", "gzpx_index_device", "gzpx_dctx_last_scan_ms",
     "gzpx_dindex_build_device", "gzpx_dindex_entries", "gzpx_dindex_destroy", "gzpx_read_ranges_device",
     "gzpx_dctx_last_ranges_members", "gzpx_dctx_last_ranges_ms",
-    "gzpx_inflate_batch_device", "gzpx_dctx_last_check_ms",
+    "gzpx_inflate_batch_device", "gzpx_dctx_last_check_ms", "gzpx_inflate_batch_sizes_device",
 ]
 
 
@@ -254,6 +254,9 @@ class GzpxLib:
         L.gzpx_inflate_batch_device.restype = i32
         L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
                                                 ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_inflate_batch_sizes_device.restype = i32
+        L.gzpx_inflate_batch_sizes_device.argtypes = [vp, i32, vp, sz, vp, vp, sz, ctypes.c_uint32, vp, vp, vp, pu64, psz,
+                                                      ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_dctx_last_check_ms.restype = i32
         L.gzpx_dctx_last_check_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_alloc_decompressor.restype = vp
@@ -908,6 +911,27 @@ class DContext:
         if raise_on_member_error:
             self._raise(rc, info)
         return out_len.value, n_failed.value, info.block
+
+    def inflate_batch_sizes_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, n, d_out_sizes_ptr,
+                                   d_in_used_ptr=None, d_results_ptr=None, max_out_size=0, stream=None,
+                                   raise_on_member_error=True):
+        """The size query in front of inflate_batch_device: what each of n members inflates to (d_out_sizes_ptr,
+        uint32[n], written) and how long it is (d_in_used_ptr, uint32[n], optional), with d_in_sizes as UPPER BOUNDS;
+        nothing is inflated and no check is verified.  max_out_size caps a member's output (0: 2^32 - 1).  Returns
+        (total_out, n_failed); a failing member raises GzpxError with block= the first one's index, unless
+        raise_on_member_error=False: then (total_out, n_failed, first_failed)."""
+        total, n_failed = ctypes.c_uint64(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_inflate_batch_sizes_device(self.h, int(wrap), d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, n,
+                                                        int(max_out_size), d_out_sizes_ptr, d_in_used_ptr, d_results_ptr,
+                                                        ctypes.byref(total), ctypes.byref(n_failed), ctypes.byref(info), stream)
+        if n_failed.value == 0:
+            if rc != OK:  # the call itself was refused, or the device failed
+                raise GzpxError(rc, self.lib.strerror(rc))
+            return (total.value, 0) if raise_on_member_error else (total.value, 0, None)
+        if raise_on_member_error:
+            self._raise(rc, info)
+        return total.value, n_failed.value, info.block
 
     def last_check_ms(self):
         """HIP-event duration of the check kernel (Adler-32 / CRC-32) of the last inflate_batch_device."""

@@ -1544,14 +1544,15 @@ int dslot_seg_scratch(DSlot &sl, size_t out_cap, size_t nb) {
 // A slot made ready for an inflate launch of nb members on `route`: what the launch reads from it, what the getters
 // read after it, and on the decode / copy route that pair's scratch for `cap` bytes of output.  `in_bytes`: the
 // compressed bytes that stand for the members' total (InflateScratch).  The slot then holds no member records and no
-// check time: the caller that brings the records back, or runs a check kernel, says so itself.
-int dslot_prepare(gzpx_dctx *c, DSlot &sl, size_t nb, int route, size_t cap, uint64_t in_bytes) {
+// check time: the caller that brings the records back, or runs a check kernel, says so itself.  `writes` false (the
+// sizes call): nothing is inflated, so the pair's scratch is neither sized nor allocated.
+int dslot_prepare(gzpx_dctx *c, DSlot &sl, size_t nb, int route, size_t cap, uint64_t in_bytes, bool writes = true) {
     sl.nb = nb;
     sl.route = route;
     sl.have_blk = sl.have_check = false;
     sl.sc.n_cu = c->n_cu;
     sl.sc.in_bytes = in_bytes;
-    return route == kInflateRouteSeg ? dslot_seg_scratch(sl, cap, nb) : GZPX_OK;
+    return route == kInflateRouteSeg && writes ? dslot_seg_scratch(sl, cap, nb) : GZPX_OK;
 }
 
 // Enqueue the inflate of one slab (c->mu held): copies in, kernels, copies out, as the compress side's submit_enqueue.
@@ -2220,6 +2221,51 @@ int gzpx_inflate_batch_device(gzpx_dctx *c, int wrap, unsigned flags, const void
         info->block = q[kWrRecFirst];
         info->found = q[kWrRecFound];
         info->expected = q[kWrRecExpected];
+    }
+    return (int)q[kWrRecStatus];
+}
+
+int gzpx_inflate_batch_sizes_device(gzpx_dctx *c, int wrap, const void *d_in, size_t in_len, const uint64_t *d_in_offsets,
+                                    const uint32_t *d_in_sizes, size_t n, uint32_t max_out_size, uint32_t *d_out_sizes,
+                                    uint32_t *d_in_used, gzpx_member_result *d_results, uint64_t *total_out, size_t *n_failed,
+                                    gzpx_check_info *info, void *hip_stream) {
+    if (!c || !total_out || !n_failed || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *total_out = 0;
+    *n_failed = 0;
+    if (wrap != GZPX_WRAP_RAW && wrap != GZPX_WRAP_ZLIB && wrap != GZPX_WRAP_GZIP) return GZPX_ERR_INVALID_ARG;
+    if (n && (!d_in_offsets || !d_in_sizes || !d_out_sizes)) return GZPX_ERR_INVALID_ARG;
+    if (n > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    hipStream_t stream = c->stream;
+    if (n == 0) return GZPX_OK;
+    const int si = free_slot(c, lk, true);
+    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
+    GZPX_TRY(dslot_reserve(sl, n));
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    Drain drain{{stream}, 1};
+    // (nothing is inflated: a capacity of 0 and no scratch of the decode / copy pair; the input stands for the members' sum)
+    GZPX_TRY(dslot_prepare(c, sl, n, c->route, 0, in_len, false));
+    launch_inflate_sizes(wrap, (const uint8_t *)d_in, in_len, d_in_offsets, d_in_sizes, max_out_size, (uint32_t)n, sl.d_blk,
+                         c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, d_out_sizes, d_in_used, d_results, sl.ev_tm);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
+    if (c->debug) {
+        HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, n * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
+        sl.have_blk = true;
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    c->last_slot = si;
+    c->last_nb = n;
+    const uint32_t *q = sl.h_summary;  // k_dresult_sizes' record
+    *total_out = (uint64_t)q[kWrRecTotal] | ((uint64_t)q[kWrRecTotal + 1] << 32);
+    *n_failed = q[kWrRecFailed];
+    if (q[kWrRecFirst] == 0xFFFFFFFFu) return GZPX_OK;
+    if (info) {
+        info->block = q[kWrRecFirst];
+        info->found = 0;
+        info->expected = 0;
     }
     return (int)q[kWrRecStatus];
 }

@@ -231,6 +231,14 @@ void launch_inflate_batch(int wrap, int short_ok, const uint8_t *d_in, uint64_t 
                           int route, uint64_t *d_user_off, void *d_results, hipEvent_t ev_mid = nullptr,
                           hipEvent_t ev_check = nullptr);  // (ev_end .. ev_check: the check kernel)
 
+// The sizes of such a batch (gzpx_inflate_batch_sizes_device): the count-only inflate kernels; d_out_sizes [nb] is
+// written, d_in_used [nb] and d_results [nb] if given, sc.summary gets k_dresult_sizes' record (kWrRec*, [6..7] the sum
+// of the good members' sizes).  Of `sc` only redo, summary, n_cu and in_bytes are used.  max_out 0: no cap below 2^32.
+void launch_inflate_sizes(int wrap, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
+                          uint32_t max_out, uint32_t nb, void *d_blk, int debug, hipEvent_t ev_begin, hipEvent_t ev_end,
+                          hipStream_t stream, const InflateScratch &sc, int route, uint32_t *d_out_sizes, uint32_t *d_in_used,
+                          void *d_results, hipEvent_t ev_mid = nullptr);
+
 // Member discovery on the device (gzpx_mscan.h): the candidate headers of a stream, sorted by position, and what the
 // chain from offset 0 makes of them.
 struct MemberScanScratch {

@@ -487,7 +487,15 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
 // entries chain from lane to lane and from wave to wave.  W = 1 for BGZF-sized members (one wave each: thousands of
 // members fill the chip), kSegBigW for Mgzip members (a 1 MiB member is a million symbols: one wave would take its
 // lanes through 16 thousand steps each, and a slab holds too few members for the chip).
-template <bool DBG, int W>
+//
+// COUNT (gzpx_inflate_batch_sizes_device): the member's size and nothing else.  isize is the cap on its output; out_off,
+// the output, the match list and the tile table are not touched (null), stored blocks are stepped over, and pass 3 keeps
+// its walk without its stores: it is where the true path is judged -- type bits, invalid codewords, and a distance
+// against the lane's true output position, which only the prefix sum in front of it gives -- so the same member is
+// handed to k_inflate in this mode as in the writing one, and a member that is not handed over has passed the same
+// checks.  A good member leaves its byte count in DBlock.produced and the payload bytes its stream took (through the
+// byte that holds the last bit of the final block) in DBlock.nmatch.
+template <bool DBG, int W, bool COUNT = false>
 __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uint32_t tid, const uint8_t *__restrict__ in_all,
                                                      DBlock *__restrict__ blk_all, const uint64_t *__restrict__ out_off, uint8_t *out_all,
                                                      uint64_t out_cap, LzMatch *__restrict__ mlist_all, uint32_t *__restrict__ tfirst_all,
@@ -500,18 +508,23 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
     const uint32_t isize = blk->isize;
     if (tid == 0) blk->nmatch = 0;
     if (isize == 0) return;  // src/par/decompress.rs:163-171: nothing to decode
-    const uint64_t ooff = out_off[b];
-    if (ooff + isize > out_cap) {
+    const uint64_t ooff = COUNT ? 0ull : out_off[b];
+    if (!COUNT && ooff + isize > out_cap) {
         if (tid == 0) blk->status = kInfInsufficientSpace;
         return;
     }
-    uint8_t *out = out_all + ooff;
+    uint8_t *out = out_all + ooff;  // (COUNT: out, ml and tf are null and never used)
     const uint8_t *pay = in_all + blk->in_off + blk->pay_off;
     const uint32_t pay_len = blk->pay_len;
     LzMatch *ml = mlist_all + (ooff / 3u + b);
     uint32_t *tf = tfirst_all + ((ooff >> kLzTileShift) + 2ull * b);
-    const bool multi = isize > kLzTile;  // more than one k_lzcopy tile: the first record of every tile is noted
+    const bool multi = !COUNT && isize > kLzTile;  // more than one k_lzcopy tile: the first record of every tile is noted
     if (multi && tid == 0) tf[0] = 0;
+    // does output [at, at + add) end behind isize?  (COUNT: the cap may be 0xFFFFFFFF, the sum needs 33 bits)
+    auto over = [&](uint32_t at, uint32_t add) -> bool {
+        if constexpr (COUNT) return (uint64_t)at + add > isize;
+        else return at + add > isize;
+    };
     const long long t_begin = DBG ? clock64() : 0;
     uint32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -546,9 +559,14 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
             // stored: raw bytes straight from the payload to their place (final bytes, like literals)
             const uint32_t len = uniform(hh.hres[4]);
             const uint32_t src = (bp - bit0) >> 3;
-            if (src + len > pay_len || o + len > isize) {
+            if (src + len > pay_len || over(o, len)) {
                 SEG_BAD();
                 break;
+            }
+            if constexpr (COUNT) {
+                o += len;
+                bp += 8u * len;
+                continue;
             }
             const uint8_t *sp = pay + src;
             uint8_t *dp = out + o;
@@ -838,7 +856,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
                 in_m += base_m;
             }
             const uint32_t new_bp = stop_ex;
-            if (o + tot_n > isize || new_bp > bit_end + (eob ? 0u : 64u)) {
+            if (over(o, tot_n) || new_bp > bit_end + (eob ? 0u : 64u)) {
                 SEG_BAD();
                 break;
             }
@@ -866,15 +884,19 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
                             SegSym y;
                             seg_sym<true>(h, win, rp, r_end, y);
                             if (y.e & kSegLit) {
-                                out[pos] = (uint8_t)y.lv;
-                                if (y.pair) out[pos + 1] = (uint8_t)y.val2;
+                                if constexpr (!COUNT) {
+                                    out[pos] = (uint8_t)y.lv;
+                                    if (y.pair) out[pos + 1] = (uint8_t)y.val2;
+                                }
                             } else if (y.e & kSegLen) {
                                 if (y.dist > pos || y.obad) bad_dist = true;
-                                LzMatch rec;
-                                rec.pos = pos;
-                                rec.len_dist = (y.lv << 16) | y.dist;
-                                ml[mi] = rec;
-                                mi++;
+                                if constexpr (!COUNT) {
+                                    LzMatch rec;
+                                    rec.pos = pos;
+                                    rec.len_dist = (y.lv << 16) | y.dist;
+                                    ml[mi] = rec;
+                                    mi++;
+                                }
                             } else if (!(y.e & kSegEob)) {
                                 bad_dist = true;  // an invalid codeword on the true path
                             }
@@ -892,6 +914,11 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
                         wave_sync();
                     }
                 }
+                // (COUNT has no caller's size to hold the sum against: what this walk from the true entry counted and
+                // where it ended is held against what pass 2 said of the lane -- entries chain from exit to exit, so a
+                // span that passes has been decoded symbol by symbol from its first bit to its last)
+                if constexpr (COUNT)
+                    if (live && (pos != o + in_n || rel0 + rp != ex)) bad_dist = true;
             }
             if (DBG) dbg[4] += (uint32_t)(clock64() - t_p3);
             if (W > 1 ? __syncthreads_or(bad_dist ? 1 : 0) != 0 : __ballot(bad_dist) != 0) {
@@ -909,13 +936,13 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
             __hip_atomic_store(hint_p, pm < 1u ? 1u : pm > 1000u ? 1000u : pm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (!bad && (o != isize || bp > bit_end)) SEG_BAD();
+    if (!bad && ((!COUNT && o != isize) || bp > bit_end)) SEG_BAD();
     if (bad) {
         seg_redo(blk, redo, b, tid);
     } else if (tid == 0) {
         blk->status = kInfOk;
         blk->produced = o;
-        blk->nmatch = mtot;
+        blk->nmatch = COUNT ? (bp - bit0 + 7u) >> 3 : mtot;
         if (multi) tf[(isize >> kLzTileShift) + 1] = mtot;
     }
     if (DBG && tid == 0) {
@@ -928,7 +955,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
 
 // The members are claimed from a ticket counter (redo[1 + nb]): the launch holds as many workgroups as the chip keeps
 // resident, and one that finishes a member takes the next -- 8,835 members on 4,096 wave slots are 2.16 member times, not three.
-template <bool DBG, int W>
+template <bool DBG, int W, bool COUNT = false>
 __global__ __launch_bounds__(64 * W, GZPX_SEG_WAVES) void k_inflate_seg(const uint8_t *__restrict__ in_all,
                                                                        DBlock *__restrict__ blk_all,
                                                                        const uint64_t *__restrict__ out_off, uint8_t *out_all,
@@ -945,7 +972,7 @@ __global__ __launch_bounds__(64 * W, GZPX_SEG_WAVES) void k_inflate_seg(const ui
         const uint32_t b = uniform(s_ticket);
         if (b >= nb) break;
         wave_sync();
-        seg_member<DBG, W>(b, tid, in_all, blk_all, out_off, out_all, out_cap, mlist_all, tfirst_all, redo, hint_p);
+        seg_member<DBG, W, COUNT>(b, tid, in_all, blk_all, out_off, out_all, out_cap, mlist_all, tfirst_all, redo, hint_p);
     }
 }
 

@@ -4949,7 +4949,11 @@ __global__ __launch_bounds__(256) void k_dscan(uint32_t nb, const DBlock *__rest
 #ifndef GZPX_INF_WAVES
 #define GZPX_INF_WAVES 5  // waves per SIMD k_inflate is compiled for (VGPR budget 512 / n)
 #endif
-template <bool DBG>
+// COUNT (gzpx_inflate_batch_sizes_device): the same walk with nothing stored and no match source read -- a DEFLATE
+// stream's length does not depend on its window.  isize is the cap on the member's output (kInfInsufficientSpace behind
+// it); what the wave leaves is the byte count in DBlock.produced and the payload bytes the stream took, through the byte
+// that holds the last bit of the final block, in DBlock.nmatch.  out_off / out_all / out_cap are not read.
+template <bool DBG, bool COUNT = false>
 __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *__restrict__ in_all, DBlock *__restrict__ blk_all,
                                                                 const uint64_t *__restrict__ out_off, uint8_t *out_all,
                                                                 uint64_t out_cap, const uint32_t *__restrict__ redo) {
@@ -4964,12 +4968,17 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
     DBlock *blk = blk_all + bidx;
     const uint32_t isize = blk->isize;
     if (isize == 0) return;  // src/par/decompress.rs:163-171: nothing to decode
-    const uint64_t ooff = out_off[bidx];
-    if (ooff + isize > out_cap) {
+    const uint64_t ooff = COUNT ? 0ull : out_off[bidx];
+    if (!COUNT && ooff + isize > out_cap) {
         if (lane == 0) blk->status = kInfInsufficientSpace;
         return;
     }
-    uint8_t *out = out_all + ooff;
+    uint8_t *out = out_all + ooff;  // (COUNT: null, and never used)
+    // does output [at, at + add) end behind isize?  (COUNT: the cap may be 0xFFFFFFFF, the sum needs 33 bits)
+    auto over = [&](uint32_t at, uint32_t add) -> bool {
+        if constexpr (COUNT) return (uint64_t)at + add > isize;
+        else return at + add > isize;
+    };
     const uint8_t *pay = in_all + blk->in_off + blk->pay_off;
     const uint32_t pay_len = blk->pay_len;
     const long long t_begin = DBG ? clock64() : 0;
@@ -5063,9 +5072,14 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
                 status = kInfBadData;
                 break;
             }
-            if (o + len > isize) {
+            if (over(o, len)) {
                 status = kInfInsufficientSpace;
                 break;
+            }
+            if constexpr (COUNT) {
+                o += len;
+                bp += 8u * len;
+                continue;
             }
             // straight from the payload to the output: head bytes up to a dword boundary of the
             // destination, then dwords (the source is read as aligned dword pairs), then the tail
@@ -5290,14 +5304,15 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
                     const uint32_t incl = wave_incl_add(mylen) + tout;
                     opos[hf] = incl - mylen;  // relative to o
                     tout = rdlane(incl, 63);
-                    bad_dist = bad_dist || (mine[hf] && is_match[hf] && (pack2[hf] & 0xFFFFu) > o + opos[hf]);
+                    if constexpr (COUNT) bad_dist = bad_dist || (mine[hf] && is_match[hf] && (uint64_t)(pack2[hf] & 0xFFFFu) > (uint64_t)o + opos[hf]);
+                    else bad_dist = bad_dist || (mine[hf] && is_match[hf] && (pack2[hf] & 0xFFFFu) > o + opos[hf]);
                     pack1[hf] = opos[hf] | ((le[hf] >> 8 & 0xFFu) << 16) | (is_match[hf] ? 1u << 24 : 0u);
                 }
                 if (__ballot(bad_dist)) {
                     status = kInfBadData;
                     break;
                 }
-                if (bp + 64 * kInfR > bit_end || o + tout > isize) {
+                if (bp + 64 * kInfR > bit_end || over(o, tout)) {
                     // The last round(s) of a member, or an overflow.  libdeflate's order of events: a
                     // symbol that starts past the limit above is BadData, one that does not fit the
                     // output is InsufficientSpace, and the earlier symbol decides (the bit reader's
@@ -5307,7 +5322,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
                     for (uint32_t hf = 0; hf < kInfR; hf++) {
                         const uint32_t q = bp + 64 * hf + lane;
                         const uint64_t mb = __ballot(mine[hf] && q >= bit_lim);
-                        const uint64_t mo = __ballot(mine[hf] && o + opos[hf] + outlen[hf] > isize);
+                        const uint64_t mo = __ballot(mine[hf] && over(o, opos[hf] + outlen[hf]));
                         if (mb && first_bad == 0xFFFFFFFFu) first_bad = 64 * hf + (uint32_t)__ffsll((long long)mb) - 1;
                         if (mo && first_ovf == 0xFFFFFFFFu) first_ovf = 64 * hf + (uint32_t)__ffsll((long long)mo) - 1;
                     }
@@ -5316,9 +5331,13 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
                         break;
                     }
                 }
-                if (o + tout > isize) {
+                if (over(o, tout)) {
                     status = kInfInsufficientSpace;
                     break;
+                }
+                if constexpr (COUNT) {  // the round's bytes are counted, and that is all there is to them
+                    o += tout;
+                    tout = 0;
                 }
                 // A round whose symbols are all literals (nearly every round of an incompressible member: configs[2]'s
                 // printable noise is literals of 7-8 bits, ~15 per round) needs no owners, no window and no order:
@@ -5326,7 +5345,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
                 bool any_match = false;
 #pragma unroll
                 for (uint32_t g = 0; g < kInfR; g++) any_match = any_match || (mine[g] && is_match[g]);
-                if (__ballot(any_match) == 0) {
+                if (!COUNT && __ballot(any_match) == 0) {
 #pragma unroll
                     for (uint32_t g = 0; g < kInfR; g++)
                         if (mine[g]) out[o + opos[g]] = (uint8_t)(le[g] >> 8);
@@ -5437,9 +5456,11 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
                     status = kInfInsufficientSpace;
                     break;
                 }
-                wave_sync();
-                if (lane == 0) win_store(o, e >> 8);
-                wave_sync();
+                if constexpr (!COUNT) {
+                    wave_sync();
+                    if (lane == 0) win_store(o, e >> 8);
+                    wave_sync();
+                }
                 o++;
                 bp += scl;
                 continue;
@@ -5466,9 +5487,13 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
                 status = kInfBadData;
                 break;
             }
-            if (o + len > isize) {
+            if (over(o, len)) {
                 status = kInfInsufficientSpace;
                 break;
+            }
+            if constexpr (COUNT) {
+                o += len;
+                continue;
             }
             // out[o + i] = out[o - dist + (i mod dist)]: every source byte is older than o
             wave_sync();
@@ -5493,13 +5518,15 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
     // libdeflate's final check (overread_count > bitsleft / 8): the stream "ended" inside the zero
     // padding behind a truncated payload -> BadData
     if (status == kInfOk && bp > bit_end) status = kInfBadData;
-    if (status == kInfOk && o != isize) status = kInfShortOutput;
-    // libdeflater hands back a zero-initialised Vec of orig_size bytes: a short block stays zero
-    for (uint32_t i = o + lane; i < isize; i += 64) out[i] = 0;
+    if constexpr (!COUNT) {
+        if (status == kInfOk && o != isize) status = kInfShortOutput;
+        // libdeflater hands back a zero-initialised Vec of orig_size bytes: a short block stays zero
+        for (uint32_t i = o + lane; i < isize; i += 64) out[i] = 0;
+    }
     if (lane == 0) {
         blk->status = status;
         blk->produced = o;
-        blk->nmatch = 0;
+        blk->nmatch = COUNT ? (bp - bit0 + 7u) >> 3 : 0u;
         if (DBG) {
             dbg[0] = (uint32_t)(clock64() - t_begin);
             for (uint32_t k = 0; k < 8; k++) blk->cyc[k] = dbg[k];
@@ -5838,6 +5865,54 @@ void launch_inflate_batch(int wrap, int short_ok, const uint8_t *d_in, uint64_t 
     hipLaunchKernelGGL(k_dresult, dim3(1), dim3(256), 0, stream, nb, (uint32_t)wrap, (uint32_t)(short_ok ? 1 : 0),
                        (const DBlock *)blk, (const uint32_t *)d_slot, (const uint32_t *)d_check, (const uint64_t *)d_out_off,
                        (WrapResult *)d_results, d_user_off, sc.summary);
+}
+
+// The sizes of a batch of members (gzpx_inflate_batch_sizes_device): the count-only forms of the inflate kernels between
+// k_dinit_wrap_sizes and k_dresult_sizes.  Nothing but the compressed bytes is read, and nothing written but the
+// records and the caller's tables: no output, no match list, no tile table (sc.mlist / sc.tfirst are not looked at).
+// The launch forms and their choice are launch_inflate_members_as's.
+template <bool DBG>
+static void launch_inflate_sizes_as(const uint8_t *d_in, uint32_t nb, DBlock *blk, hipStream_t stream, const InflateScratch &sc,
+                                    bool seg, hipEvent_t ev_mid) {
+    if (!seg) {
+        hipLaunchKernelGGL((k_inflate<DBG, true>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)nullptr,
+                           (uint8_t *)nullptr, 0ull, (const uint32_t *)nullptr);
+        return;
+    }
+    const bool big = nb && sc.in_bytes / nb >= kSegBigBytes;
+    const uint32_t seg_wgs = (uint32_t)(sc.n_cu > 0 ? sc.n_cu : 256) * 4u * GZPX_SEG_WAVES / (big ? (uint32_t)kSegBigW : (uint32_t)kSegSmallW);
+    const uint32_t seg_grid = nb < seg_wgs ? nb : seg_wgs;
+    uint32_t *seg_hint = sc.summary ? sc.summary + kDsSegHint : nullptr;
+    if (big)
+        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegBigW, true>), dim3(seg_grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
+                           (const uint64_t *)nullptr, (uint8_t *)nullptr, 0ull, (LzMatch *)nullptr, (uint32_t *)nullptr, sc.redo,
+                           nb, seg_hint);
+    else
+        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegSmallW, true>), dim3(seg_grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
+                           (const uint64_t *)nullptr, (uint8_t *)nullptr, 0ull, (LzMatch *)nullptr, (uint32_t *)nullptr, sc.redo,
+                           nb, seg_hint);
+    if (ev_mid) (void)hipEventRecord(ev_mid, stream);
+    hipLaunchKernelGGL((k_inflate<DBG, true>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)nullptr,
+                       (uint8_t *)nullptr, 0ull, (const uint32_t *)sc.redo);
+}
+
+void launch_inflate_sizes(int wrap, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
+                          uint32_t max_out, uint32_t nb, void *d_blk, int debug, hipEvent_t ev_begin, hipEvent_t ev_end,
+                          hipStream_t stream, const InflateScratch &sc, int route, uint32_t *d_out_sizes, uint32_t *d_in_used,
+                          void *d_results, hipEvent_t ev_mid) {
+    DBlock *blk = (DBlock *)d_blk;
+    const bool seg = route != kInflateRouteWave && sc.redo;
+    WrapTable t{d_in, in_len, d_offsets, d_sizes, nullptr, (uint32_t)wrap};
+    hipLaunchKernelGGL(k_dinit_wrap_sizes, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, t, max_out ? max_out : 0xFFFFFFFFu,
+                       blk, seg ? sc.redo : (uint32_t *)nullptr);
+    if (ev_begin) (void)hipEventRecord(ev_begin, stream);
+    if (debug)
+        launch_inflate_sizes_as<true>(d_in, nb, blk, stream, sc, seg, ev_mid);
+    else
+        launch_inflate_sizes_as<false>(d_in, nb, blk, stream, sc, seg, ev_mid);
+    if (ev_end) (void)hipEventRecord(ev_end, stream);
+    hipLaunchKernelGGL(k_dresult_sizes, dim3(1), dim3(256), 0, stream, nb, (uint32_t)wrap, (const DBlock *)blk, d_out_sizes,
+                       d_in_used, (WrapResult *)d_results, sc.summary);
 }
 
 // gzpx_adler32: (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]

@@ -1,6 +1,6 @@
 // gzpx_wrap.h -- batches of independent DEFLATE members in a wrapper of the caller's choice (raw RFC 1951, zlib
-// RFC 1950, gzip RFC 1952), for gzpx_inflate_batch_device.  Included from gzpx_kernels.hip, namespace gzpx, behind
-// k_inflate / k_inflate_seg / k_lzcopy, which do the inflating: what is here puts their records (DBlock) in place
+// RFC 1950, gzip RFC 1952), for gzpx_inflate_batch_device and gzpx_inflate_batch_sizes_device.  Included from
+// gzpx_kernels.hip, namespace gzpx, behind k_inflate / k_inflate_seg / k_lzcopy, which do the inflating: what is here puts their records (DBlock) in place
 // from a caller's table, checks what a wrapper carries, and reports per member.
 //
 //   k_dinit_wrap   one lane per member: the table entry against in_len, the wrapper's header, the trailer -> DBlock
@@ -13,6 +13,13 @@
 //   (k_dcrc32      gzip: as for BGZF; k_lzcopy's in-tile CRC serves too.  Raw: neither.)
 //   k_dresult      per-member status / produced / check values, the caller's offsets, and the record for the host
 //                  (kWrRec*, gzpx_device.h): first failing member, its status and two values, how many failed, the total.
+//
+// and for gzpx_inflate_batch_sizes_device, which inflates nothing and answers what every member inflates to:
+//   k_dinit_wrap_sizes   k_dinit_wrap's entry and header rules (one routine, dinit_wrap_member) for a member whose end is
+//                        not known: the payload runs to the end of the entry, no trailer is read, isize is the cap.
+//   (k_inflate_seg<.., COUNT> + k_inflate<.., COUNT> over its hand-backs, or the latter alone: launch_inflate_sizes)
+//   k_dresult_sizes      the member's length from where its stream ended, the trailer against the entry, the caller's
+//                        tables, and the same record with the 64-bit sum of the sizes.
 #pragma once
 
 // DBlock.status of a member that the wrapper kernels took out (never decoded; InflateStatus: gzpx_device.h, kInfRedo: gzpx_inflate_seg.h)
@@ -168,14 +175,15 @@ struct WrapTable {
     uint32_t wrap;
 };
 
-__global__ __launch_bounds__(256) void k_dinit_wrap(uint32_t nb, WrapTable t, DBlock *__restrict__ blk,
-                                                    uint32_t *__restrict__ slot, uint32_t *__restrict__ redo) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b == 0 && redo) {
-        redo[0] = 0;       // members handed back to k_inflate
-        redo[1 + nb] = 0;  // k_inflate_seg's ticket counter
-    }
-    if (b >= nb) return;
+// SIZES (gzpx_inflate_batch_sizes_device, k_dinit_wrap_sizes): the same entry and header rules for a member whose end
+// is not known.  size[b] is an upper bound; the payload runs from behind the header to the end of the entry (the
+// trailer's place is found behind the final block: k_dresult_sizes), no trailer is read, and isize is the cap on the
+// member's output, `max_out` -- never 0 for a member that is to be sized.  An entry's payload is cut at kWrapMaxPay
+// bytes: bit positions are 32-bit words in the kernels that follow.
+constexpr uint32_t kWrapMaxPay = 0x1FFFFF00u;
+template <bool SIZES>
+__device__ __forceinline__ void dinit_wrap_member(uint32_t b, const WrapTable &t, uint32_t max_out, DBlock *__restrict__ blk,
+                                                  uint32_t *__restrict__ slot) {
     const uint64_t off = t.off[b];
     const uint32_t sz = t.size[b];
     const uint32_t want = t.out_size ? t.out_size[b] : 0u;
@@ -191,21 +199,23 @@ __global__ __launch_bounds__(256) void k_dinit_wrap(uint32_t nb, WrapTable t, DB
     d.pay_off = 0;
     d.pay_len = 0;
     for (uint32_t k = 0; k < 8; k++) d.cyc[k] = 0;
-    uint32_t my_slot = want;
+    uint32_t my_slot = SIZES ? max_out : want;
     if (off > t.in_len || sz > t.in_len - off || sz < overhead) {
         d.status = kWrapArg;
     } else {
         const uint8_t *p = t.in + off;  // p[0, sz) is inside the input
         if (t.wrap == kWrapRaw) {
             d.pay_len = sz;
-            if (sz == 0 && want != 0) d.status = kInfBadData;  // (no final block; and nothing of such a member may be read)
+            if (sz == 0 && (SIZES || want != 0)) d.status = kInfBadData;  // (no final block; and nothing of such a member may be read)
         } else if (t.wrap == kWrapZlib) {
             const uint32_t cmf = p[0], flg = p[1];
             if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) d.status = kWrapHeader;
             d.pay_off = 2;
             d.pay_len = sz - 6u;
-            const uint8_t *f = p + sz - 4;  // Adler-32, big endian
-            d.crc = ((uint32_t)f[0] << 24) | ((uint32_t)f[1] << 16) | ((uint32_t)f[2] << 8) | (uint32_t)f[3];
+            if constexpr (!SIZES) {
+                const uint8_t *f = p + sz - 4;  // Adler-32, big endian
+                d.crc = ((uint32_t)f[0] << 24) | ((uint32_t)f[1] << 16) | ((uint32_t)f[2] << 8) | (uint32_t)f[3];
+            }
         } else {
             const uint32_t lim = sz - 8u;  // every header field ends in front of the trailer
             const uint32_t flg = p[3];
@@ -235,20 +245,49 @@ __global__ __launch_bounds__(256) void k_dinit_wrap(uint32_t nb, WrapTable t, DB
             }
             d.pay_off = pos;
             d.pay_len = lim - pos;
-            const uint8_t *f = p + lim;
-            d.crc = (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) | ((uint32_t)f[3] << 24);
-            const uint32_t isz = (uint32_t)f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) | ((uint32_t)f[7] << 24);
-            if (!t.out_size) {
-                my_slot = isz;
-            } else if (isz != want && d.status == kInfOk) {
-                d.status = kWrapSize;
-                d.crc = isz;
+            if constexpr (!SIZES) {
+                const uint8_t *f = p + lim;
+                d.crc = (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) | ((uint32_t)f[3] << 24);
+                const uint32_t isz = (uint32_t)f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) | ((uint32_t)f[7] << 24);
+                if (!t.out_size) {
+                    my_slot = isz;
+                } else if (isz != want && d.status == kInfOk) {
+                    d.status = kWrapSize;
+                    d.crc = isz;
+                }
             }
+        }
+        if constexpr (SIZES) {  // the payload: everything behind the header, as far as the entry goes
+            const uint32_t rest = sz - d.pay_off;
+            d.pay_len = rest < kWrapMaxPay ? rest : kWrapMaxPay;
+            d.size = d.pay_off + d.pay_len;
         }
     }
     if (d.status == kInfOk) d.isize = my_slot;
-    slot[b] = my_slot;
+    if constexpr (!SIZES) slot[b] = my_slot;
     blk[b] = d;
+}
+
+__global__ __launch_bounds__(256) void k_dinit_wrap(uint32_t nb, WrapTable t, DBlock *__restrict__ blk,
+                                                    uint32_t *__restrict__ slot, uint32_t *__restrict__ redo) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0 && redo) {
+        redo[0] = 0;       // members handed back to k_inflate
+        redo[1 + nb] = 0;  // k_inflate_seg's ticket counter
+    }
+    if (b >= nb) return;
+    dinit_wrap_member<false>(b, t, 0u, blk, slot);
+}
+
+__global__ __launch_bounds__(256) void k_dinit_wrap_sizes(uint32_t nb, WrapTable t, uint32_t max_out, DBlock *__restrict__ blk,
+                                                          uint32_t *__restrict__ redo) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0 && redo) {
+        redo[0] = 0;
+        redo[1 + nb] = 0;
+    }
+    if (b >= nb) return;
+    dinit_wrap_member<true>(b, t, max_out, blk, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_dscan_slots(uint32_t nb, const uint32_t *__restrict__ slot, DBlock *__restrict__ blk,
@@ -347,5 +386,84 @@ __global__ __launch_bounds__(256) void k_dresult(uint32_t nb, uint32_t wrap, uin
         rec[kWrRecTotal] = (uint32_t)total;
         rec[kWrRecTotal + 1] = (uint32_t)(total >> 32);
         if (user_off) user_off[nb] = total;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// gzpx_inflate_batch_sizes_device: what k_inflate_seg<.., COUNT> / k_inflate<.., COUNT> left in the records -> the
+// caller's tables.  A member's length is its header, the payload bytes its stream took and the trailer (0 / 4 / 8
+// bytes), and it has to end inside the entry: a stream whose trailer does not fit is as invalid as one that ends
+// early.  No trailer byte is read.  produced = the size, found = the member's length, for a good member; both 0 for a
+// failed one.  The total goes through the workgroup's 64-bit sum (k_dscan's loop), one pass over the members.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ WrapResult sizes_verdict(const DBlock &d, uint32_t wrap) {
+    WrapResult r{kWrOk, 0, 0, 0};
+    const uint32_t st = d.status;
+    if (st == kWrapArg) r.status = kWrInvalidArg;
+    else if (st == kWrapHeader) r.status = kWrInvalidHeader;
+    else if (st == kInfInsufficientSpace) r.status = kWrInsufficientSpace;
+    else if (st != kInfOk) r.status = kWrBadData;
+    else {
+        const uint64_t used = (uint64_t)d.pay_off + d.nmatch + (wrap == kWrapGzip ? 8u : wrap == kWrapZlib ? 4u : 0u);
+        if (used > d.size) {
+            r.status = kWrBadData;
+        } else {
+            r.produced = d.produced;
+            r.found = (uint32_t)used;
+        }
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k_dresult_sizes(uint32_t nb, uint32_t wrap, const DBlock *__restrict__ blk,
+                                                       uint32_t *__restrict__ out_sizes, uint32_t *__restrict__ in_used,
+                                                       WrapResult *__restrict__ results, uint32_t *__restrict__ rec) {
+    __shared__ uint64_t wsum[4];
+    __shared__ uint64_t carry_s;
+    __shared__ uint32_t first, failed;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        carry_s = 0;
+        first = 0xFFFFFFFFu;
+        failed = 0;
+    }
+    __syncthreads();
+    uint32_t my_first = 0xFFFFFFFFu, my_failed = 0;
+    for (uint32_t base = 0; base < nb; base += 256) {
+        const uint32_t b = base + tid;
+        uint64_t v = 0;
+        if (b < nb) {
+            const WrapResult r = sizes_verdict(blk[b], wrap);
+            out_sizes[b] = r.produced;
+            if (in_used) in_used[b] = r.found;
+            if (results) results[b] = r;
+            v = r.produced;
+            if (r.status != kWrOk) {
+                my_first = my_first < b ? my_first : b;
+                my_failed++;
+            }
+        }
+        uint64_t total;
+        (void)block_exclusive_scan256(v, wsum, &total);
+        if (tid == 0) carry_s += total;  // (thread 0 alone reads and writes it; the scan's barriers order the rest)
+    }
+    if (my_failed) {  // once per lane, not once per member
+        atomicMin(&first, my_first);
+        atomicAdd(&failed, my_failed);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t b = first;
+        WrapResult r{0, 0, 0, 0};
+        if (b != 0xFFFFFFFFu) r = sizes_verdict(blk[b], wrap);
+        const uint64_t total = carry_s;
+        rec[kWrRecFirst] = b;
+        rec[kWrRecStatus] = r.status;
+        rec[kWrRecFound] = 0;
+        rec[kWrRecExpected] = 0;
+        rec[kWrRecFailed] = failed;
+        rec[5] = 0;
+        rec[kWrRecTotal] = (uint32_t)total;
+        rec[kWrRecTotal + 1] = (uint32_t)(total >> 32);
     }
 }

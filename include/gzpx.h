@@ -436,6 +436,50 @@ int gzpx_inflate_batch_device(gzpx_dctx *ctx, int wrap, unsigned flags,
                               gzpx_member_result *d_results, /* DEVICE [n], optional: written */
                               size_t *out_len, size_t *n_failed, gzpx_check_info *info, void *hip_stream);
 int gzpx_dctx_last_check_ms(gzpx_dctx *ctx, float *ms);
+/* ---- the size query of such a batch: what every member inflates to and how long it is, for callers whose metadata
+ * is missing or untrusted (raw DEFLATE containers, PNG IDAT, zlib chunks) and for tables whose entries are not cut
+ * exactly.  The counterpart of libdeflate's *_decompress_ex with both actual_*_ret pointers, without an output buffer:
+ * the inflate kernels run in a count-only form that decodes the Huffman symbols and adds up lengths -- no literal is
+ * stored, no match source read, no byte of output written -- so the call reads the compressed bytes once and writes
+ * 4 to 24 bytes per member.
+ *   Context, lock, slot, hip_stream, "returns synchronised", n == 0 and n > 0xFFFFFFF0: as gzpx_inflate_batch_device.
+ *   Honours gzpx_dctx_set_route; both routes give the same answers.  Every table is a DEVICE array and none crosses to
+ *   the host; what comes back is one 32-byte record.  No output-sized scratch is allocated.
+ *   Extents: in_sizes[i] is an UPPER BOUND here.  Member i begins at in_offsets[i] and ends no later than
+ *   in_offsets[i] + in_sizes[i]; no byte behind that bound or behind in_len is read (bytes between the member's end
+ *   and the bound may be).  A bound that leaves more than 0x1FFFFF00 bytes behind the wrapper's header is cut there.
+ *   Per member, on success: out_sizes[i] = the exact number of bytes the DEFLATE stream inflates to; in_used[i] = the
+ *   member's length as libdeflate reports it in actual_in_nbytes_ret: the wrapper's header, the stream through the
+ *   byte that holds the last bit of the final block, and the trailer (RAW 0, ZLIB 4, GZIP 8 bytes);
+ *   d_results[i] = {GZPX_OK, out_size, in_used, 0}.
+ *   On failure out_sizes[i] = in_used[i] = 0 and d_results[i].status is the first that applies:
+ *     GZPX_ERR_INVALID_ARG         the entry leaves [0, in_len) or is shorter than its wrapper (ZLIB 6, GZIP 18)
+ *     GZPX_ERR_INVALID_HEADER      the ZLIB / GZIP header rules of gzpx_inflate_batch_device, FDICT included (a GZIP
+ *                                  header field has to end in front of the ENTRY's last 8 bytes)
+ *     GZPX_ERR_INSUFFICIENT_SPACE  the stream has more output than max_out_size (0: 0xFFFFFFFF): the guard against a
+ *                                  decompression bomb -- counting stops at the symbol that crosses the cap
+ *     GZPX_ERR_BAD_DATA            the stream is invalid by libdeflate's rules (a match that reaches in front of the
+ *                                  member's first byte included: the running count decides, no window is needed), or
+ *                                  the stream or its trailer does not end inside the entry
+ *   Checks: none.  No Adler-32 / CRC-32 is verified and ISIZE is not read -- there are no bytes to check; the inflate
+ *   call that follows verifies them.
+ *   Returns the first failing member's status with info->block = its index (found = expected = 0); *n_failed = how
+ *   many failed; *total_out = the sum of out_sizes, i.e. of the good members' sizes.
+ *   gzpx_dctx_last_inflate_ms (and _stage_ms: [0] the count-only k_inflate_seg, [1] the hand-backs) answer for this
+ *   call as for the batch call; gzpx_dctx_last_redo_count likewise.
+ *   Intended use: this call, then allocate *total_out bytes, then gzpx_inflate_batch_device with d_out_sizes as this
+ *   call wrote them -- and, if the table's entries were loose, with d_in_used as its d_in_sizes.  The second call is
+ *   unchanged: the fast route, Adler-32 / CRC-32 verified.  A member that failed here has a slot of 0 bytes there and
+ *   is not decoded; for RAW, which has no check, the second call then reports nothing about it (ZLIB / GZIP members
+ *   with in_used = 0 fail there as GZPX_ERR_INVALID_ARG): this call's results are where its failure is recorded. */
+int gzpx_inflate_batch_sizes_device(gzpx_dctx *ctx, int wrap,
+                                    const void *d_in, size_t in_len,
+                                    const uint64_t *d_in_offsets, const uint32_t *d_in_sizes, size_t n, /* DEVICE [n] */
+                                    uint32_t max_out_size,         /* cap per member; 0 = 0xFFFFFFFF */
+                                    uint32_t *d_out_sizes,         /* DEVICE [n], written */
+                                    uint32_t *d_in_used,           /* DEVICE [n], optional, written */
+                                    gzpx_member_result *d_results, /* DEVICE [n], optional, written */
+                                    uint64_t *total_out, size_t *n_failed, gzpx_check_info *info, void *hip_stream);
 typedef struct gzpx_decompressor gzpx_decompressor;
 gzpx_decompressor *gzpx_alloc_decompressor(void);
 /* 0 = ok (short output allowed, *actual = bytes produced), GZPX_ERR_BAD_DATA, GZPX_ERR_INSUFFICIENT_SPACE */

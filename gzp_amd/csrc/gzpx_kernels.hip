@@ -1148,7 +1148,9 @@ __global__ __launch_bounds__(kMpThreads, 8) void k_parse(
 //            every position it lands on; it keeps three 32-bit registers (token starts, "is a match",
 //            "the older candidate won") and its exit.  Entries are corrected round by round as in
 //            k_parse; a re-walk that lands on a token start of the previous walk has re-synchronised
-//            and keeps the rest of that walk (no second search).
+//            and keeps the rest of that walk (no second search).  Positions without a candidate
+//            (d0 == 0) are literals before anything is searched: one bit per position, built
+//            where the pass's d0 goes into LDS, lets a walk step over a run of them at once.
 //   phase 2  token / match counts per segment -> one workgroup scan.
 //   phase 3  sub-block boundaries (the first token with 8192 matches of the current sub-block before
 //            it: match ranks are known from the scan, every lane names its own candidate), then
@@ -1185,7 +1187,7 @@ __device__ __forceinline__ uint32_t l1_search(const uint32_t *in_w, const uint16
                                               uint32_t mis, bool &older, bool no_gather = false) {
     older = false;
     const uint32_t d0 = (!TAIL || p + 5 <= n) ? (uint32_t)d0_h[p - hb] : 0u;
-    if (!d0) return 0;
+    if (!d0) return 0;  // (the walks step over these positions; they ask under Config.debug bit 3 only)
     const uint32_t q = p - d0;  // the bucket's newer entry; the older one is ITS predecessor
     // (an LDS read for every lane and a masked global one for the few whose q lies before the pass.
     // Left alone, the compiler turns the two loads into ONE flat load of a selected pointer, which
@@ -1243,6 +1245,7 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
     __shared__ uint32_t in_w[kInWords];        // the block's bytes (+ lead misalignment, + pad)
     __shared__ uint32_t s_claimed;             // the block this workgroup takes after the next one
     __shared__ uint32_t d0_w[kMhHalf / 2];     // d0 (u16) of the positions of the current pass
+    __shared__ uint32_t nz_w[kMpThreads];      // "has a candidate", one bit per position of the pass: a dword per segment
     __shared__ uint32_t seg_exit[2 * kMpThreads];  // where the walk of segment s leaves it (two copies, see the rounds)
     __shared__ uint32_t wsum_t[kMpWaves];
     __shared__ unsigned long long bnd;  // (position << 32 | token index) of the sub-block boundary
@@ -1367,6 +1370,20 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
             dst[tid + kMpThreads] = d0v1;
             dst[tid + 2 * kMpThreads] = d0v2;
             dst[tid + 3 * kMpThreads] = d0v3;
+            // which of them have a candidate: one bit per position, the eight of a uint4 are one byte and the 32
+            // of a walk segment one aligned dword of nz_w (d0 <= 32767: adding 0x7fff carries into bit 15 of a
+            // non-zero half and never out of it)
+            auto nz8 = [](const uint4 &v) -> uint8_t {
+                const uint32_t k = 0x7fff7fffu, h = 0x80008000u;
+                const uint32_t a = (((v.x + k) & h) >> 15) | (((v.y + k) & h) >> 13) | (((v.z + k) & h) >> 11) |
+                                   (((v.w + k) & h) >> 9);  // bits 0, 2, 4, 6: the low halves; 16, 18, 20, 22: the high ones
+                return (uint8_t)(a | (a >> 15));
+            };
+            uint8_t *nz_b = (uint8_t *)nz_w;
+            nz_b[tid] = nz8(d0v0);
+            nz_b[tid + kMpThreads] = nz8(d0v1);
+            nz_b[tid + 2 * kMpThreads] = nz8(d0v2);
+            nz_b[tid + 3 * kMpThreads] = nz8(d0v3);
             // (uniform) the next pass's d0 -- this block's, or the next block's first -- travels while this pass is walked
             if (he < n) {
                 GZPX_D0_REQUEST(cand, he, n);
@@ -1386,16 +1403,34 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
         // (segments past the end exist only in the last pass, whose final token ends at n: that is
         // the "exit" the token build reads for them)
         uint32_t my_exit = active ? seg_begin : n;
-        bool have_old = false;
+        // Where the walk can stop: bit k = position seg_begin + k has a candidate (d0 != 0) and is searched at all
+        // (p + 5 <= n, the TAIL rule of l1_search).  Every other position is a literal whatever lies around it, so a
+        // walk steps over a run of them with one mask operation instead of one wave-step each (text: a fifth of
+        // the positions, two fifths of the first walk's lane-steps).  The bits behind a short last segment are set:
+        // a run that reaches them has left the segment.  Config.debug bit 3: all ones, a search at every position.
+        uint32_t nz = nz_w[tid];
+        {
+            const uint32_t n_srch = n - 4u > seg_begin ? n - 4u - seg_begin : 0u;  // searched positions from seg_begin on
+            if (n_srch < kMhSeg) nz &= (1u << n_srch) - 1u;
+            if (seg_end - seg_begin < kMhSeg) nz |= ~0u << (seg_end - seg_begin);  // (inactive lanes never walk)
+            if (cfg.debug & 8u) nz = ~0u;
+        }
         // (whole waves take the TAIL form of the search together: the last wave of the block)
         const bool tail_wave = __ballot(active && seg_end + 266u > n) != 0;
         auto walk_as = [&](uint32_t pos, auto tail_tag) {
             constexpr bool kTail = decltype(tail_tag)::value;
-            const uint32_t o_marks = marks, o_mbits = mbits, o_wbits = wbits;
+            const uint32_t o_marks = marks, o_mbits = mbits, o_wbits = wbits;  // (all zero before the first walk)
             marks = mbits = wbits = 0;
             while (pos < seg_end) {
-                const uint32_t bit = 1u << (pos - seg_begin);
-                if (have_old && (o_marks & bit)) {
+                // the run of candidate-less positions from pos on: literals, up to the next candidate or -- the
+                // sequential walk would have looked at each of them -- the next token start of the previous walk
+                const uint32_t from = ~0u << (pos - seg_begin);
+                const uint32_t stop = (nz | o_marks) & from;
+                const uint32_t bit = stop & (0u - stop);  // (0: the run reaches the end of a whole segment)
+                marks |= from & (bit - 1u);
+                pos = stop ? seg_begin + (uint32_t)__ffs((int)stop) - 1u : seg_end;
+                if (pos >= seg_end) break;
+                if (o_marks & bit) {
                     // landed on a token start of the previous walk: from here on the two walks are one
                     const uint32_t keep = ~(bit - 1u);
                     marks |= o_marks & keep;
@@ -1412,7 +1447,6 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
                 pos += len ? len : 1u;
             }
             my_exit = pos;
-            have_old = true;
         };
         auto walk = [&](uint32_t pos) {
             if (tail_wave) walk_as(pos, std::true_type{});

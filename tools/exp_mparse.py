@@ -1,6 +1,7 @@
 """What bounds k_mparse?  Second library with -DGZPX_EXPERIMENT (never the product build): cycles per
 phase (thread 0's clock, summed over blocks) and timing with parts switched off -- results wrong on purpose.
-   bit 13: walks without the cand[p - d0] gather      bit 14: without the token build"""
+   bit 13: walks without the cand[p - d0] gather      bit 14: without the token build
+   bit 3 (a product switch, results right): a search at every position, no step over candidate-less runs"""
 import ctypes
 import os
 import subprocess
@@ -26,7 +27,7 @@ d_out = torch.empty(cap, dtype=torch.uint8, device="cuda")
 ctx.set_profiling(True)
 nb = ctx.n_blocks(n)
 cyc = (ctypes.c_ulonglong * 8)()
-for name, flags in [("baseline", 0), ("no gather", 1 << 13), ("no token build", 1 << 14),
+for name, flags in [("baseline", 0), ("search everywhere", 1 << 3), ("no gather", 1 << 13), ("no token build", 1 << 14),
                     ("neither", (1 << 13) | (1 << 14))]:
     ctx.debug_set_flags(flags)
     acc = {}

@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ counters of the bench workloads (two passes of <= 8 SQ counters each; counters only with --kernel-trace)
+# SQ counters of the bench workloads (two passes of <= 8 SQ counters each, every pass a run of its own with no tracing option beside --pmc)
 #   tools/pmc_sq.sh <outdir-under-gpurun_out> ["<extra bench args>"]
 # prints the per-launch table and writes <outdir>/sq_counters.json (workload -> kernel -> counter, with the build id
 # of the library that ran); tools/summarize_profiles.py merges those into profiles/sq_counters.json, which
@@ -9,8 +9,8 @@ O=$R/gpurun_out/${1:-pmc_sq}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras $2"
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS -d $O/a -o a --output-format csv -- $B > $O/a.log 2>&1
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR -d $O/b -o b --output-format csv -- $B > $O/b.log 2>&1
+timeout -k 10 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS -d $O/a -o a --output-format csv -- $B > $O/a.log 2>&1 || { echo "stopped: $O/a.log"; exit 1; }
+timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR -d $O/b -o b --output-format csv -- $B > $O/b.log 2>&1 || { echo "stopped: $O/b.log"; exit 1; }
 python3 - <<PY
 import csv, glob, collections, json, sys
 sys.path.insert(0, "$R")

@@ -65,7 +65,7 @@ except FileNotFoundError:
 # size itself (it must read every byte once), so the x1.996 of the streaming kernels does not apply.
 uncorrected = {"k_crc32"}
 doc = {
-    "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py slab "
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py slab "
               "(compress workload; k_d*/k_inflate from --workload inflate)",
     "units": "bytes per launch (counter KiB x 1024)",
     "fetch_calibration_factor": round(cal, 3),
@@ -118,7 +118,7 @@ print("calibration factor", cal)
 
 # SQ counters (tools/pmc_sq.sh <dir> "<args>" writes gpurun_out/<dir>/sq_counters.json per workload): merged into
 # profiles/sq_counters.json, the source of bench.py's `roofline.issue` -- same build-id rule as the traffic file.
-sq = {"source": "rocprofv3 --kernel-trace --pmc <8 SQ counters> x 2 passes (tools/pmc_sq.sh), per LAUNCH; WAVE_CYCLES / "
+sq = {"source": "rocprofv3 --pmc <8 SQ counters> x 2 passes (tools/pmc_sq.sh), per LAUNCH; WAVE_CYCLES / "
                 "WAIT_* / ACTIVE_INST_* in quad-cycles, INSTS_* in wave-instructions",
       "round": tag, "build_id": doc["build_id"], "workloads": {}}
 import glob

@@ -67,7 +67,31 @@ uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
     return multmodp(x8n(len2), crc1) ^ crc2;
 }
 
+constexpr size_t kTrailerBytes = 8;  // CRC-32 + ISIZE behind a member's payload
+// BGZF's end-of-file marker, an empty member: header + the two bytes of an empty static block + trailer
+constexpr size_t kEofMarkerBytes = header_bytes(GZPX_FORMAT_BGZF) + 2 + kTrailerBytes;
+
+CrcConsts crc_consts() {
+    CrcConsts cc;
+    for (unsigned l = 0; l < 10; l++) cc.pow64[l] = x2k(9 + l);
+    cc.pow_tile = x2k(19);   // x^(8 * 65536) = x^(2^19)
+    cc.pow_small = x2k(17);  // x^(8 * 16384)
+    return cc;
+}
+
+// The stages of gzpx_ctx_last_stage_ms, in pipeline order (include/gzpx.h).  A Snap context fills kStMatch
+// (k_snap_chunk), kStScan (k_snap_frame + k_scan) and kStEmit (k_snap_emit).
+enum Stage : int { kStInitMeta, kStCandidates, kStMatch, kStParse, kStHist, kStHuffman, kStCrc32, kStScan, kStEmit, kNStages };
+static_assert(kNStages == GZPX_N_STAGES, "the stage enum and include/gzpx.h disagree");
+
 constexpr int kProfPairs = 64;  // launch groups of one batch that measurement mode can bracket
+// measurement mode: the timing events of a context and the groups of the batch enqueued last
+struct ProfLog {
+    Event ev[2 * kProfPairs];                // begin / end of launch groups
+    Stage stage[kProfPairs] = {};
+    int b[kProfPairs] = {0}, e[kProfPairs] = {0};  // a group's begin / end event (indices into ev)
+    int n = 0;
+};
 
 constexpr int kSlots = 3;  // slabs of one context that may be in flight (copy in / kernels / copy out)
 
@@ -154,7 +178,7 @@ struct Slot : NoCopy {
     // the job
     uint8_t *job_d_out = nullptr;  // where the kernels wrote
     size_t job_out_cap = 0;
-    uint8_t *host_out = nullptr;  // null: device job (output stays in HBM)
+    uint8_t *host_out = nullptr;  // null: nothing for wait to copy out (device job; a shard of the multi-device call)
     size_t host_out_cap = 0;
     uint64_t total_nb = 0;
     uint32_t n_batches = 0;
@@ -173,14 +197,11 @@ struct gzpx_ctx : NoCopy {
     Event ev_meta, ev_crc;        // fork / join of the side stream
     Event ev_crc_t0, ev_crc_t1;   // timing of k_crc32 when profiling
     Event ev_dep;  // "the caller's stream got this far" (device jobs)
-    Event prof_ev[2 * kProfPairs];  // measurement mode: begin / end of launch groups
-    int prof_stage[64] = {0};
-    int prof_b[64] = {0}, prof_e[64] = {0};  // a group's begin / end event (indices into prof_ev)
-    int prof_n = 0;
+    ProfLog prof;
     uint32_t batch_blocks = 0;
     Scratch scratch = {};
     SnapScratch snap = {};  // GZPX_FORMAT_SNAP only
-    BlockMeta *h_meta = nullptr;  // pinned; CRC-only contexts and the debug hooks
+    BlockMeta *h_meta = nullptr;  // pinned, one entry (debug hooks)
     SubMeta *h_sub = nullptr;     // pinned, max_sub entries (debug hooks)
     Allocs fixed;     // everything alloc_scratch allocates, but for ...
     Allocs lanes;     // ... scratch.no_*: the near-optimal lanes (retried with fewer of them)
@@ -188,7 +209,6 @@ struct gzpx_ctx : NoCopy {
     Slot slots[kSlots];
     uint64_t next_gen = 1;
     int profiling = 0;  // 0 off, 1 every stage, 2 the dominant stage only (two markers per batch instead of thirteen)
-    bool crc_only = false;
     float stage_ms[GZPX_N_STAGES] = {0};
     uint32_t last_nb = 0;
     char devname[256] = {0};
@@ -210,13 +230,11 @@ size_t snap_bound_per_block(size_t bs) { return 10 + bs + 8 * (size_t)snap_chunk
 
 size_t framed_bound_per_block(const gzpx_ctx *ctx) {
     if (ctx->cfg.format == GZPX_FORMAT_SNAP) return snap_bound_per_block(ctx->cfg.buffer_size);
-    return header_bytes(ctx->cfg.format) + ctx->cfg.buffer_size + extra_amount(ctx->cfg.buffer_size) + 8;
+    return header_bytes(ctx->cfg.format) + ctx->cfg.buffer_size + extra_amount(ctx->cfg.buffer_size) + kTrailerBytes;
 }
 
-uint64_t blocks_of(const gzpx_ctx *ctx, size_t in_len) {
-    const size_t bs = ctx->cfg.buffer_size;
-    return in_len == 0 ? 1 : (in_len + bs - 1) / bs;
-}
+// blocks a slab of in_len bytes is cut into (an empty slab is one empty block)
+uint64_t blocks_of(size_t bs, size_t in_len) { return in_len == 0 ? 1 : (in_len + bs - 1) / bs; }
 
 // bytes of device scratch one block needs (see gzpx_device.h Scratch)
 size_t scratch_bytes_per_block(const Config &c) {
@@ -245,10 +263,6 @@ int alloc_scratch(gzpx_ctx *ctx) {
         GZPX_TRY(a.dev(ss.coff, chunks * 4));
         GZPX_TRY(a.dev(s.out_off, (nb + 1) * sizeof(uint64_t)));
         GZPX_TRY(a.dev(s.sizes, nb * sizeof(uint32_t)));
-        return GZPX_OK;
-    }
-    if (ctx->crc_only) {  // gzpx_crc32's private context: k_init_meta + k_crc32 only
-        GZPX_TRY(a.pinned(ctx->h_meta, nb * sizeof(BlockMeta)));
         return GZPX_OK;
     }
     GZPX_TRY(a.pinned(ctx->h_meta, sizeof(BlockMeta)));
@@ -329,7 +343,7 @@ int ctx_acquire(gzpx_ctx *ctx) {
     GZPX_TRY(ctx->ev_crc_t1.create(true));
     GZPX_TRY(ctx->ev_dep.create());
     GZPX_TRY(alloc_scratch(ctx));
-    for (Event &e : ctx->prof_ev) GZPX_TRY(e.create(true));
+    for (Event &e : ctx->prof.ev) GZPX_TRY(e.create(true));
     return GZPX_OK;
 }
 
@@ -340,25 +354,34 @@ int ctx_acquire(gzpx_ctx *ctx) {
 // bench slab 0.08 ms.)
 struct ProfPairs {
     gzpx_ctx *ctx;
+    ProfLog &log;
     bool on;
     hipEvent_t dom_b = nullptr, dom_e = nullptr;  // mode 2, asynchronous: the job's own pair, read when it is waited for
     int used = 0;              // events handed out
     int last_ev = -1;          // the event recorded last ...
     hipStream_t last_st = nullptr;  // ... on this stream, with nothing enqueued behind it yet
-    int begin(int stage, hipStream_t st) {
-        if (!on || ctx->prof_n >= kProfPairs || used + 2 > 2 * kProfPairs) return -1;
-        if (ctx->profiling == 2 && stage != 2) return -1;
+    // a batch of the job in slot `sl` (which says whether the job carries the pair around its dominant stage)
+    ProfPairs(gzpx_ctx *c, const Slot &sl) : ctx(c), log(c->prof), on(c->profiling != 0) {
+        if (sl.dom_timed) {
+            dom_b = sl.ev_dom_b;
+            dom_e = sl.ev_dom_e;
+        }
+        log.n = 0;
+    }
+    int begin(Stage stage, hipStream_t st) {
+        if (!on || log.n >= kProfPairs || used + 2 > 2 * kProfPairs) return -1;
+        if (ctx->profiling == 2 && stage != kStMatch) return -1;
         if (dom_b) {
             (void)hipEventRecord(dom_b, st);
             return -2;
         }
-        const int i = ctx->prof_n++;
-        ctx->prof_stage[i] = stage;
+        const int i = log.n++;
+        log.stage[i] = stage;
         if (last_ev >= 0 && last_st == st) {
-            ctx->prof_b[i] = last_ev;
+            log.b[i] = last_ev;
         } else {
-            ctx->prof_b[i] = used++;
-            (void)hipEventRecord(ctx->prof_ev[ctx->prof_b[i]], st);
+            log.b[i] = used++;
+            (void)hipEventRecord(log.ev[log.b[i]], st);
         }
         last_ev = -1;
         return i;
@@ -366,76 +389,89 @@ struct ProfPairs {
     void end(int i, hipStream_t st) {
         if (i == -2) (void)hipEventRecord(dom_e, st);
         if (i < 0) return;
-        ctx->prof_e[i] = used++;
-        (void)hipEventRecord(ctx->prof_ev[ctx->prof_e[i]], st);
-        last_ev = ctx->prof_e[i];
+        log.e[i] = used++;
+        (void)hipEventRecord(log.ev[log.e[i]], st);
+        last_ev = log.e[i];
         last_st = st;
     }
     // something that is not part of a measured group went onto `st`: the next group records its own begin
     void touch(hipStream_t st) {
         if (last_st == st) last_ev = -1;
     }
+    // the batch is enqueued.  Measurement mode, unless the job carries its own pair: one host wait per batch
+    int finish(hipStream_t stream) {
+        if (!on || dom_b) return GZPX_OK;
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (int i = 0; i < log.n; i++) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, log.ev[log.b[i]], log.ev[log.e[i]]));
+            ctx->stage_ms[log.stage[i]] += ms;
+        }
+        return GZPX_OK;
+    }
 };
 
+// Where the CRC of every block forks onto the low-priority side stream (it needs only the input; k_emit joins it).
+// It is a question of whom it takes issue slots from (per 550 MiB step, round 3): beside k_mparse that kernel goes
+// from 2.01 to 2.07 ms and k_hist + k_huffman, alone now, from 0.41 to 0.33 -- 3.50 against 3.53 ms; forked behind
+// k_mparse (in front of the dense pair) 3.56.  (Round 2, beside the one-workgroup-per-block k_candidates: that kernel
+// slowed down by the CRC's time.)  Levels 2-12 fork BEHIND their match / parse kernels, beside k_hist / k_huffman
+// (round 6, tools/gpu_r6_fork_ab.sh: the one-workgroup-per-CU matchers lose more to the CRC's waves than the small
+// kernels do -- configs[2] 61.2-62.0 -> 60.7 ms, text at levels 2-9 0.04 ms each).
+enum CrcFork {
+    kForkBesideMatch,   // behind k_candidates
+    kForkBehindMparse,  // level 1: behind k_mparse / k_match, in front of k_parse
+    kForkBehindMatch,   // behind every match / parse kernel
+};
+// (Config.debug bits 8-9, experiments: 1 = behind all match / parse kernels, 2 = behind the first of them, which
+// levels 2-12 have only one group of, 3 = beside them whatever the level)
+CrcFork crc_fork_of(const Config &c) {
+    switch ((c.debug >> 8) & 3u) {
+    case 1: return kForkBehindMatch;
+    case 2: return c.level <= 1 ? kForkBehindMparse : kForkBehindMatch;
+    case 3: return kForkBesideMatch;
+    default: return c.level <= 1 ? kForkBesideMatch : kForkBehindMatch;
+    }
+}
+
 // One batch of blocks through the pipeline, enqueued on `stream`.  Nothing here waits for the device.
-// `prev` / `result`: the batch before this one of the same slab (device, may be null) and this
-// batch's own record; output offsets continue from prev->total.
-int enqueue_batch(gzpx_ctx *ctx, const uint8_t *d_in, size_t in_len, uint32_t nb, int is_last,
-                  uint8_t *d_out, size_t out_cap, hipStream_t stream, const SlabResult *prev,
-                  SlabResult *result, hipEvent_t dom_b = nullptr, hipEvent_t dom_e = nullptr) {
+// `sl`: the slot of the batch's job.  `prev` / `result`: the batch before this one of the same slab (device, may
+// be null) and this batch's own record; output offsets continue from prev->total.
+int enqueue_batch(gzpx_ctx *ctx, const Slot &sl, const uint8_t *d_in, size_t in_len, uint32_t nb, int is_last,
+                  uint8_t *d_out, size_t out_cap, hipStream_t stream, const SlabResult *prev, SlabResult *result) {
     const Config &c = ctx->dcfg;
     const Scratch &s = ctx->scratch;
-    ProfPairs pp{ctx, ctx->profiling != 0};
-    pp.dom_b = dom_b;
-    pp.dom_e = dom_e;
-    ctx->prof_n = 0;
-    // fork: the CRC of every block on the low-priority side stream, beside the match kernels.  Where it
-    // runs is a question of whom it takes issue slots from (per 550 MiB step, round 3): beside k_mparse
-    // that kernel goes from 2.01 to 2.07 ms and k_hist + k_huffman, alone now, from 0.41 to 0.33 -- 3.50
-    // against 3.53 ms; forked behind k_mparse (in front of the dense pair) 3.56.  (Round 2, beside the
-    // one-workgroup-per-block k_candidates: that kernel slowed down by the CRC's time.)
+    ProfPairs pp(ctx, sl);
     auto fork_crc = [&]() -> int {
         HIP_TRY(hipEventRecord(ctx->ev_meta, stream));
         HIP_TRY(hipStreamWaitEvent(ctx->s_side, ctx->ev_meta, 0));
         pp.touch(stream);
-        const int tc = pp.begin(6, ctx->s_side);
+        const int tc = pp.begin(kStCrc32, ctx->s_side);
         launch_crc32(c, d_in, in_len, nb, s, ctx->crc_consts, ctx->s_side);
         pp.end(tc, ctx->s_side);
         HIP_TRY(hipEventRecord(ctx->ev_crc, ctx->s_side));
         return GZPX_OK;
     };
-    // Levels 2-12 fork BEHIND their match / parse kernels, beside k_hist / k_huffman (round 6, tools/gpu_r6_fork_ab.sh: the
-    // one-workgroup-per-CU matchers lose more to the CRC's waves than the small kernels do -- configs[2] 61.2-62.0 ->
-    // 60.7 ms, text at levels 2-9 0.04 ms each).
-    // (Config.debug bits 8-9, experiments: 1 = fork behind all match / parse kernels, 2 = behind the first of them,
-    // 3 = beside them whatever the level)
-    const uint32_t fork_sel = (c.debug >> 8) & 3u;
-    const uint32_t fork_at = fork_sel == 0 ? (c.level <= 1 ? 1u : 0u) : fork_sel == 1 ? 0u : fork_sel == 2 ? 2u : 1u;
+    const CrcFork fork = crc_fork_of(c);
     // (the slab is cut into blocks -- BlockMeta -- by the first k_candidates launch; level 0: k_init_meta)
-    int t = pp.begin(c.level == 0 ? 0 : 1, stream);
+    int t = pp.begin(c.level == 0 ? kStInitMeta : kStCandidates, stream);
     launch_candidates(c, d_in, in_len, nb, is_last, s, stream);
     pp.end(t, stream);
-    if (fork_at == 1) {
-        const int rc = fork_crc();
-        if (rc != GZPX_OK) return rc;
-    }
+    if (fork == kForkBesideMatch) GZPX_TRY(fork_crc());
     if (c.level <= 1) {  // (at level 0 every block is a passthrough block: the kernels return at once)
         // (Tried in round 3: the batch cut into 2..8 block ranges, k_hist / k_huffman of range k on a
         // side stream beside the matching of range k + 1.  4.27 -> 4.83 / 5.90 / 7.44 ms per step: the
         // 24 six-KiB workgroups k_huffman puts on a CU take the LDS that k_candidates / k_mparse need
         // whole, so the big kernels lose CUs to the small one instead of sharing them.)
-        t = pp.begin(2, stream);
+        t = pp.begin(kStMatch, stream);
         launch_match(c, d_in, in_len, nb, s, stream);  // k_mparse, and k_match over the blocks it handed back
         pp.end(t, stream);
-        if (fork_at == 2) {
-            const int rc = fork_crc();
-            if (rc != GZPX_OK) return rc;
-        }
-        t = pp.begin(3, stream);
+        if (fork == kForkBehindMparse) GZPX_TRY(fork_crc());
+        t = pp.begin(kStParse, stream);
         launch_parse(c, d_in, in_len, nb, s, stream);
         pp.end(t, stream);
     } else {
-        t = pp.begin(2, stream);
+        t = pp.begin(kStMatch, stream);
         if (c.level >= 10) {  // levels 10-12: the near-optimal parser, one lane per block (gzpx_nearopt.hip)
             launch_near_optimal(c, d_in, nb, s, stream);
         } else if (c.lazy) {  // levels 5-9: every match variant once, then the serial-per-block lazy parse
@@ -448,73 +484,51 @@ int enqueue_batch(gzpx_ctx *ctx, const uint8_t *d_in, size_t in_len, uint32_t nb
         }
         pp.end(t, stream);
     }
-    if (fork_at == 0 || (fork_at == 2 && c.level > 1)) {
-        const int rc = fork_crc();
-        if (rc != GZPX_OK) return rc;
-    }
-    t = pp.begin(4, stream);
+    if (fork == kForkBehindMatch) GZPX_TRY(fork_crc());
+    t = pp.begin(kStHist, stream);
     launch_hist(c, nb, s, stream);
     pp.end(t, stream);
-    t = pp.begin(5, stream);
+    t = pp.begin(kStHuffman, stream);
     launch_huffman(c, nb, s, stream);
     pp.end(t, stream);
-    t = pp.begin(7, stream);
+    t = pp.begin(kStScan, stream);
     launch_scan(nb, s, prev, result, stream);
     pp.end(t, stream);
     // join behind k_scan (which does not read the CRCs): k_emit writes them into the footers
     HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_crc, 0));
     pp.touch(stream);  // (the wait for the side stream is nobody's stage time)
-    t = pp.begin(8, stream);
+    t = pp.begin(kStEmit, stream);
     launch_emit(c, d_in, in_len, nb, s, d_out, out_cap, stream);
     pp.end(t, stream);
     HIP_TRY(hipGetLastError());
-    if (pp.on && !dom_b) {  // measurement mode: one host wait per batch
-        HIP_TRY(hipStreamSynchronize(stream));
-        for (int i = 0; i < ctx->prof_n; i++) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->prof_ev[ctx->prof_b[i]], ctx->prof_ev[ctx->prof_e[i]]));
-            ctx->stage_ms[ctx->prof_stage[i]] += ms;
-        }
-    }
+    GZPX_TRY(pp.finish(stream));
     ctx->last_nb = nb;
     return GZPX_OK;
 }
 
 // Snap's batch (src/snap.rs:61-74, FrameEncoder over every buffer): k_snap_chunk (raw Snappy + CRC-32C of every
-// 64 KiB chunk), k_snap_frame + k_scan (framed sizes, offsets), k_snap_emit.  Stage slots: 2 = k_snap_chunk,
-// 7 = k_snap_frame + k_scan, 8 = k_snap_emit; the others stay 0.  Snap has no end-of-stream marker: is_last has no
-// effect.
-int enqueue_snap_batch(gzpx_ctx *ctx, const uint8_t *d_in, size_t in_len, uint32_t nb, uint8_t *d_out,
-                       size_t out_cap, hipStream_t stream, const SlabResult *prev, SlabResult *result,
-                       hipEvent_t dom_b = nullptr, hipEvent_t dom_e = nullptr) {
+// 64 KiB chunk), k_snap_frame + k_scan (framed sizes, offsets), k_snap_emit; the other stages stay 0.  Snap has no
+// end-of-stream marker: is_last has no effect.
+int enqueue_snap_batch(gzpx_ctx *ctx, const Slot &sl, const uint8_t *d_in, size_t in_len, uint32_t nb, uint8_t *d_out,
+                       size_t out_cap, hipStream_t stream, const SlabResult *prev, SlabResult *result) {
     const Scratch &s = ctx->scratch;
     const uint32_t bs = (uint32_t)ctx->cfg.buffer_size;
-    ProfPairs pp{ctx, ctx->profiling != 0};
-    pp.dom_b = dom_b;
-    pp.dom_e = dom_e;
-    ctx->prof_n = 0;
+    ProfPairs pp(ctx, sl);
     if (ctx->snap.dbg)
         HIP_TRY(hipMemsetAsync(ctx->snap.dbg, 0,
                                (size_t)nb * snap_chunks_per_buffer(bs) * 8 * sizeof(uint64_t), stream));
-    int t = pp.begin(2, stream);
+    int t = pp.begin(kStMatch, stream);
     launch_snap_chunk(d_in, in_len, bs, nb, ctx->snap, stream);
     pp.end(t, stream);
-    t = pp.begin(7, stream);
+    t = pp.begin(kStScan, stream);
     launch_snap_frame(in_len, bs, nb, s, ctx->snap, stream);
     launch_scan(nb, s, prev, result, stream);
     pp.end(t, stream);
-    t = pp.begin(8, stream);
+    t = pp.begin(kStEmit, stream);
     launch_snap_emit(d_in, in_len, bs, nb, s, ctx->snap, d_out, out_cap, stream);
     pp.end(t, stream);
     HIP_TRY(hipGetLastError());
-    if (pp.on && !dom_b) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        for (int i = 0; i < ctx->prof_n; i++) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->prof_ev[ctx->prof_b[i]], ctx->prof_ev[ctx->prof_e[i]]));
-            ctx->stage_ms[ctx->prof_stage[i]] += ms;
-        }
-    }
+    GZPX_TRY(pp.finish(stream));
     ctx->last_nb = nb;
     return GZPX_OK;
 }
@@ -535,6 +549,20 @@ int slot_staging(Slot &sl, size_t in_len, size_t out_need) {
                 [&](size_t cap) { return sl.out_mem.dev(sl.d_out, cap); });
 }
 
+// One slab to compress.  A host job goes through the slot's staging buffers and its stream is copied to `out` when
+// the ticket is waited for (the multi-device call, which learns every shard's place only then, leaves `out` null
+// and starts the copies itself); a device job works on the caller's buffers in HBM.
+struct SlabJob {
+    const uint8_t *in;
+    size_t in_len;
+    int mode;  // GZPX_SLAB_*
+    uint8_t *out;
+    size_t out_cap;
+    bool device;                  // in / out are device memory
+    hipStream_t after = nullptr;  // device jobs: the stream to order behind (order_behind)
+    bool wait_for_slot = false;   // every slot in flight: wait for one, instead of GZPX_ERR_BUSY
+};
+
 int check_slab_args(const gzpx_ctx *ctx, const void *in, size_t in_len, int mode, const void *out) {
     const size_t bs = ctx->cfg.buffer_size;
     if (mode != GZPX_SLAB_FULL_BLOCKS && mode != GZPX_SLAB_LAST && mode != GZPX_SLAB_FLUSH)
@@ -544,14 +572,11 @@ int check_slab_args(const gzpx_ctx *ctx, const void *in, size_t in_len, int mode
     return GZPX_OK;
 }
 
-// Enqueue one slab (ctx->mu held).  host_in / host_out non-null: a host-buffer job that goes
-// through the slot's staging buffers; otherwise d_in / d_out are the caller's device buffers.
-int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, size_t in_len, int mode,
-                   uint8_t *host_out, uint8_t *d_out, size_t out_cap, hipStream_t after, bool block_for_slot,
-                   std::unique_lock<std::mutex> &lk, uint64_t *ticket) {
-    if (ctx->crc_only) return GZPX_ERR_INVALID_ARG;
-    const size_t caller_cap = out_cap;  // (host jobs: out_cap becomes the staging buffer's below)
-    const int si = free_slot(ctx, lk, block_for_slot);
+// Enqueue one slab: lock, set device, take a slot, put the job's copies and kernels on the context's streams.
+int submit_enqueue(gzpx_ctx *ctx, const SlabJob &job, uint64_t *ticket) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(ctx, lk, job.wait_for_slot);
     if (si < 0) return GZPX_ERR_BUSY;
     Drain drain{{ctx->s_h2d, ctx->stream, ctx->s_side}, 3};  // (a failure leaves the slot free)
     Slot &sl = ctx->slots[si];
@@ -562,17 +587,18 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
         GZPX_TRY(sl.ev_dom_b.create(true));
         GZPX_TRY(sl.ev_dom_e.create(true));
     }
-    const size_t bs = ctx->cfg.buffer_size;
-    const uint64_t total_nb = blocks_of(ctx, in_len);
+    const size_t bs = ctx->cfg.buffer_size, in_len = job.in_len;
+    const uint64_t total_nb = blocks_of(bs, in_len);
     const uint64_t n_batches = (total_nb + ctx->batch_blocks - 1) / ctx->batch_blocks;
-    int rc = slot_reserve(sl, (size_t)n_batches, (size_t)total_nb);
-    if (rc != GZPX_OK) return rc;
+    GZPX_TRY(slot_reserve(sl, (size_t)n_batches, (size_t)total_nb));
     hipStream_t stream = ctx->stream;
-    if (host_out) {
-        rc = slot_staging(sl, in_len, gzpx_slab_bound(ctx, in_len));
-        if (rc != GZPX_OK) return rc;
+    const uint8_t *d_in = job.in;  // where the kernels read and write, and how much they may write
+    uint8_t *d_out = job.out;
+    size_t out_cap = job.out_cap;
+    if (!job.device) {
+        GZPX_TRY(slot_staging(sl, in_len, gzpx_slab_bound(ctx, in_len)));
         if (in_len) {
-            HIP_TRY(hipMemcpyAsync(sl.d_in, host_in, in_len, hipMemcpyHostToDevice, ctx->s_h2d));
+            HIP_TRY(hipMemcpyAsync(sl.d_in, job.in, in_len, hipMemcpyHostToDevice, ctx->s_h2d));
             HIP_TRY(hipEventRecord(sl.ev_h2d, ctx->s_h2d));
             HIP_TRY(hipStreamWaitEvent(stream, sl.ev_h2d, 0));
         }
@@ -580,14 +606,13 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
         d_out = sl.d_out;
         out_cap = sl.d_out_cap;
     } else {
-        GZPX_TRY(order_behind(stream, after, ctx->ev_dep));
+        GZPX_TRY(order_behind(stream, job.after, ctx->ev_dep));
     }
     memset(ctx->stage_ms, 0, sizeof(ctx->stage_ms));
     // profiling mode 2 on a one-batch slab: the job carries its own pair of events around the dominant stage and
     // stays asynchronous (the pair is read when the ticket is waited for); every other measurement waits per batch
     sl.dom_timed = ctx->profiling == 2 && n_batches == 1;
-    const hipEvent_t dom_b = sl.dom_timed ? sl.ev_dom_b.h : nullptr, dom_e = sl.dom_timed ? sl.ev_dom_e.h : nullptr;
-    const int is_last = mode == GZPX_SLAB_LAST;
+    const int is_last = job.mode == GZPX_SLAB_LAST;
     for (uint64_t bi = 0; bi < n_batches; bi++) {
         const uint64_t b0 = bi * ctx->batch_blocks;
         const uint32_t nb = (uint32_t)((total_nb - b0 < ctx->batch_blocks) ? total_nb - b0 : ctx->batch_blocks);
@@ -595,13 +620,12 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
         size_t in_batch = in_len > in_begin ? in_len - in_begin : 0;
         if (in_batch > (size_t)nb * bs) in_batch = (size_t)nb * bs;
         const int last_batch = (b0 + nb == total_nb) ? is_last : 0;
+        const SlabResult *prev = bi ? sl.d_results + (bi - 1) : nullptr;
         if (ctx->cfg.format == GZPX_FORMAT_SNAP)
-            rc = enqueue_snap_batch(ctx, d_in + in_begin, in_batch, nb, d_out, out_cap, stream,
-                                    bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi, dom_b, dom_e);
+            GZPX_TRY(enqueue_snap_batch(ctx, sl, d_in + in_begin, in_batch, nb, d_out, out_cap, stream, prev, sl.d_results + bi));
         else
-            rc = enqueue_batch(ctx, d_in + in_begin, in_batch, nb, last_batch, d_out, out_cap, stream,
-                               bi ? sl.d_results + (bi - 1) : nullptr, sl.d_results + bi, dom_b, dom_e);
-        if (rc != GZPX_OK) return rc;
+            GZPX_TRY(enqueue_batch(ctx, sl, d_in + in_begin, in_batch, nb, last_batch, d_out, out_cap, stream, prev,
+                                   sl.d_results + bi));
         // the per-block sizes of this batch, before the next batch reuses the scratch
         HIP_TRY(hipMemcpyAsync(sl.h_sizes + b0, ctx->scratch.sizes, nb * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                stream));
@@ -611,8 +635,8 @@ int submit_enqueue(gzpx_ctx *ctx, const uint8_t *host_in, const uint8_t *d_in, s
     HIP_TRY(hipEventRecord(sl.ev_kernels, stream));
     sl.job_d_out = d_out;
     sl.job_out_cap = out_cap;
-    sl.host_out = host_out;
-    sl.host_out_cap = host_out ? caller_cap : 0;
+    sl.host_out = job.device ? nullptr : job.out;
+    sl.host_out_cap = job.device ? 0 : job.out_cap;
     sl.total_nb = total_nb;
     sl.n_batches = (uint32_t)n_batches;
     *ticket = issue_ticket(ctx, si);
@@ -639,7 +663,7 @@ Completion kernels_done(gzpx_ctx *ctx, Slot &sl) {
         float ms = 0;
         std::lock_guard<std::mutex> lk(ctx->mu);  // (a submit on another thread clears stage_ms under this lock)
         memset(ctx->stage_ms, 0, sizeof(ctx->stage_ms));
-        if (hipEventElapsedTime(&ms, sl.ev_dom_b, sl.ev_dom_e) == hipSuccess) ctx->stage_ms[2] = ms;
+        if (hipEventElapsedTime(&ms, sl.ev_dom_b, sl.ev_dom_e) == hipSuccess) ctx->stage_ms[kStMatch] = ms;
         sl.dom_timed = false;
     }
     for (uint32_t bi = 0; bi < sl.n_batches && c.rc == GZPX_OK; bi++) {
@@ -704,7 +728,189 @@ int wait_ticket(gzpx_ctx *ctx, uint64_t ticket, size_t *out_len, uint32_t *block
     return rc;
 }
 
-int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out);
+// the four single-context entry points: check, submit
+int submit_checked(gzpx_ctx *ctx, const SlabJob &job, uint64_t *ticket) {
+    if (!ctx || !ticket) return GZPX_ERR_INVALID_ARG;
+    GZPX_TRY(check_slab_args(ctx, job.in, job.in_len, job.mode, job.out));
+    return submit_enqueue(ctx, job, ticket);
+}
+
+// ... of which the two run forms wait for a slot, and then for the job
+int run_checked(gzpx_ctx *ctx, SlabJob job, size_t *out_len, uint32_t *block_sizes, size_t max_blocks, size_t *n_blocks) {
+    if (!ctx || !out_len) return GZPX_ERR_INVALID_ARG;
+    if (block_sizes && max_blocks < blocks_of(ctx->cfg.buffer_size, job.in_len)) return GZPX_ERR_INVALID_ARG;
+    uint64_t ticket = 0;
+    job.wait_for_slot = true;
+    GZPX_TRY(submit_checked(ctx, job, &ticket));
+    return wait_ticket(ctx, ticket, out_len, block_sizes, max_blocks, n_blocks);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------- multi-device slab call
+// SURVEY 8(b) "multi-device variant", 8(e): blocks share no state, so a slab shards into contiguous
+// block ranges, one per device, balanced to one block; only the range that holds the slab's end is
+// cut with the caller's mode (short final piece / EOF marker).  Every device runs the single-device
+// pipeline on its range -- no data-path exchange between them -- and the in-order write-out is done
+// on the host side of the boundary: once the shard sizes are known (16 bytes per device), every
+// device copies its shard straight to its offset in `out`, all copies in flight together, each
+// over its own PCIe link.  (The one-process-per-GPU form of the same split, with the shards
+// gathered over RCCL, is gzp_amd/shard.py + bench.py --gpus N.)
+struct gzpx_multi {
+    std::vector<gzpx_ctx *> ctxs;
+    size_t buffer_size = 0;
+    std::mutex mu;
+    // device-resident form: every device's own output staging (its shard before the gather)
+    struct Stage {
+        uint8_t *d = nullptr;
+        size_t cap = 0;
+        Allocs mem;
+    };
+    std::unique_ptr<Stage[]> stage;  // one per device
+};
+
+namespace {
+
+// the block range of device g of G when a slab of in_len bytes is cut (contiguous, balanced to one block)
+struct MultiPart {
+    uint64_t first = 0, nb = 0;
+    size_t lo = 0, n = 0;
+};
+void multi_part_of(size_t in_len, size_t bs, size_t G, size_t g, MultiPart &p) {
+    const uint64_t total_nb = blocks_of(bs, in_len);
+    p = MultiPart();
+    for (size_t k = 0; k <= g; k++) {
+        p.first += p.nb;
+        p.nb = total_nb / G + (k < total_nb % G ? 1 : 0);
+    }
+    p.lo = (size_t)(p.first * bs < in_len ? p.first * bs : in_len);
+    const size_t hi = (size_t)((p.first + p.nb) * bs < in_len ? (p.first + p.nb) * bs : in_len);
+    p.n = hi - p.lo;
+}
+
+// One slab over the devices of `m`, the sequence both forms of the call share.  They differ in what a device submits
+// -- `job_of(g, range, job)` fills in device g's job, with nothing of that device's enqueued yet -- and in how a
+// shard travels to its place once the sizes are known: `start_copy(g, slot, offset, produced)`.
+template <class JobOf, class StartCopy>
+int multi_compress(gzpx_multi *m, size_t in_len, int mode, size_t out_cap, size_t *out_len, uint32_t *block_sizes,
+                   size_t max_blocks, size_t *n_blocks, JobOf &&job_of, StartCopy &&start_copy) {
+    std::lock_guard<std::mutex> guard(m->mu);
+    const size_t bs = m->buffer_size, G = m->ctxs.size();
+    const uint64_t total_nb = blocks_of(bs, in_len);
+    if (block_sizes && max_blocks < total_nb) return GZPX_ERR_INVALID_ARG;
+    struct Part {
+        MultiPart r;
+        uint64_t ticket = 0;
+        Slot *slot = nullptr;
+        Completion c;
+        bool submitted = false;
+    };
+    std::vector<Part> parts(G);
+    int rc = GZPX_OK;
+    // 1. every device: copy-in (host form) + kernels of its range; the devices work concurrently.  Only the range
+    // that holds the slab's end is cut with the caller's mode.
+    for (size_t g = 0; g < G && rc == GZPX_OK; g++) {
+        Part &p = parts[g];
+        multi_part_of(in_len, bs, G, g, p.r);
+        if (p.r.nb == 0) continue;
+        SlabJob job{nullptr, p.r.n, p.r.first + p.r.nb == total_nb ? mode : GZPX_SLAB_FULL_BLOCKS, nullptr, 0, false};
+        job.wait_for_slot = true;
+        rc = job_of(g, p.r, job);
+        if (rc == GZPX_OK) rc = submit_enqueue(m->ctxs[g], job, &p.ticket);
+        p.submitted = rc == GZPX_OK;
+    }
+    // 2. shard sizes (a 16-byte record per device) -> stream offsets
+    size_t fail_block = (size_t)total_nb;
+    for (size_t g = 0; g < G; g++) {
+        Part &p = parts[g];
+        if (!p.submitted) continue;
+        const int si = claim_ticket(m->ctxs[g], p.ticket);
+        if (si < 0) {
+            if (rc == GZPX_OK) rc = GZPX_ERR_DEVICE;
+            p.submitted = false;
+            continue;
+        }
+        p.slot = &m->ctxs[g]->slots[si];
+        p.c = kernels_done(m->ctxs[g], *p.slot);
+        if (p.c.rc != GZPX_OK && rc == GZPX_OK) {  // the first failing block in stream order
+            rc = p.c.rc;
+            fail_block = (size_t)p.r.first + p.c.blocks_done;
+        }
+    }
+    size_t total = 0;
+    std::vector<size_t> offs(G, 0);
+    for (size_t g = 0; g < G; g++) {
+        offs[g] = total;
+        if (parts[g].submitted) total += parts[g].c.produced;
+    }
+    if (rc == GZPX_OK && total > out_cap) rc = GZPX_ERR_INSUFFICIENT_SPACE;
+    // 3. the ordered gather: every shard straight into its place, all copies started; 4. all copies finished
+    for (size_t g = 0; g < G && rc == GZPX_OK; g++)
+        if (parts[g].submitted && parts[g].c.produced) rc = start_copy(g, *parts[g].slot, offs[g], parts[g].c.produced);
+    for (size_t g = 0; g < G; g++) {
+        Part &p = parts[g];
+        if (!p.submitted) continue;
+        const int r2 = finish_copy_out(m->ctxs[g], *p.slot, p.c.produced);
+        if (rc == GZPX_OK) rc = r2;
+        if (rc == GZPX_OK && block_sizes)
+            memcpy(block_sizes + p.r.first, p.slot->h_sizes, (size_t)p.r.nb * sizeof(uint32_t));
+        release_slot(m->ctxs[g], *p.slot);
+    }
+    *out_len = rc == GZPX_OK ? total : 0;
+    if (n_blocks) *n_blocks = rc == GZPX_OK ? (size_t)total_nb : fail_block;
+    return rc;
+}
+
+constexpr size_t kCheckChunk = (size_t)64 << 20, kCheckTiles = kCheckChunk / kTile;  // a checksum call's unit of work
+
+// The process-lifetime state behind gzpx_crc32 / gzpx_adler32 (device 0; the caller holds the state's mutex): the
+// stream and the buffers of every call, made by the first one, whole or not at all -- a call that fails to make them
+// leaves nothing behind and the next one tries again -- and never deleted: no HIP call at process exit.
+template <class State>
+int checksum_state(State *&state) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GZPX_ERR_NO_DEVICE;
+    if (hipSetDevice(0) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (state) return GZPX_OK;
+    std::unique_ptr<State> fresh(new (std::nothrow) State());
+    if (!fresh) return GZPX_ERR_DEVICE;
+    GZPX_TRY(fresh->init());
+    state = fresh.release();
+    return GZPX_OK;
+}
+
+// gzpx_crc32: k_init_meta cuts a chunk into 64 KiB tiles, k_crc32 takes one tile per workgroup
+struct CrcState {
+    Stream stream;
+    Config cfg = {};       // (the two kernels read block_size alone)
+    Scratch scratch = {};  // ... and meta: the tiles' BlockMeta
+    CrcConsts cc;
+    BlockMeta *h_meta = nullptr;  // pinned mirror
+    Allocs mem;
+    uint8_t *d_in = nullptr;  // staging, grown on demand
+    size_t d_in_cap = 0;
+    Allocs in_mem;
+    int init() {
+        cfg.block_size = kTile;
+        cc = crc_consts();
+        GZPX_TRY(stream.create());
+        GZPX_TRY(mem.dev(scratch.meta, kCheckTiles * sizeof(BlockMeta)));
+        return mem.pinned(h_meta, kCheckTiles * sizeof(BlockMeta));
+    }
+};
+
+struct AdlerState {
+    Stream stream;
+    uint8_t *d_in = nullptr;
+    uint32_t *d_out3 = nullptr, *h_out3 = nullptr;
+    Allocs mem;
+    int init() {
+        GZPX_TRY(stream.create());
+        GZPX_TRY(mem.dev(d_in, kCheckChunk));
+        GZPX_TRY(mem.dev(d_out3, kCheckTiles * 12));
+        return mem.pinned(h_out3, kCheckTiles * 12);
+    }
+};
 
 }  // namespace
 
@@ -722,18 +928,11 @@ void gzpx_config_default(gzpx_config *cfg, int format) {
     cfg->max_slab_bytes = (size_t)1 << 30;
 }
 
-int gzpx_ctx_create(const gzpx_config *cfg, gzpx_ctx **out) { return ctx_create(cfg, false, out); }
-
-}  // extern "C"
-
-namespace {
-
-int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
+int gzpx_ctx_create(const gzpx_config *cfg, gzpx_ctx **out) {
     if (!cfg || !out) return GZPX_ERR_INVALID_ARG;
     *out = nullptr;
     const bool snap = cfg->format == GZPX_FORMAT_SNAP;
-    if (cfg->format != GZPX_FORMAT_BGZF && cfg->format != GZPX_FORMAT_MGZIP && !(snap && !crc_only))
-        return GZPX_ERR_INVALID_ARG;
+    if (cfg->format != GZPX_FORMAT_BGZF && cfg->format != GZPX_FORMAT_MGZIP && !snap) return GZPX_ERR_INVALID_ARG;
     if (cfg->buffer_size < kDictSize) return GZPX_ERR_BUFFER_SIZE;  // src/par/compress.rs:68-74
     // (Snap ignores the level and has no libdeflate rules, src/snap.rs:53-59, 91)
     if (!snap && (cfg->level < 0 || cfg->level > 12)) return GZPX_ERR_COMPRESSION_LEVEL;
@@ -748,7 +947,6 @@ int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
     gzpx_ctx *ctx = new (std::nothrow) gzpx_ctx();
     if (!ctx) return GZPX_ERR_DEVICE;
     ctx->cfg = *cfg;
-    ctx->crc_only = crc_only;
     ctx->dcfg.format = (uint32_t)cfg->format;
     // (a Snap context runs none of the deflate kernels: its level and compat are kept as given and ignored)
     const int lvl = snap ? 0 : cfg->level, cmp = snap ? GZPX_COMPAT_LIBDEFLATE_1_24 : cfg->compat;
@@ -784,24 +982,17 @@ int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
         ctx->dcfg.lazy = lvl >= 10 ? 0u : lvl >= 8 ? 2u : lvl >= 5 ? 1u : 0u;
         ctx->dcfg.no_passes = lvl >= 10 ? (uint32_t)lvl - 8u : 0u;
     }
-    for (unsigned l = 0; l < 10; l++) ctx->crc_consts.pow64[l] = x2k(9 + l);
-    ctx->crc_consts.pow_tile = x2k(19);  // x^(8 * 65536) = x^(2^19)
-    ctx->crc_consts.pow_small = x2k(17);  // x^(8 * 16384)
+    ctx->crc_consts = crc_consts();
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) {
         snprintf(ctx->devname, sizeof(ctx->devname), "%.150s (%.60s, %d CUs)", prop.name, prop.gcnArchName,
                  prop.multiProcessorCount);
         ctx->dcfg.n_cu = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 0u;
     }
-    const uint64_t want = blocks_of(ctx, cfg->max_slab_bytes ? cfg->max_slab_bytes : 1);
+    const uint64_t want = blocks_of(cfg->buffer_size, cfg->max_slab_bytes ? cfg->max_slab_bytes : 1);
     ctx->batch_blocks = (uint32_t)(want < kMaxBatchBlocks ? want : kMaxBatchBlocks);
-    if (snap) {
-        const size_t fit = kMaxScratchBytes / snap_scratch_bytes_per_block(cfg->buffer_size);
-        if (ctx->batch_blocks > fit) ctx->batch_blocks = (uint32_t)fit;
-    } else if (!crc_only) {
-        const size_t fit = kMaxScratchBytes / scratch_bytes_per_block(ctx->dcfg);
-        if (ctx->batch_blocks > fit) ctx->batch_blocks = (uint32_t)fit;
-    }
+    const size_t fit = kMaxScratchBytes / (snap ? snap_scratch_bytes_per_block(cfg->buffer_size) : scratch_bytes_per_block(ctx->dcfg));
+    if (ctx->batch_blocks > fit) ctx->batch_blocks = (uint32_t)fit;
     if (ctx->batch_blocks == 0) ctx->batch_blocks = 1;
     const int rc = ctx_acquire(ctx);
     if (rc != GZPX_OK) {
@@ -811,10 +1002,6 @@ int ctx_create(const gzpx_config *cfg, bool crc_only, gzpx_ctx **out) {
     *out = ctx;
     return GZPX_OK;
 }
-
-}  // namespace
-
-extern "C" {
 
 void gzpx_ctx_destroy(gzpx_ctx *ctx) {
     if (!ctx) return;
@@ -830,29 +1017,19 @@ int gzpx_ctx_active_compat(const gzpx_ctx *ctx) {
 
 size_t gzpx_slab_bound(const gzpx_ctx *ctx, size_t in_len) {
     if (!ctx) return 0;
-    if (ctx->cfg.format == GZPX_FORMAT_SNAP) return (size_t)blocks_of(ctx, in_len) * framed_bound_per_block(ctx);
-    return (size_t)blocks_of(ctx, in_len) * framed_bound_per_block(ctx) + 28 + 64;
+    const size_t blocks = (size_t)blocks_of(ctx->cfg.buffer_size, in_len) * framed_bound_per_block(ctx);
+    return ctx->cfg.format == GZPX_FORMAT_SNAP ? blocks : blocks + kEofMarkerBytes + 64;
 }
 
 int gzpx_compress_slab_submit(gzpx_ctx *ctx, const uint8_t *in, size_t in_len, int mode, uint8_t *out,
                               size_t out_cap, uint64_t *ticket) {
-    if (!ctx || !ticket) return GZPX_ERR_INVALID_ARG;
-    int rc = check_slab_args(ctx, in, in_len, mode, out);
-    if (rc != GZPX_OK) return rc;
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-    return submit_enqueue(ctx, in, nullptr, in_len, mode, out, nullptr, out_cap, nullptr, false, lk, ticket);
+    return submit_checked(ctx, {in, in_len, mode, out, out_cap, false}, ticket);
 }
 
 int gzpx_compress_slab_submit_device(gzpx_ctx *ctx, const void *d_in, size_t in_len, int mode, void *d_out,
                                      size_t out_cap, void *after_stream, uint64_t *ticket) {
-    if (!ctx || !ticket) return GZPX_ERR_INVALID_ARG;
-    int rc = check_slab_args(ctx, d_in, in_len, mode, d_out);
-    if (rc != GZPX_OK) return rc;
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-    return submit_enqueue(ctx, nullptr, (const uint8_t *)d_in, in_len, mode, nullptr, (uint8_t *)d_out, out_cap,
-                          (hipStream_t)after_stream, false, lk, ticket);
+    return submit_checked(ctx, {(const uint8_t *)d_in, in_len, mode, (uint8_t *)d_out, out_cap, true, (hipStream_t)after_stream},
+                          ticket);
 }
 
 int gzpx_compress_slab_wait(gzpx_ctx *ctx, uint64_t ticket, size_t *out_len, uint32_t *block_sizes,
@@ -873,36 +1050,14 @@ int gzpx_compress_slab_event(gzpx_ctx *ctx, uint64_t ticket, void **hip_event) {
 int gzpx_compress_slab_device(gzpx_ctx *ctx, const void *d_in, size_t in_len, int mode,
                               void *d_out, size_t out_cap, size_t *out_len, uint32_t *block_sizes,
                               size_t max_blocks, size_t *n_blocks, void *hip_stream) {
-    if (!ctx || !out_len) return GZPX_ERR_INVALID_ARG;
-    int rc = check_slab_args(ctx, d_in, in_len, mode, d_out);
-    if (rc != GZPX_OK) return rc;
-    if (block_sizes && max_blocks < blocks_of(ctx, in_len)) return GZPX_ERR_INVALID_ARG;
-    uint64_t ticket = 0;
-    {
-        std::unique_lock<std::mutex> lk(ctx->mu);
-        if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-        rc = submit_enqueue(ctx, nullptr, (const uint8_t *)d_in, in_len, mode, nullptr, (uint8_t *)d_out, out_cap,
-                            (hipStream_t)hip_stream, true, lk, &ticket);
-    }
-    if (rc != GZPX_OK) return rc;
-    return wait_ticket(ctx, ticket, out_len, block_sizes, max_blocks, n_blocks);
+    return run_checked(ctx, {(const uint8_t *)d_in, in_len, mode, (uint8_t *)d_out, out_cap, true, (hipStream_t)hip_stream},
+                       out_len, block_sizes, max_blocks, n_blocks);
 }
 
 int gzpx_compress_slab(gzpx_ctx *ctx, const uint8_t *in, size_t in_len, int mode, uint8_t *out,
                        size_t out_cap, size_t *out_len, uint32_t *block_sizes, size_t max_blocks,
                        size_t *n_blocks) {
-    if (!ctx || !out_len) return GZPX_ERR_INVALID_ARG;
-    int rc = check_slab_args(ctx, in, in_len, mode, out);
-    if (rc != GZPX_OK) return rc;
-    if (block_sizes && max_blocks < blocks_of(ctx, in_len)) return GZPX_ERR_INVALID_ARG;
-    uint64_t ticket = 0;
-    {
-        std::unique_lock<std::mutex> lk(ctx->mu);
-        if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-        rc = submit_enqueue(ctx, in, nullptr, in_len, mode, out, nullptr, out_cap, nullptr, true, lk, &ticket);
-    }
-    if (rc != GZPX_OK) return rc;
-    return wait_ticket(ctx, ticket, out_len, block_sizes, max_blocks, n_blocks);
+    return run_checked(ctx, {in, in_len, mode, out, out_cap, false}, out_len, block_sizes, max_blocks, n_blocks);
 }
 
 int gzpx_encode_block(gzpx_ctx *ctx, const uint8_t *in, size_t n, int is_last, uint8_t *out,
@@ -921,47 +1076,6 @@ int gzpx_encode_block(gzpx_ctx *ctx, const uint8_t *in, size_t n, int is_last, u
     *out_len = got;
     return GZPX_OK;
 }
-
-// ---------------------------------------------------------------- multi-device slab call
-// SURVEY 8(b) "multi-device variant", 8(e): blocks share no state, so a slab shards into contiguous
-// block ranges, one per device, balanced to one block; only the range that holds the slab's end is
-// cut with the caller's mode (short final piece / EOF marker).  Every device runs the single-device
-// pipeline on its range -- no data-path exchange between them -- and the in-order write-out is done
-// on the host side of the boundary: once the shard sizes are known (16 bytes per device), every
-// device copies its shard straight to its offset in `out`, all copies in flight together, each
-// over its own PCIe link.  (The one-process-per-GPU form of the same split, with the shards
-// gathered over RCCL, is gzp_amd/shard.py + bench.py --gpus N.)
-struct gzpx_multi {
-    std::vector<gzpx_ctx *> ctxs;
-    size_t buffer_size = 0;
-    std::mutex mu;
-    // device-resident form: every device's own output staging (its shard before the gather)
-    struct Stage {
-        uint8_t *d = nullptr;
-        size_t cap = 0;
-        Allocs mem;
-    };
-    std::unique_ptr<Stage[]> stage;  // one per device
-};
-
-namespace {
-// the block range of device g of G when a slab of in_len bytes is cut (contiguous, balanced to one block)
-struct MultiPart {
-    uint64_t first = 0, nb = 0;
-    size_t lo = 0, n = 0;
-};
-void multi_part_of(size_t in_len, size_t bs, size_t G, size_t g, MultiPart &p) {
-    const uint64_t total_nb = in_len == 0 ? 1 : (in_len + bs - 1) / bs;
-    p = MultiPart();
-    for (size_t k = 0; k <= g; k++) {
-        p.first += p.nb;
-        p.nb = total_nb / G + (k < total_nb % G ? 1 : 0);
-    }
-    p.lo = (size_t)(p.first * bs < in_len ? p.first * bs : in_len);
-    const size_t hi = (size_t)((p.first + p.nb) * bs < in_len ? (p.first + p.nb) * bs : in_len);
-    p.n = hi - p.lo;
-}
-}  // namespace
 
 int gzpx_multi_create(const gzpx_config *cfg, const int *devices, size_t n_devices, gzpx_multi **out) {
     if (!cfg || !devices || !n_devices || !out) return GZPX_ERR_INVALID_ARG;
@@ -1020,190 +1134,57 @@ int gzpx_multi_shard(const gzpx_multi *m, size_t in_len, size_t g, size_t *offse
 
 // The device-resident form: north_star's write-out.  Range g of the slab already lives on device g
 // (d_in[g]); every device compresses its range into its own staging buffer, the host learns the shard
-// sizes (a 16-byte record per device) and each shard then travels ONCE, device to device, into its
-// stream offset of `d_out` on devices[root] -- hipMemcpyPeerAsync on the owning device's copy stream,
-// all peers at once (every peer has its own xGMI link to the root); the root's own shard is a local
-// copy.  No payload byte touches host memory.  In-order property: src/par/compress.rs:305-310.
+// sizes and each shard then travels ONCE, device to device, into its stream offset of `d_out` on
+// devices[root] -- hipMemcpyPeerAsync on the owning device's copy stream, all peers at once (every peer
+// has its own xGMI link to the root); the root's own shard is a local copy.  No payload byte touches
+// host memory.  In-order property: src/par/compress.rs:305-310.
 int gzpx_multi_compress_slab_device(gzpx_multi *m, const void *const *d_in, size_t in_len, int mode, size_t root,
                                     void *d_out, size_t out_cap, size_t *out_len, uint32_t *block_sizes,
                                     size_t max_blocks, size_t *n_blocks) {
     if (!m || !out_len || m->ctxs.empty() || !d_in || !d_out || root >= m->ctxs.size()) return GZPX_ERR_INVALID_ARG;
-    if (mode != GZPX_SLAB_FULL_BLOCKS && mode != GZPX_SLAB_LAST && mode != GZPX_SLAB_FLUSH) return GZPX_ERR_INVALID_ARG;
-    const size_t bs = m->buffer_size, G = m->ctxs.size();
-    if (mode == GZPX_SLAB_FULL_BLOCKS && (in_len == 0 || in_len % bs != 0)) return GZPX_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> guard(m->mu);
-    const uint64_t total_nb = in_len == 0 ? 1 : (in_len + bs - 1) / bs;
-    if (block_sizes && max_blocks < total_nb) return GZPX_ERR_INVALID_ARG;
-    struct Part {
-        MultiPart r;
-        uint64_t ticket = 0;
-        Slot *slot = nullptr;
-        Completion c;
-        bool submitted = false;
-    };
-    std::vector<Part> parts(G);
-    int rc = GZPX_OK;
-    // 1. every device: the kernels of its range, output into its own staging (devices work concurrently)
-    for (size_t g = 0; g < G && rc == GZPX_OK; g++) {
-        Part &p = parts[g];
-        multi_part_of(in_len, bs, G, g, p.r);
-        if (p.r.nb == 0) continue;
-        if (p.r.n && !d_in[g]) {
-            rc = GZPX_ERR_INVALID_ARG;
-            break;
-        }
-        const bool owns_end = p.r.first + p.r.nb == total_nb;
-        gzpx_ctx *ctx = m->ctxs[g];
-        std::unique_lock<std::mutex> lk(ctx->mu);
-        if (hipSetDevice(ctx->cfg.device) != hipSuccess) {
-            rc = GZPX_ERR_DEVICE;
-            break;
-        }
-        const size_t need = gzpx_slab_bound(ctx, p.r.n);
-        gzpx_multi::Stage &st = m->stage[g];
-        rc = grow(st.mem, st.cap, need, need + need / 8 + 4096, [&](size_t cap) { return st.mem.dev(st.d, cap); });
-        if (rc != GZPX_OK) break;
-        rc = submit_enqueue(ctx, nullptr, (const uint8_t *)d_in[g], p.r.n, owns_end ? mode : GZPX_SLAB_FULL_BLOCKS, nullptr,
-                            st.d, st.cap, (hipStream_t)GZPX_STREAM_NONE, true, lk, &p.ticket);  // (the caller's contract: the ranges are ready)
-        p.submitted = rc == GZPX_OK;
-    }
-    // 2. shard sizes -> stream offsets
-    size_t fail_block = (size_t)total_nb;
-    for (size_t g = 0; g < G; g++) {
-        Part &p = parts[g];
-        if (!p.submitted) continue;
-        const int si = claim_ticket(m->ctxs[g], p.ticket);
-        if (si < 0) {
-            if (rc == GZPX_OK) rc = GZPX_ERR_DEVICE;
-            p.submitted = false;
-            continue;
-        }
-        p.slot = &m->ctxs[g]->slots[si];
-        p.c = kernels_done(m->ctxs[g], *p.slot);
-        if (p.c.rc != GZPX_OK && rc == GZPX_OK) {  // the first failing block in stream order
-            rc = p.c.rc;
-            fail_block = (size_t)p.r.first + p.c.blocks_done;
-        }
-    }
-    size_t total = 0;
-    std::vector<size_t> offs(G, 0);
-    for (size_t g = 0; g < G; g++) {
-        offs[g] = total;
-        if (parts[g].submitted) total += parts[g].c.produced;
-    }
-    if (rc == GZPX_OK && total > out_cap) rc = GZPX_ERR_INSUFFICIENT_SPACE;
-    // 3. the ordered gather: every shard straight into its place on the root device, all at once
+    GZPX_TRY(check_slab_args(m->ctxs[0], d_in, in_len, mode, d_out));
     const int root_dev = m->ctxs[root]->cfg.device;
-    for (size_t g = 0; g < G && rc == GZPX_OK; g++) {
-        Part &p = parts[g];
-        if (!p.submitted || !p.c.produced) continue;
-        gzpx_ctx *ctx = m->ctxs[g];
-        if (hipSetDevice(ctx->cfg.device) != hipSuccess ||
-            hipMemcpyPeerAsync((uint8_t *)d_out + offs[g], root_dev, m->stage[g].d, ctx->cfg.device, p.c.produced,
-                               ctx->s_d2h) != hipSuccess ||
-            hipEventRecord(p.slot->ev_d2h, ctx->s_d2h) != hipSuccess)
-            rc = GZPX_ERR_DEVICE;
-    }
-    for (size_t g = 0; g < G; g++) {
-        Part &p = parts[g];
-        if (!p.submitted) continue;
-        const int r2 = finish_copy_out(m->ctxs[g], *p.slot, p.c.produced);
-        if (rc == GZPX_OK) rc = r2;
-        if (rc == GZPX_OK && block_sizes)
-            memcpy(block_sizes + p.r.first, p.slot->h_sizes, (size_t)p.r.nb * sizeof(uint32_t));
-        release_slot(m->ctxs[g], *p.slot);
-    }
-    *out_len = rc == GZPX_OK ? total : 0;
-    if (n_blocks) *n_blocks = rc == GZPX_OK ? (size_t)total_nb : fail_block;
-    return rc;
+    return multi_compress(
+        m, in_len, mode, out_cap, out_len, block_sizes, max_blocks, n_blocks,
+        [&](size_t g, const MultiPart &r, SlabJob &job) -> int {
+            if (r.n && !d_in[g]) return GZPX_ERR_INVALID_ARG;
+            if (hipSetDevice(m->ctxs[g]->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
+            const size_t need = gzpx_slab_bound(m->ctxs[g], r.n);
+            gzpx_multi::Stage &st = m->stage[g];
+            GZPX_TRY(grow(st.mem, st.cap, need, need + need / 8 + 4096, [&](size_t cap) { return st.mem.dev(st.d, cap); }));
+            job.in = (const uint8_t *)d_in[g];
+            job.out = st.d;
+            job.out_cap = st.cap;
+            job.device = true;
+            job.after = (hipStream_t)GZPX_STREAM_NONE;  // (the caller's contract: the ranges are ready)
+            return GZPX_OK;
+        },
+        [&](size_t g, Slot &sl, size_t off, size_t produced) -> int {
+            gzpx_ctx *ctx = m->ctxs[g];
+            if (hipSetDevice(ctx->cfg.device) != hipSuccess ||
+                hipMemcpyPeerAsync((uint8_t *)d_out + off, root_dev, m->stage[g].d, ctx->cfg.device, produced, ctx->s_d2h) !=
+                    hipSuccess ||
+                hipEventRecord(sl.ev_d2h, ctx->s_d2h) != hipSuccess)
+                return GZPX_ERR_DEVICE;
+            return GZPX_OK;
+        });
 }
 
 size_t gzpx_multi_devices(const gzpx_multi *m) { return m ? m->ctxs.size() : 0; }
 
+// The host form: every device copies its shard straight to its offset in `out`, each over its own PCIe link.
 int gzpx_multi_compress_slab(gzpx_multi *m, const uint8_t *in, size_t in_len, int mode, uint8_t *out,
                              size_t out_cap, size_t *out_len, uint32_t *block_sizes, size_t max_blocks,
                              size_t *n_blocks) {
     if (!m || !out_len || m->ctxs.empty()) return GZPX_ERR_INVALID_ARG;
-    int rc = check_slab_args(m->ctxs[0], in, in_len, mode, out);
-    if (rc != GZPX_OK) return rc;
-    std::lock_guard<std::mutex> guard(m->mu);
-    const size_t bs = m->buffer_size, G = m->ctxs.size();
-    const uint64_t total_nb = in_len == 0 ? 1 : (in_len + bs - 1) / bs;
-    if (block_sizes && max_blocks < total_nb) return GZPX_ERR_INVALID_ARG;
-    struct Part {
-        uint64_t first = 0, nb = 0;
-        size_t lo = 0, n = 0;
-        uint64_t ticket = 0;
-        Slot *slot = nullptr;
-        Completion c;
-        bool submitted = false;
-    };
-    std::vector<Part> parts(G);
-    uint64_t first = 0;
-    for (size_t g = 0; g < G; g++) {  // contiguous ranges, balanced to within one block
-        Part &p = parts[g];
-        p.first = first;
-        p.nb = total_nb / G + (g < total_nb % G ? 1 : 0);
-        first += p.nb;
-        p.lo = (size_t)(p.first * bs < in_len ? p.first * bs : in_len);
-        const size_t hi = (size_t)((p.first + p.nb) * bs < in_len ? (p.first + p.nb) * bs : in_len);
-        p.n = hi - p.lo;
-    }
-    // 1. every device: copy-in + kernels of its range (devices work concurrently)
-    for (size_t g = 0; g < G && rc == GZPX_OK; g++) {
-        Part &p = parts[g];
-        if (p.nb == 0) continue;
-        const bool owns_end = p.first + p.nb == total_nb;
-        gzpx_ctx *ctx = m->ctxs[g];
-        std::unique_lock<std::mutex> lk(ctx->mu);
-        if (hipSetDevice(ctx->cfg.device) != hipSuccess) {
-            rc = GZPX_ERR_DEVICE;
-            break;
-        }
-        // (`out` is only a placeholder here: the real destination is known after the sizes are)
-        rc = submit_enqueue(ctx, in + p.lo, nullptr, p.n, owns_end ? mode : GZPX_SLAB_FULL_BLOCKS, out, nullptr, 0, nullptr,
-                            true, lk, &p.ticket);
-        p.submitted = rc == GZPX_OK;
-    }
-    // 2. sizes -> offsets; 3. all copies started; 4. all copies finished
-    size_t fail_block = (size_t)total_nb;
-    for (size_t g = 0; g < G; g++) {
-        Part &p = parts[g];
-        if (!p.submitted) continue;
-        const int si = claim_ticket(m->ctxs[g], p.ticket);
-        if (si < 0) {
-            if (rc == GZPX_OK) rc = GZPX_ERR_DEVICE;
-            p.submitted = false;
-            continue;
-        }
-        p.slot = &m->ctxs[g]->slots[si];
-        p.c = kernels_done(m->ctxs[g], *p.slot);
-        if (p.c.rc != GZPX_OK && rc == GZPX_OK) {  // the first failing block in stream order
-            rc = p.c.rc;
-            fail_block = (size_t)p.first + p.c.blocks_done;
-        }
-    }
-    size_t total = 0;
-    std::vector<size_t> offs(G, 0);
-    for (size_t g = 0; g < G; g++) {
-        offs[g] = total;
-        if (parts[g].submitted) total += parts[g].c.produced;
-    }
-    if (rc == GZPX_OK && total > out_cap) rc = GZPX_ERR_INSUFFICIENT_SPACE;
-    for (size_t g = 0; g < G && rc == GZPX_OK; g++)
-        if (parts[g].submitted) rc = start_copy_out(m->ctxs[g], *parts[g].slot, out + offs[g], parts[g].c.produced);
-    for (size_t g = 0; g < G; g++) {
-        Part &p = parts[g];
-        if (!p.submitted) continue;
-        const int r2 = finish_copy_out(m->ctxs[g], *p.slot, p.c.produced);
-        if (rc == GZPX_OK) rc = r2;
-        if (rc == GZPX_OK && block_sizes)
-            memcpy(block_sizes + p.first, p.slot->h_sizes, (size_t)p.nb * sizeof(uint32_t));
-        release_slot(m->ctxs[g], *p.slot);
-    }
-    *out_len = rc == GZPX_OK ? total : 0;
-    if (n_blocks) *n_blocks = rc == GZPX_OK ? (size_t)total_nb : fail_block;
-    return rc;
+    GZPX_TRY(check_slab_args(m->ctxs[0], in, in_len, mode, out));
+    return multi_compress(
+        m, in_len, mode, out_cap, out_len, block_sizes, max_blocks, n_blocks,
+        [&](size_t, const MultiPart &r, SlabJob &job) -> int {
+            job.in = in + r.lo;  // (the stream stays in the slot's staging: its place in `out` is known after the sizes are)
+            return GZPX_OK;
+        },
+        [&](size_t g, Slot &sl, size_t off, size_t produced) { return start_copy_out(m->ctxs[g], sl, out + off, produced); });
 }
 
 // ---------------------------------------------------------------- libdeflate-shaped ABI
@@ -1254,9 +1235,9 @@ size_t gzpx_deflate_compress(gzpx_compressor *c, const void *in, size_t n, void 
     if (gzpx_compress_slab(c->ctx, (const uint8_t *)in, n, GZPX_SLAB_LAST, c->tmp.data(), c->tmp.size(),
                            &got, nullptr, 0, &nb) != GZPX_OK)
         return 0;
-    const size_t payload = got - 20 - 8;
+    const size_t hdr = header_bytes(c->ctx->dcfg.format), payload = got - hdr - kTrailerBytes;
     if (payload > cap) return 0;  // libdeflate: 0 when the output does not fit
-    memcpy(out, c->tmp.data() + 20, payload);
+    memcpy(out, c->tmp.data() + hdr, payload);
     return payload;
 }
 
@@ -1279,37 +1260,24 @@ void gzpx_free_compressor(gzpx_compressor *c) {
 int gzpx_crc32_checked(uint32_t crc, const void *buf, size_t n, uint32_t *out) {
     // libdeflate_crc32 semantics: crc32(crc, buf) = combine(crc, crc32(0, buf), n)
     static std::mutex mu;
-    static gzpx_ctx *ctx = nullptr;
+    static CrcState *state = nullptr;
     if (!out || (!buf && n)) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(mu);
-    if (!ctx) {
-        gzpx_config cfg;
-        gzpx_config_default(&cfg, GZPX_FORMAT_MGZIP);
-        cfg.level = 1;
-        cfg.buffer_size = kTile;
-        cfg.max_slab_bytes = (size_t)64 << 20;
-        const int rc = ctx_create(&cfg, true, &ctx);  // k_init_meta + k_crc32 only: no compressor scratch
-        if (rc != GZPX_OK) return rc;
-    }
+    GZPX_TRY(checksum_state(state));
     *out = crc;
-    if (n == 0) return GZPX_OK;
-    std::lock_guard<std::mutex> lock2(ctx->mu);
-    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
-    Slot &sl = ctx->slots[0];  // staging only
+    CrcState &st = *state;
     const uint8_t *p = (const uint8_t *)buf;
-    const size_t slab_max = (size_t)ctx->batch_blocks * kTile;
     while (n) {
-        const size_t take = n < slab_max ? n : slab_max;
-        int rc = slot_staging(sl, take, 0);
-        if (rc != GZPX_OK) return rc;
+        const size_t take = n < kCheckChunk ? n : kCheckChunk;
+        GZPX_TRY(grow(st.in_mem, st.d_in_cap, take + 16, take + take / 8 + 4096,
+                      [&](size_t cap) { return st.in_mem.dev(st.d_in, cap); }));
         const uint32_t nb = (uint32_t)((take + kTile - 1) / kTile);
-        HIP_TRY(hipMemcpyAsync(sl.d_in, p, take, hipMemcpyHostToDevice, ctx->stream));
-        launch_init_meta(ctx->dcfg, take, nb, 0, ctx->scratch, ctx->stream);
-        launch_crc32(ctx->dcfg, sl.d_in, take, nb, ctx->scratch, ctx->crc_consts, ctx->stream);
-        HIP_TRY(hipMemcpyAsync(ctx->h_meta, ctx->scratch.meta, nb * sizeof(BlockMeta), hipMemcpyDeviceToHost,
-                               ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (uint32_t b = 0; b < nb; b++) crc = crc32_combine(crc, ctx->h_meta[b].crc, ctx->h_meta[b].n);
+        HIP_TRY(hipMemcpyAsync(st.d_in, p, take, hipMemcpyHostToDevice, st.stream));
+        launch_init_meta(st.cfg, take, nb, 0, st.scratch, st.stream);
+        launch_crc32(st.cfg, st.d_in, take, nb, st.scratch, st.cc, st.stream);
+        HIP_TRY(hipMemcpyAsync(st.h_meta, st.scratch.meta, nb * sizeof(BlockMeta), hipMemcpyDeviceToHost, st.stream));
+        HIP_TRY(hipStreamSynchronize(st.stream));
+        for (uint32_t b = 0; b < nb; b++) crc = crc32_combine(crc, st.h_meta[b].crc, st.h_meta[b].n);
         p += take;
         n -= take;
     }
@@ -1346,36 +1314,13 @@ uint32_t gzpx_adler32_combine(uint32_t adler1, uint32_t adler2, uint64_t len2) {
 }
 
 int gzpx_adler32_checked(uint32_t adler, const void *buf, size_t n, uint32_t *out) {
-    constexpr size_t kChunk = (size_t)64 << 20, kTiles = kChunk / 65536;
-    // the stream and the buffers of every call, made by the first one: whole or not at all (a call that fails to
-    // make them leaves nothing behind and the next one tries again), then kept for the life of the process
-    struct State {
-        Stream stream;
-        uint8_t *d_in = nullptr;
-        uint32_t *d_out3 = nullptr, *h_out3 = nullptr;
-        Allocs mem;
-        int init() {
-            GZPX_TRY(stream.create());
-            GZPX_TRY(mem.dev(d_in, kChunk));
-            GZPX_TRY(mem.dev(d_out3, kTiles * 12));
-            return mem.pinned(h_out3, kTiles * 12);
-        }
-    };
     static std::mutex mu;
-    static State *state = nullptr;  // (never deleted: no HIP call at process exit)
+    static AdlerState *state = nullptr;
     if (!out || (!buf && n)) return GZPX_ERR_INVALID_ARG;
     *out = adler;
     if (n == 0) return GZPX_OK;
     std::lock_guard<std::mutex> lock(mu);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GZPX_ERR_NO_DEVICE;
-    if (hipSetDevice(0) != hipSuccess) return GZPX_ERR_DEVICE;
-    if (!state) {
-        std::unique_ptr<State> fresh(new (std::nothrow) State());
-        if (!fresh) return GZPX_ERR_DEVICE;
-        GZPX_TRY(fresh->init());
-        state = fresh.release();
-    }
+    GZPX_TRY(checksum_state(state));
     uint8_t *const d_in = state->d_in;
     uint32_t *const d_out3 = state->d_out3, *const h_out3 = state->h_out3;
     const hipStream_t stream = state->stream;
@@ -1383,7 +1328,7 @@ int gzpx_adler32_checked(uint32_t adler, const void *buf, size_t n, uint32_t *ou
     uint32_t a = adler & 0xFFFFu, b = (adler >> 16) & 0xFFFFu;
     const uint8_t *p = (const uint8_t *)buf;
     while (n) {
-        const size_t take = n < kChunk ? n : kChunk;
+        const size_t take = n < kCheckChunk ? n : kCheckChunk;
         const size_t tiles = (take + 65535) / 65536;
         HIP_TRY(hipMemcpyAsync(d_in, p, take, hipMemcpyHostToDevice, stream));
         launch_adler32(d_in, take, d_out3, stream);
@@ -1805,9 +1750,7 @@ int gzpx_dctx_create(int device, int format, gzpx_dctx **out) {
     }
     if (const char *e = getenv("GZPX_INFLATE_ROUTE"))
         if (!strcmp(e, "wave")) c->route = kInflateRouteWave;
-    for (unsigned l = 0; l < 10; l++) c->cc.pow64[l] = x2k(9 + l);
-    c->cc.pow_tile = x2k(19);
-    c->cc.pow_small = x2k(17);
+    c->cc = crc_consts();
     if (c->stream.create() != GZPX_OK || c->s_h2d.create() != GZPX_OK || c->s_d2h.create() != GZPX_OK ||
         c->ev_dep.create() != GZPX_OK) {
         gzpx_dctx_destroy(c);
@@ -2401,28 +2344,37 @@ int gzpx_ctx_last_stage_ms(const gzpx_ctx *ctx, float ms[GZPX_N_STAGES]) {
 }
 
 const char *gzpx_stage_name(int stage) {
-    static const char *names[GZPX_N_STAGES] = {"k_init_meta", "k_candidates", "k_match", "k_parse", "k_hist",
-                                               "k_huffman",   "k_crc32",      "k_scan",  "k_emit"};
-    return (stage >= 0 && stage < GZPX_N_STAGES) ? names[stage] : "?";
+    switch (stage) {
+    case kStInitMeta: return "k_init_meta";
+    case kStCandidates: return "k_candidates";
+    case kStMatch: return "k_match";
+    case kStParse: return "k_parse";
+    case kStHist: return "k_hist";
+    case kStHuffman: return "k_huffman";
+    case kStCrc32: return "k_crc32";
+    case kStScan: return "k_scan";
+    case kStEmit: return "k_emit";
+    default: return "?";
+    }
 }
 
 const char *gzpx_ctx_stage_kernel(const gzpx_ctx *ctx, int stage) {
     if (ctx && ctx->cfg.format == GZPX_FORMAT_SNAP)  // (the CRC-32C is computed inside k_snap_chunk)
-        return stage == 2 ? "k_snap_chunk" : stage == 7 ? "k_snap_frame+k_scan" : stage == 8 ? "k_snap_emit" : "-";
-    // the kernels behind stages 2 and 3 depend on the level (and, at level 1, on the block size)
-    if (ctx && stage == 2) {
+        return stage == kStMatch ? "k_snap_chunk" : stage == kStScan ? "k_snap_frame+k_scan" : stage == kStEmit ? "k_snap_emit" : "-";
+    // the kernels behind the match and parse stages depend on the level (and, at level 1, on the block size)
+    if (ctx && stage == kStMatch) {
         const Config &c = ctx->dcfg;
         if (c.level <= 1) return (c.block_size <= kTile && !(c.debug & 2u)) ? "k_mparse" : "k_match";
         if (c.level >= 10) return "k_near_optimal";
         return c.lazy ? "k_match_hc+k_parse_lazy" : "k_match_hc+k_parse_hc";
     }
-    if (ctx && stage == 3 && ctx->dcfg.level > 1) return "-";
+    if (ctx && stage == kStParse && ctx->dcfg.level > 1) return "-";
     return gzpx_stage_name(stage);
 }
 
 int gzpx_debug_tokens(gzpx_ctx *ctx, size_t block, uint32_t *tokens, size_t max_tokens,
                       size_t *n_tokens, uint32_t *sub_first_token, size_t *n_sub) {
-    if (!ctx || !n_tokens || block >= ctx->last_nb || ctx->crc_only || ctx->cfg.format == GZPX_FORMAT_SNAP)
+    if (!ctx || !n_tokens || block >= ctx->last_nb || ctx->cfg.format == GZPX_FORMAT_SNAP)
         return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
@@ -2477,7 +2429,7 @@ int gzpx_debug_set_flags(gzpx_ctx *ctx, uint32_t flags) {
 }
 
 int gzpx_debug_redo_count(gzpx_ctx *ctx, uint32_t *count) {
-    if (!ctx || !count || ctx->crc_only || ctx->cfg.format == GZPX_FORMAT_SNAP) return GZPX_ERR_INVALID_ARG;
+    if (!ctx || !count || ctx->cfg.format == GZPX_FORMAT_SNAP) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return GZPX_ERR_DEVICE;
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -39,7 +39,7 @@ def _hooks(emu_lib):
 @pytest.fixture
 def live(emu_lib):
     """A function that reads (allocations, events, streams) live now; the two process-lifetime states (gzpx_crc32's
-    context, gzpx_adler32's buffers) exist before its first reading, and no context of an earlier test is left."""
+    and gzpx_adler32's stream and buffers) exist before its first reading, and no context of an earlier test is left."""
     L = _hooks(emu_lib)
     _native.crc32(b"abc", lib=emu_lib)
     _native.adler32(b"abc", lib=emu_lib)
@@ -268,3 +268,38 @@ def test_adler32_state_is_made_whole_or_not_at_all(emu_lib):
                        timeout=120)
     assert r.returncode == 0, r.stderr
     assert r.stdout.split() == [str(_native.ERR_DEVICE), "True", str(_native.OK), "True"], (r.stdout, r.stderr)
+
+
+# ------------------------------------------------------------------------------------------------ 5. gzpx_crc32's state
+_CRC_CHILD = r"""
+import ctypes, sys, zlib
+L = ctypes.CDLL(sys.argv[1])
+for f in (L.emu_live_allocs, L.emu_live_events, L.emu_live_streams):
+    f.restype = ctypes.c_long
+L.emu_fail_nth_alloc.argtypes = [ctypes.c_long]
+L.gzpx_crc32_checked.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
+live = lambda: (L.emu_live_allocs(), L.emu_live_events(), L.emu_live_streams())
+data = bytes((i * 131 + 7) & 255 for i in range(1000))
+out = ctypes.c_uint32(0)
+before = live()
+L.emu_fail_nth_alloc(2)  # the stream and the tiles' table exist by then
+rc = L.gzpx_crc32_checked(0, data, len(data), ctypes.byref(out))
+L.emu_fail_nth_alloc(0)
+print(rc, live() == before)
+rc = L.gzpx_crc32_checked(0, data, len(data), ctypes.byref(out))
+print(rc, out.value == zlib.crc32(data))
+# a running CRC over more than one 64 KiB tile with an odd tail (the staging grows for it)
+big = bytes((i * i * 31 + i) & 255 for i in range(200001))
+rc = L.gzpx_crc32_checked(zlib.crc32(big[:1000]), big[1000:], len(big) - 1000, ctypes.byref(out))
+print(rc, out.value == zlib.crc32(big))
+"""
+
+
+def test_crc32_state_is_made_whole_or_not_at_all(emu_lib):
+    """The sibling of the Adler-32 test, in a fresh process for the same reason: the first call ever fails while the
+    state is being made and must leave nothing live; the second finds nothing half-made and computes zlib's value."""
+    r = subprocess.run([sys.executable, "-c", _CRC_CHILD, os.path.abspath(emu_lib.path)], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.split() == [str(_native.ERR_DEVICE), "True", str(_native.OK), "True", str(_native.OK), "True"], \
+        (r.stdout, r.stderr)

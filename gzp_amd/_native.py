@@ -43,6 +43,7 @@ INFLATE_SEG, INFLATE_WAVE = 0, 1
 RANGE_UNCOMPRESSED, RANGE_VIRTUAL = 0, 1
 WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # inflate_batch_device: RFC 1951 / 1950 / 1952
 BATCH_SHORT_OK = 1
+CHECK_CRC32, CHECK_ADLER32, CHECK_CRC32C = 0, 1, 2  # checksum_batch_device: zlib crc32 / zlib adler32 / Castagnoli
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -68,6 +69,7 @@ EXPORTS = [
     "gzpx_dindex_build_device", "gzpx_dindex_entries", "gzpx_dindex_destroy", "gzpx_read_ranges_device",
     "gzpx_dctx_last_ranges_members", "gzpx_dctx_last_ranges_ms",
     "gzpx_inflate_batch_device", "gzpx_dctx_last_check_ms", "gzpx_inflate_batch_sizes_device",
+    "gzpx_checksum_batch_device", "gzpx_dctx_set_checksum_width",
 ]
 
 
@@ -257,6 +259,11 @@ class GzpxLib:
         L.gzpx_inflate_batch_sizes_device.restype = i32
         L.gzpx_inflate_batch_sizes_device.argtypes = [vp, i32, vp, sz, vp, vp, sz, ctypes.c_uint32, vp, vp, vp, pu64, psz,
                                                       ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_checksum_batch_device.restype = i32
+        L.gzpx_checksum_batch_device.argtypes = [vp, i32, vp, sz, vp, vp, sz, vp, vp, vp, vp, psz,
+                                                 ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_set_checksum_width.restype = i32
+        L.gzpx_dctx_set_checksum_width.argtypes = [vp, ctypes.c_uint]
         L.gzpx_dctx_last_check_ms.restype = i32
         L.gzpx_dctx_last_check_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_alloc_decompressor.restype = vp
@@ -932,6 +939,35 @@ class DContext:
         if raise_on_member_error:
             self._raise(rc, info)
         return total.value, n_failed.value, info.block
+
+    # ---- checksums of a table of buffers that lie in device memory (gzpx_cksum.h)
+    def checksum_batch_device(self, kind, d_in_ptr, in_len, d_offsets_ptr, d_sizes_ptr, n, d_sums_ptr=None, d_seeds_ptr=None,
+                              d_expected_ptr=None, d_results_ptr=None, stream=None, raise_on_entry_error=True):
+        """CRC-32 / Adler-32 / CRC-32C (kind: CHECK_CRC32 / CHECK_ADLER32 / CHECK_CRC32C) of n entries of d_in, entry i at
+        d_in[offsets[i], offsets[i] + sizes[i]) -- or, with d_sizes_ptr None, d_in[offsets[i], offsets[i + 1]): the
+        d_out_offsets array (n + 1 entries) of inflate_batch_device as it is.  Every table is a DEVICE array (offsets
+        uint64, the others uint32); d_sums_ptr is written, d_seeds_ptr gives running values (zlib's second argument),
+        d_expected_ptr makes the call verify (d_sums_ptr may then be None), d_results_ptr (GzpxMemberResult[n]) is
+        written.  Returns (n_failed, info) with info None when every entry is good; a failing entry raises GzpxError
+        with block= the first one's index, unless raise_on_entry_error=False: then info is its GzpxCheckInfo."""
+        n_failed = ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_checksum_batch_device(self.h, int(kind), d_in_ptr, in_len, d_offsets_ptr, d_sizes_ptr, n,
+                                                   d_seeds_ptr, d_expected_ptr, d_sums_ptr, d_results_ptr,
+                                                   ctypes.byref(n_failed), ctypes.byref(info), stream)
+        if n_failed.value == 0:
+            if rc != OK:  # the call itself was refused, or the device failed
+                raise GzpxError(rc, self.lib.strerror(rc))
+            return 0, None
+        if raise_on_entry_error:
+            if rc == ERR_INVALID_CHECK:
+                self._raise(rc, info)
+            raise GzpxError(rc, self.lib.strerror(rc), block=info.block)
+        return n_failed.value, info
+
+    def set_checksum_width(self, workgroups):
+        """Diagnostics: the persistent workgroups of checksum_batch_device's tile kernel (0: the default)."""
+        self.lib.check(self.lib.L.gzpx_dctx_set_checksum_width(self.h, int(workgroups)))
 
     def last_check_ms(self):
         """HIP-event duration of the check kernel (Adler-32 / CRC-32) of the last inflate_batch_device."""

@@ -1462,6 +1462,12 @@ struct gzpx_dctx : NoCopy {
     uint8_t *d_stage = nullptr;  // the selected members, inflated back to back
     size_t stage_cap = 0;
     Allocs stage_mem;
+    // checksums of a table (gzpx_checksum_batch_device): scratch of one call at a time, used under `mu`
+    CksumScratch ck;
+    size_t ck_entry_cap = 0, ck_wg_cap = 0;
+    Allocs ck_entries;  // ck.prefix, ck.part
+    Allocs ck_wgs;      // ck.carry
+    uint32_t ck_width = 0;  // gzpx_dctx_set_checksum_width
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -2211,6 +2217,60 @@ int gzpx_inflate_batch_sizes_device(gzpx_dctx *c, int wrap, const void *d_in, si
         info->expected = 0;
     }
     return (int)q[kWrRecStatus];
+}
+
+int gzpx_checksum_batch_device(gzpx_dctx *c, int kind, const void *d_in, size_t in_len, const uint64_t *d_offsets,
+                               const uint32_t *d_sizes, size_t n, const uint32_t *d_seeds, const uint32_t *d_expected,
+                               uint32_t *d_sums, gzpx_member_result *d_results, size_t *n_failed, gzpx_check_info *info,
+                               void *hip_stream) {
+    static_assert(sizeof(gzpx_member_result) == 16, "k_cksum_finish writes this layout");
+    if (!c || !n_failed || !info || (!d_in && in_len) || !d_offsets) return GZPX_ERR_INVALID_ARG;
+    *n_failed = 0;
+    if (kind != GZPX_CHECK_CRC32 && kind != GZPX_CHECK_ADLER32 && kind != GZPX_CHECK_CRC32C) return GZPX_ERR_INVALID_ARG;
+    if (!d_sums && !d_expected) return GZPX_ERR_INVALID_ARG;
+    if (n > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (n == 0) return GZPX_OK;
+    hipStream_t stream = c->stream;
+    const int si = free_slot(c, lk, true);
+    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock; its events and record serve)
+    GZPX_TRY(dslot_reserve(sl, 1));
+    const uint32_t wgs = cksum_workgroups(c->n_cu, c->ck_width);
+    GZPX_TRY(grow(c->ck_entries, c->ck_entry_cap, n, n + n / 4 + 64, [&](size_t cap) -> int {
+        GZPX_TRY(c->ck_entries.dev(c->ck.prefix, (cap + 1) * 8));
+        return c->ck_entries.dev(c->ck.part, cap * 4);
+    }));
+    GZPX_TRY(grow(c->ck_wgs, c->ck_wg_cap, wgs, wgs, [&](size_t cap) { return c->ck_wgs.dev(c->ck.carry, cap * 8); }));
+    c->ck.rec = sl.sc.summary;
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    Drain drain{{stream}, 1};
+    sl.have_blk = sl.have_check = false;
+    HIP_TRY(hipEventRecord(sl.ev_t1, stream));
+    launch_cksum_batch(kind, (const uint8_t *)d_in, in_len, d_offsets, d_sizes, (uint32_t)n, d_seeds, d_expected, d_sums,
+                       d_results, c->ck, wgs, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sl.ev_tc, stream));
+    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    sl.have_check = true;
+    c->last_slot = si;
+    c->last_nb = 0;  // (no member was inflated: the inflate getters answer 0)
+    const uint32_t *q = sl.h_summary;  // k_cksum_record's record
+    *n_failed = q[kWrRecFailed];
+    if (q[kWrRecFirst] == 0xFFFFFFFFu) return GZPX_OK;
+    info->block = q[kWrRecFirst];
+    info->found = q[kWrRecFound];
+    info->expected = q[kWrRecExpected];
+    return (int)q[kWrRecStatus];
+}
+
+int gzpx_dctx_set_checksum_width(gzpx_dctx *ctx, unsigned workgroups) {
+    if (!ctx || workgroups > 65536u) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ctx->ck_width = workgroups;
+    return GZPX_OK;
 }
 
 int gzpx_dctx_last_check_ms(gzpx_dctx *ctx, float *ms) {

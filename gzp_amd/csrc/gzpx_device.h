@@ -239,6 +239,21 @@ void launch_inflate_sizes(int wrap, const uint8_t *d_in, uint64_t in_len, const 
                           hipStream_t stream, const InflateScratch &sc, int route, uint32_t *d_out_sizes, uint32_t *d_in_used,
                           void *d_results, hipEvent_t ev_mid = nullptr);
 
+// Checksums of a table of buffers (gzpx_cksum.h, gzpx_checksum_batch_device): CRC-32 / Adler-32 / CRC-32C (`kind`:
+// GZPX_CHECK_*) of n entries of d_in -- entry i is [off[i], off[i] + size[i]), or [off[i], off[i + 1]) with d_sizes null.
+// Every table is device memory; s.rec gets the record (kWrRec*, [6..7] zero).  `workgroups`: the persistent launch,
+// cksum_workgroups(n_cu, 0) unless a test asks for another width; s.carry holds two words for each of them.
+struct CksumScratch {
+    uint64_t *prefix = nullptr;  // [n + 1] exclusive scan of the entries' tiles
+    uint32_t *part = nullptr;    // [n]     the term of an entry that one workgroup took whole; then its sum
+    uint32_t *carry = nullptr;   // [2 * workgroups] the terms of entries that reach across workgroups
+    uint32_t *rec = nullptr;     // the launch record (a slot's summary)
+};
+uint32_t cksum_workgroups(int n_cu, uint32_t width);
+void launch_cksum_batch(int kind, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
+                        uint32_t n, const uint32_t *d_seeds, const uint32_t *d_expected, uint32_t *d_sums, void *d_results,
+                        const CksumScratch &s, uint32_t workgroups, hipStream_t stream);
+
 // Member discovery on the device (gzpx_mscan.h): the candidate headers of a stream, sorted by position, and what the
 // chain from offset 0 makes of them.
 struct MemberScanScratch {

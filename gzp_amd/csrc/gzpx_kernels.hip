@@ -5573,6 +5573,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_mscan.h"
 #include "gzpx_ranges.h"
 #include "gzpx_wrap.h"
+#include "gzpx_cksum.h"
 
 // CRC-32 of the inflated blocks (LibDeflateCrc over the whole orig_size buffer, src/check.rs:45-71):
 // the workgroup routine of k_crc32, blocks addressed through their output offsets.
@@ -5953,6 +5954,31 @@ void launch_inflate_sizes(int wrap, const uint8_t *d_in, uint64_t in_len, const 
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream) {
     const uint32_t tiles = (uint32_t)((n + kAdlerTile - 1) / kAdlerTile);
     if (tiles) hipLaunchKernelGGL(k_adler32_tiles, dim3(tiles), dim3(kAdlerThreads), 0, stream, d_in, n, d_out3);
+}
+
+// Checksums of a table of buffers (gzpx_cksum.h): plan, tiles, finish, record, with no host round trip between them --
+// the persistent launch is sized by the device (or by `width`, for tests), the number of tiles is read on the device.
+uint32_t cksum_workgroups(int n_cu, uint32_t width) { return width ? width : (uint32_t)(n_cu > 0 ? n_cu : 256) * kCkWgPerCu; }
+
+void launch_cksum_batch(int kind, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
+                        uint32_t n, const uint32_t *d_seeds, const uint32_t *d_expected, uint32_t *d_sums, void *d_results,
+                        const CksumScratch &s, uint32_t workgroups, hipStream_t stream) {
+    static const CkPow pw_crc32 = ck_pow_table<kCkPolyCrc32>(), pw_crc32c = ck_pow_table<kCkPolyCrc32c>();
+    const CkTable t{d_in, in_len, d_offsets, d_sizes, n};
+    const CkOut o{d_seeds, d_expected, d_sums, (WrapResult *)d_results};
+    hipLaunchKernelGGL(k_cksum_plan, dim3(1), dim3(kCkPlanThreads), 0, stream, t, s.prefix, s.rec);
+    if (kind == (int)kCkAdler32)
+        hipLaunchKernelGGL((k_cksum_tiles<kCkAdler32>), dim3(workgroups), dim3(kCkThreads), 0, stream, t, d_seeds,
+                           (const uint64_t *)s.prefix, s.part, s.carry, pw_crc32);
+    else if (kind == (int)kCkCrc32c)
+        hipLaunchKernelGGL((k_cksum_tiles<kCkCrc32c>), dim3(workgroups), dim3(kCkThreads), 0, stream, t, d_seeds,
+                           (const uint64_t *)s.prefix, s.part, s.carry, pw_crc32c);
+    else
+        hipLaunchKernelGGL((k_cksum_tiles<kCkCrc32>), dim3(workgroups), dim3(kCkThreads), 0, stream, t, d_seeds,
+                           (const uint64_t *)s.prefix, s.part, s.carry, pw_crc32);
+    hipLaunchKernelGGL(k_cksum_finish, dim3((n + 255) / 256), dim3(256), 0, stream, (uint32_t)kind, t, o,
+                       (const uint64_t *)s.prefix, s.part, (const uint32_t *)s.carry, workgroups, s.rec);
+    hipLaunchKernelGGL(k_cksum_record, dim3(1), dim3(64), 0, stream, t, d_expected, (const uint32_t *)s.part, s.rec);
 }
 
 // Member discovery (gzpx_mscan.h).  Everything the later kernels need to know about the candidates they work on is

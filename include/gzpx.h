@@ -480,6 +480,56 @@ int gzpx_inflate_batch_sizes_device(gzpx_dctx *ctx, int wrap,
                                     uint32_t *d_in_used,           /* DEVICE [n], optional, written */
                                     gzpx_member_result *d_results, /* DEVICE [n], optional, written */
                                     uint64_t *total_out, size_t *n_failed, gzpx_check_info *info, void *hip_stream);
+/* ---- checksums of a table of device-resident buffers: CRC-32, CRC-32C and Adler-32 of n entries of one input, for the
+ * callers whose checksum lies outside the DEFLATE stream -- ZIP entries (CRC-32 in the directory), PNG chunks, Parquet
+ * pages (CRC-32 in the page header), Zarr's crc32c codec, and gzp's whole-stream checks (src/check.rs:85-164) -- and so
+ * for what gzpx_inflate_batch_device leaves in device memory from a GZPX_WRAP_RAW batch.  The counterpart of zlib's
+ * crc32(seed, buf, len) / adler32(seed, buf, len) (libdeflate_crc32 / libdeflate_adler32) for a table of buffers in
+ * device memory: tables in, sums out, and nothing crosses to the host but one 32-byte record.
+ *   Context: any gzpx_dctx, whatever format it was created for.  Runs under the context's lock, returns synchronised;
+ *   hip_stream as for gzpx_inflate_batch_device, GZPX_STREAM_NONE included.  gzpx_dctx_last_check_ms answers for this
+ *   call too: the HIP-event duration of its kernels.
+ *   Entries: with d_sizes, entry i is d_in[off[i], off[i] + size[i]) -- an (in_offsets, in_sizes) pair.  With
+ *   d_sizes == NULL (the span form) d_offsets has n + 1 entries and entry i is d_in[off[i], off[i + 1]): the
+ *   d_out_offsets array gzpx_inflate_batch_device writes, taken as it is; such an entry may be longer than 4 GiB.
+ *   Entries may overlap, repeat, nest, be empty and come in any order.
+ *   Value: sums[i] = zlib's crc32(seed, buf, len) (GZPX_CHECK_CRC32), adler32(seed, buf, len) (GZPX_CHECK_ADLER32), or
+ *   the same CRC with the Castagnoli polynomial (GZPX_CHECK_CRC32C: iSCSI / RFC 3720, NOT the masked form of Snappy
+ *   frames).  seed = d_seeds[i]: the sum of what lies in front, for a buffer that is hashed in pieces; without d_seeds
+ *   0 for both CRCs and 1 for Adler-32.  An empty entry yields its seed.
+ *   Verify: with d_expected, a valid entry whose sum differs from d_expected[i] is a failed entry.
+ *   Status of one entry, the first that applies:
+ *     GZPX_ERR_INVALID_ARG    the entry leaves [0, in_len), or in the span form off[i + 1] < off[i]; sums[i] = 0 and no
+ *                             byte is read for it
+ *     GZPX_ERR_INVALID_CHECK  the sum differs from d_expected[i]
+ *   d_results[i] = {status, the entry's length saturated at 0xFFFFFFFF (0 for an invalid entry), found = sums[i],
+ *   expected = d_expected[i], or 0 without d_expected}.
+ *   Returns the status of the first failing entry in table order with info->block = its index and found / expected
+ *   filled in; every other entry is still computed, *n_failed says how many failed.
+ *   GZPX_ERR_INVALID_ARG for the call, with nothing launched: a null ctx, d_in (with in_len > 0), d_offsets,
+ *   n_failed or info; an unknown kind; neither d_sums nor d_expected; n > 0xFFFFFFF0.  n == 0 is OK.
+ *   Memory: scratch is 12 bytes per entry and 8 bytes per workgroup launched, kept by the context; nothing is sized by
+ *   in_len or by the sum of the sizes (overlapping entries make that sum unbounded); no table crosses to the host, and
+ *   there is no host round trip between the kernels.
+ *   Reads: the bytes of valid entries and the aligned 4-byte words that hold an entry's first and last byte -- never a
+ *   byte in front of the aligned 16-byte word that holds d_in[0] or behind the one that holds d_in[in_len - 1].
+ * gzpx_dctx_set_checksum_width: diagnostics -- the number of persistent workgroups of the call's tile kernel (0, the
+ * default: six per compute unit; at most 65536).  The sums do not depend on it; tests move the workgroups' edges
+ * with it. */
+#define GZPX_CHECK_CRC32   0  /* zlib / gzip crc32: reflected 0xEDB88320, init and xor-out all ones          */
+#define GZPX_CHECK_ADLER32 1  /* zlib adler32                                                                 */
+#define GZPX_CHECK_CRC32C  2  /* Castagnoli, reflected 0x82F63B78, init and xor-out all ones, NOT Snappy-masked */
+int gzpx_checksum_batch_device(gzpx_dctx *ctx, int kind,
+                               const void *d_in, size_t in_len,
+                               const uint64_t *d_offsets,     /* DEVICE [n], or [n + 1] when d_sizes == NULL */
+                               const uint32_t *d_sizes,       /* DEVICE [n], or NULL: the span form          */
+                               size_t n,
+                               const uint32_t *d_seeds,       /* DEVICE [n], optional: running values         */
+                               const uint32_t *d_expected,    /* DEVICE [n], optional: verify                 */
+                               uint32_t *d_sums,              /* DEVICE [n], optional if d_expected is given  */
+                               gzpx_member_result *d_results, /* DEVICE [n], optional                         */
+                               size_t *n_failed, gzpx_check_info *info, void *hip_stream);
+int gzpx_dctx_set_checksum_width(gzpx_dctx *ctx, unsigned workgroups);
 typedef struct gzpx_decompressor gzpx_decompressor;
 gzpx_decompressor *gzpx_alloc_decompressor(void);
 /* 0 = ok (short output allowed, *actual = bytes produced), GZPX_ERR_BAD_DATA, GZPX_ERR_INSUFFICIENT_SPACE */

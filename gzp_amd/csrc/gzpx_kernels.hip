@@ -207,6 +207,27 @@ __device__ __forceinline__ void offset_slot(uint32_t off, uint32_t &slot, uint32
     }
 }
 
+// The two token consumers (k_hist, k_emit) look slots up without a branch: a text wave always holds
+// literals and matches, so every side of a branch would run for every token.
+//   length: a 256-entry LDS table of length - 3.  k_hist keeps slot | extra-bit count << 5 (length_entry);
+//           k_emit builds, from the same entries, the codeword and extra bits of every length for each sub-block
+//   offset: d = offset - 1.  With k = floor(log2(d | 1)) the extra-bit count is max(k - 1, 0) and the slot
+//           2k + the bit below d's top bit, which for d < 4 is d itself
+__device__ __forceinline__ uint32_t length_entry(uint32_t x) {
+    uint32_t ls, le, lv;
+    length_slot(x + 3, ls, le, lv);
+    return ls | (le << 5);
+}
+__device__ __forceinline__ void build_length_table(uint8_t *lslot, uint32_t tid) {
+    if (tid < 256) lslot[tid] = (uint8_t)length_entry(tid);
+}
+
+__device__ __forceinline__ void offset_slot_flat(uint32_t d, uint32_t &slot, uint32_t &ebits) {
+    const uint32_t k = 31u - (uint32_t)__clz((int)(d | 1u));
+    ebits = (uint32_t)max((int)k - 1, 0);
+    slot = 2u * k + ((d >> ebits) & 1u);
+}
+
 
 // RFC 1951's order of the code length code lengths (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13,
 // 2, 14, 1, 15), five bits each in two constants: a table indexed by a lane or a loop counter would be an
@@ -3480,6 +3501,9 @@ __global__ void k_hc_init(uint32_t nb, HcState *hc, uint32_t *pending) {
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kHistCopies = 8;                 // (a power of two)
 constexpr uint32_t kHistPad = kHistStride + 1;      // copies a word apart in the banks
+constexpr uint32_t kHistStep = 2048;                // tokens per workgroup step: two 16-byte loads per lane
+constexpr uint32_t kHistNoToken = 0x7FFFFFFFu;      // (never a real token: a literal is < 256)
+static_assert(kHistStep % 1024 == 0, "whole 16-byte loads per lane");
 
 __global__ __launch_bounds__(256) void k_hist(Config cfg, const BlockMeta *__restrict__ meta_all,
                                               const SubMeta *__restrict__ sub_all,
@@ -3490,10 +3514,12 @@ __global__ __launch_bounds__(256) void k_hist(Config cfg, const BlockMeta *__res
     // three quarters of this kernel's LDS cycles were bank conflicts).  Eight copies, picked by the
     // lane, staggered by one bank; summed when the sub-block is written out.
     __shared__ uint32_t hist[kHistCopies * kHistPad];
+    __shared__ uint8_t lslot[256];
     const uint32_t tid = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const BlockMeta *meta = meta_all + b;
     if (meta->n <= cfg.passthrough) return;
+    build_length_table(lslot, tid);
     const SubMeta *sub = sub_all + (uint64_t)b * cfg.max_sub;
     const uint32_t *tok = tok_all + (uint64_t)b * cfg.stride;
     const uint32_t nsub = meta->nsub;
@@ -3501,23 +3527,40 @@ __global__ __launch_bounds__(256) void k_hist(Config cfg, const BlockMeta *__res
     for (uint32_t s = 0; s < nsub; s++) {
         for (uint32_t i = tid; i < kHistCopies * kHistPad; i += 256) hist[i] = 0;
         __syncthreads();
-        const uint32_t t_end = sub[s].tok_end;
-        for (uint32_t t0 = sub[s].tok_begin + tid; t0 < t_end; t0 += 4 * 256) {
-            uint32_t tk[4];
+        // A step is kHistStep tokens from an index that is a multiple of 4: two 16-byte loads per lane, issued
+        // together.  (Token rows are 16-byte aligned and padded by 2048 entries, so a step that begins inside
+        // the sub-block may be loaded whole.)  Whether a step lies inside [t_begin, t_end) is decided once, for
+        // the workgroup; only the first and the last step look at each token's index.
+        const uint32_t t_begin = sub[s].tok_begin, t_end = sub[s].tok_end;
+        for (uint32_t t0 = t_begin & ~3u; t0 < t_end; t0 += kHistStep) {
+            uint32_t tk[kHistStep / 256];
 #pragma unroll
-            for (uint32_t k = 0; k < 4; k++) tk[k] = t0 + k * 256 < t_end ? tok[t0 + k * 256] : 0xFFFFFFFFu;
+            for (uint32_t k = 0; k < kHistStep / 1024; k++) {
+                const uint4 v = *(const uint4 *)(tok + t0 + 1024u * k + 4u * tid);
+                tk[4 * k + 0] = v.x;
+                tk[4 * k + 1] = v.y;
+                tk[4 * k + 2] = v.z;
+                tk[4 * k + 3] = v.w;
+            }
+            const bool edge = t0 < t_begin || t0 + kHistStep > t_end;
+            if (edge) {
 #pragma unroll
-            for (uint32_t k = 0; k < 4; k++) {
+                for (uint32_t k = 0; k < kHistStep / 256; k++) {
+                    const uint32_t i = t0 + 1024u * (k / 4) + 4u * tid + (k & 3u);
+                    if (i < t_begin || i >= t_end) tk[k] = kHistNoToken;
+                }
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kHistStep / 256; k++) {
                 const uint32_t t = tk[k];
-                if (t == 0xFFFFFFFFu) continue;  // (never a real token: offset field < 32768)
-                if (t & kTokMatch) {
-                    uint32_t ls, le, lv, os, oe, ov;
-                    length_slot(t & 0x1FFu, ls, le, lv);
-                    offset_slot((t >> 9) & 0xFFFFu, os, oe, ov);
-                    atomicAdd(&mine[257 + ls], 1u);
+                if (edge && t == kHistNoToken) continue;
+                const bool m = (int32_t)t < 0;
+                const uint32_t lt = lslot[(t - 3u) & 0xFFu];
+                atomicAdd(&mine[m ? 257u + (lt & 31u) : t], 1u);
+                if (m) {
+                    uint32_t os, oe;
+                    offset_slot_flat(((t >> 9) & 0xFFFFu) - 1u, os, oe);
                     atomicAdd(&mine[kNumLitlen + os], 1u);
-                } else {
-                    atomicAdd(&mine[t], 1u);
                 }
             }
         }
@@ -4460,7 +4503,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan(uint32_t nb, const BlockM
 // The stage is a sliding window over the block's output: when the next piece (a header, 1024
 // tokens, 16 KiB of stored bytes, the footer) might not fit, everything complete is written out
 // and the window moves on.  A 64 KiB BGZF block never needs to slide.
-constexpr uint32_t kStageWords = 18432;  // 72 KiB
+constexpr uint32_t kStageWords = 18224;  // 71.2 KiB (a BGZF block is at most 65,6xx bytes; the rest of 72 KiB: the length table, the second set of wave sums)
 
 __device__ __forceinline__ void stage_or_bits(uint32_t *stage, uint32_t bitpos, uint64_t v) {
     const uint32_t w = bitpos >> 5, sh = bitpos & 31u;
@@ -4480,6 +4523,16 @@ __device__ __forceinline__ void stage_put_byte(uint32_t *stage, uint32_t byte_id
 // just below the block's first output byte) to global memory: whole dwords where every byte
 // belongs to this block, single bytes at the block's two edges.
 constexpr uint32_t kEmitThreads = 1024;
+constexpr uint32_t kEmitTpl = 4;                         // tokens per thread and step of the token loop (8: the compiler spills)
+constexpr uint32_t kEmitStep = kEmitTpl * kEmitThreads;  // tokens per workgroup scan
+// The sub-block's codes in LDS, as the token loop wants them:
+//   [0, 288)    litlen symbols: codeword | length << 24 (so a literal and a match length are read alike)
+//   [288, 320)  offset symbols: codeword | length << 16, as in global memory
+//   [320, 576)  match length - 3 -> length codeword with its extra bits above | the bit count of both << 24
+constexpr uint32_t kEmitLenTab = kCodeWords;
+constexpr uint32_t kEmitCodeWords = kCodeWords + 256;
+constexpr uint32_t kNullSym = 287;  // a litlen symbol no stream holds: its entry is kept 0, the token without bits
+static_assert(kEmitTpl % 4 == 0 && kEmitTpl <= 8, "16-byte token loads; two byte-wide bit counts summed in one word");
 
 __device__ __forceinline__ void stage_flush(const uint32_t *stage, uint8_t *dst_aligned,
                                             uint32_t win_base, uint32_t upto, uint32_t lead,
@@ -4498,6 +4551,22 @@ __device__ __forceinline__ void stage_flush(const uint32_t *stage, uint8_t *dst_
     }
 }
 
+// block_exclusive_scan with ONE barrier: consecutive steps of a sub-block's token loop alternate between two sets of
+// wave sums, and a wave that writes a set again has passed the barrier of the step between (or the barriers between
+// two sub-blocks), behind every reader of that set.
+__device__ __forceinline__ uint32_t emit_scan(uint32_t v, uint32_t *wsum, uint32_t *total) {
+    constexpr unsigned NW = kEmitThreads / 64;
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t inc = wave_incl_add(v);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    const uint32_t mine = lane < NW ? wsum[lane] : 0u;
+    const uint32_t winc = wave_incl_add(mine);
+    *total = rdlane(winc, NW - 1);
+    const uint32_t base = wave ? rdlane(winc, wave - 1) : 0u;
+    return base + inc - v;
+}
+
 __device__ __forceinline__ void emit_block(const Config &cfg, const uint8_t *__restrict__ slab,
                                            const BlockMeta *__restrict__ meta_all,
                                            const SubMeta *__restrict__ sub_all,
@@ -4506,7 +4575,7 @@ __device__ __forceinline__ void emit_block(const Config &cfg, const uint8_t *__r
                                            const uint32_t *__restrict__ hdr_all,
                                            const uint64_t *__restrict__ out_off,
                                            uint8_t *__restrict__ out, uint64_t out_cap, const uint32_t b,
-                                           uint32_t *stage, uint32_t *codes, uint32_t *wsum, const uint8_t *lslot) {
+                                           uint32_t *stage, uint32_t *codes, uint32_t *wsum) {
     const uint32_t tid = threadIdx.x;
     const BlockMeta *meta = meta_all + b;
     const SubMeta *sub = sub_all + (uint64_t)b * cfg.max_sub;
@@ -4524,7 +4593,9 @@ __device__ __forceinline__ void emit_block(const Config &cfg, const uint8_t *__r
     const uint32_t end_byte = lead + framed;
     uint32_t win_base = 0;  // aligned coordinate of stage[0] (multiple of 4)
 
-    for (uint32_t i = tid; i < kStageWords; i += kEmitThreads) stage[i] = 0;
+    // (only what the block will use; a block that slides zeroes the whole window from then on)
+    const uint32_t used_words = (end_byte + 3) >> 2 < kStageWords ? (end_byte + 3) >> 2 : kStageWords;
+    for (uint32_t i = tid; i < used_words; i += kEmitThreads) stage[i] = 0;
     __syncthreads();
 
     // ---- gzip member header (src/bgzf.rs:274-303 / src/mgzip.rs:246-275)
@@ -4614,88 +4685,120 @@ __device__ __forceinline__ void emit_block(const Config &cfg, const uint8_t *__r
         // ---- Huffman-coded sub-block: header bits, tokens, end-of-block
         __syncthreads();  // the previous sub-block is done with `codes`
         const uint32_t *cd = codes_all + ((uint64_t)b * cfg.max_sub + s) * kCodeWords;
-        for (uint32_t i = tid; i < kCodeWords; i += kEmitThreads) codes[i] = cd[i];
+        if (tid < kEmitCodeWords) {
+            uint32_t e;
+            if (tid < kNumLitlen) {
+                const uint32_t lc = cd[tid];
+                e = tid == kNullSym ? 0u : (lc & 0xFFFFu) | (lc >> 16 << 24);
+            } else if (tid < kEmitLenTab) {
+                e = cd[tid];
+            } else {
+                const uint32_t x = tid - kEmitLenTab, lt = length_entry(x);
+                const uint32_t lc = cd[257u + (lt & 31u)], le = lt >> 5;
+                e = (lc & 0xFFFFu) | ((x & ((1u << le) - 1u)) << (lc >> 16)) | (((lc >> 16) + le) << 24);
+            }
+            codes[tid] = e;
+        }
         const uint32_t *hw = hdr_all + ((uint64_t)b * cfg.max_sub + s) * kHdrWords;
         const uint32_t nhw = (sm.hdr_bits + 31) >> 5;
         ensure(32u * kHdrWords);
         for (uint32_t i = tid; i < nhw; i += kEmitThreads) stage_or_bits(stage, bitpos + 32 * i, hw[i]);
         bitpos += sm.hdr_bits;
         __syncthreads();
-        // 4 consecutive tokens per thread: one workgroup scan per 4096 tokens, and neighbouring
-        // codewords are merged into <= 64-bit pieces before they are OR-ed into the staging buffer
-        // token words are fetched one step ahead, unconditionally (index clamped to the block's
-        // last token) so that the four loads of a step are in flight together
-        const uint32_t tok_last = meta->ntok - 1;
-        uint32_t tnext[4];
+        // kEmitTpl consecutive tokens per thread and step, from an index that is a multiple of 4: 16-byte
+        // token loads, one workgroup scan per kEmitStep tokens.  A wave whose tokens all lie behind tok_end
+        // takes part in the scan only; a wave that straddles an end of [tok_begin, tok_end) swaps the
+        // tokens outside for kNullSym, which has no bits.  (Token rows are 16-byte aligned and padded by
+        // 2048 entries: a wave that begins inside the sub-block may load all its tokens.)  The next step's
+        // tokens are fetched a step ahead.
+        const uint32_t wtok = uniform((tid >> 6) * (64u * kEmitTpl));  // this wave's first token within a step
+        const uint32_t *ltok = tok + kEmitTpl * tid;
+        uint4 tnext[kEmitTpl / 4];
+        if ((sm.tok_begin & ~3u) + wtok < sm.tok_end) {
 #pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-            const uint32_t i = sm.tok_begin + 4 * tid + j;
-            tnext[j] = tok[i < tok_last ? i : tok_last];
+            for (uint32_t q = 0; q < kEmitTpl / 4; q++) tnext[q] = *(const uint4 *)(ltok + (sm.tok_begin & ~3u) + 4 * q);
         }
-        for (uint32_t tb = sm.tok_begin; tb < sm.tok_end; tb += 4 * kEmitThreads) {
-            ensure(4u * kEmitThreads * 48u);
-            const uint32_t t0 = tb + 4 * tid;
-            uint64_t bits[4];
-            uint32_t nbits[4], sum = 0;
-            uint32_t tcur[4];
+        uint32_t step = 0;
+        for (uint32_t tb = sm.tok_begin & ~3u; tb < sm.tok_end; tb += kEmitStep) {
+            // per token: first symbol's codeword + extra bits (<= 20 bits), offset codeword + extra bits
+            // (<= 28, none for a literal), and the two bit counts in one word (low byte | next byte)
+            uint32_t pa[kEmitTpl], pb[kEmitTpl], nn[kEmitTpl], sumnn = 0;
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) tcur[j] = tnext[j];
+            for (uint32_t j = 0; j < kEmitTpl; j++) pa[j] = pb[j] = nn[j] = 0;
+            const bool live = tb + wtok < sm.tok_end;
+            if (live) {
+                uint32_t t[kEmitTpl];
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                const uint32_t i = t0 + 4 * kEmitThreads + j;
-                tnext[j] = tok[i < tok_last ? i : tok_last];
-            }
+                for (uint32_t q = 0; q < kEmitTpl / 4; q++) {
+                    t[4 * q + 0] = tnext[q].x;
+                    t[4 * q + 1] = tnext[q].y;
+                    t[4 * q + 2] = tnext[q].z;
+                    t[4 * q + 3] = tnext[q].w;
+                }
+                if (tb + wtok < sm.tok_begin || tb + wtok + 64u * kEmitTpl > sm.tok_end) {
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                bits[j] = 0;
-                nbits[j] = 0;
-                if (t0 + j < sm.tok_end) {
-                    const uint32_t t = tcur[j];
-                    if (t & kTokMatch) {
-                        const uint32_t len = t & 0x1FFu, off = (t >> 9) & 0xFFFFu;
-                        uint32_t os, oe, ov;
-                        const uint32_t lt = lslot[len - 3u];
-                        const uint32_t ls = lt & 31u, le = lt >> 5, lv = (len - 3u) & ((1u << le) - 1u);
-                        offset_slot(off, os, oe, ov);
-                        const uint32_t lc = codes[257 + ls], oc = codes[kNumLitlen + os];
-                        // length codeword + extra bits (<= 20 bits) and offset codeword + extra bits (<= 28)
-                        // are put together in 32-bit arithmetic, then joined by ONE 64-bit shift
-                        const uint32_t lpart = (lc & 0xFFFFu) | (lv << (lc >> 16)), lbits = (lc >> 16) + le;
-                        const uint32_t opart = (oc & 0xFFFFu) | (ov << (oc >> 16)), obits = (oc >> 16) + oe;
-                        bits[j] = (uint64_t)lpart | ((uint64_t)opart << lbits);
-                        nbits[j] = lbits + obits;
-                    } else {
-                        const uint32_t lc = codes[t];
-                        bits[j] = lc & 0xFFFFu;
-                        nbits[j] = lc >> 16;
+                    for (uint32_t j = 0; j < kEmitTpl; j++) {
+                        const uint32_t i = tb + kEmitTpl * tid + j;
+                        if (i < sm.tok_begin || i >= sm.tok_end) t[j] = kNullSym;
                     }
-                    sum += nbits[j];
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < kEmitTpl; j++) {
+                    const uint32_t tk = t[j];
+                    const bool m = (int32_t)tk < 0;
+                    const uint32_t lc = codes[m ? kEmitLenTab + ((tk - 3u) & 0xFFu) : tk];
+                    const uint32_t d = m ? ((tk >> 9) & 0xFFFFu) - 1u : 0u;
+                    uint32_t os, oe;
+                    offset_slot_flat(d, os, oe);  // (a literal: slot 0, no extra bits)
+                    // (read by every lane and masked: a branch here would keep the tokens' LDS reads apart)
+                    const uint32_t oc = codes[kNumLitlen + os] & (uint32_t)((int32_t)tk >> 31);
+                    pa[j] = lc & 0xFFFFFFu;
+                    pb[j] = (oc & 0xFFFFu) | ((d & ((1u << oe) - 1u)) << (oc >> 16));
+                    nn[j] = (lc >> 24) | (((oc >> 16) + oe) << 8);
+                    sumnn += nn[j];  // (8 tokens: <= 160 and <= 224, the bytes do not carry)
+                }
+                // (fetched here, not before the lookups: the scan and the bit writer cover the latency, and this step's
+                // token registers are free again)
+                if (tb + kEmitStep + wtok < sm.tok_end) {
+#pragma unroll
+                    for (uint32_t q = 0; q < kEmitTpl / 4; q++) tnext[q] = *(const uint4 *)(ltok + tb + kEmitStep + 4 * q);
                 }
             }
             uint32_t total;
-            const uint32_t ex = block_exclusive_scan<kEmitThreads / 64>(sum, wsum, &total);
-            uint32_t off_bits = bitpos + ex, accn = 0;
-            uint64_t acc = 0;
+            const uint32_t ex = emit_scan((sumnn & 0xFFu) + (sumnn >> 8), wsum + (kEmitThreads / 64) * (step & 1u), &total);
+            step++;
+            ensure(total);
+            if (live) {
+                // The lane's bits go through a 32-bit accumulator that starts at the lane's bit offset within its
+                // first dword and hands over every dword it completes.  Only the first and the last dword are
+                // shared with a neighbour; the OR into the zeroed stage serves both kinds.
+                uint32_t *w = stage + ((bitpos + ex) >> 5);
+                uint32_t accn = (bitpos + ex) & 31u, lo = 0;
+                auto append = [&](uint32_t v, uint32_t nbits) {
+                    lo |= v << accn;
+                    accn += nbits;
+                    if (accn >= 32u) {  // (nbits <= 28: there were bits before, and 1..31 of v's are left over or none)
+                        atomicOr(w, lo);
+                        w++;
+                        accn -= 32u;
+                        lo = v >> (nbits - accn);
+                    }
+                };
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                if (accn + nbits[j] > 64) {
-                    stage_or_bits(stage, off_bits, acc);
-                    off_bits += accn;
-                    acc = 0;
-                    accn = 0;
+                for (uint32_t j = 0; j < kEmitTpl; j++) {
+                    append(pa[j], nn[j] & 0xFFu);
+                    append(pb[j], nn[j] >> 8);
                 }
-                acc |= bits[j] << accn;
-                accn += nbits[j];
+                if (lo) atomicOr(w, lo);
             }
-            if (accn) stage_or_bits(stage, off_bits, acc);
             bitpos += total;
         }
         ensure(64);
         if (tid == 0) {
             const uint32_t ec = codes[256];
-            stage_or_bits(stage, bitpos, ec & 0xFFFFu);
+            stage_or_bits(stage, bitpos, ec & 0xFFFFFFu);
         }
-        bitpos += codes[256] >> 16;
+        bitpos += codes[256] >> 24;
         __syncthreads();
     }
 
@@ -4731,18 +4834,11 @@ __global__ __launch_bounds__(kEmitThreads, 8) void k_emit(Config cfg, const uint
                                               const uint64_t *__restrict__ out_off,
                                               uint8_t *__restrict__ out, uint64_t out_cap, uint32_t nb) {
     __shared__ uint32_t stage[kStageWords];
-    __shared__ uint32_t codes[kCodeWords];
-    __shared__ uint32_t wsum[kEmitThreads / 64];
-    __shared__ uint8_t lslot[256];  // length - 3 -> DEFLATE length slot | extra-bit count << 5 (one LDS read instead of ~10 VALU)
-    if (threadIdx.x < 256) {
-        uint32_t ls, le, lv;
-        length_slot(threadIdx.x + 3, ls, le, lv);
-        lslot[threadIdx.x] = (uint8_t)(ls | (le << 5));
-    }
+    __shared__ uint32_t codes[kEmitCodeWords];
+    __shared__ uint32_t wsum[2 * (kEmitThreads / 64)];
     for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
         __syncthreads();  // the previous block is done with the stage
-        emit_block(cfg, slab, meta_all, sub_all, tok_all, codes_all, hdr_all, out_off, out, out_cap, b, stage, codes, wsum,
-                   lslot);
+        emit_block(cfg, slab, meta_all, sub_all, tok_all, codes_all, hdr_all, out_off, out, out_cap, b, stage, codes, wsum);
     }
 }
 

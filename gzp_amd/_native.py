@@ -44,6 +44,7 @@ RANGE_UNCOMPRESSED, RANGE_VIRTUAL = 0, 1
 WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # inflate_batch_device: RFC 1951 / 1950 / 1952
 BATCH_SHORT_OK = 1
 CHECK_CRC32, CHECK_ADLER32, CHECK_CRC32C = 0, 1, 2  # checksum_batch_device: zlib crc32 / zlib adler32 / Castagnoli
+LINES_TILE = 16384  # GZPX_LINES_TILE: the tile of the line table, in bytes of the inflated stream
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -70,6 +71,9 @@ EXPORTS = [
     "gzpx_dctx_last_ranges_members", "gzpx_dctx_last_ranges_ms",
     "gzpx_inflate_batch_device", "gzpx_dctx_last_check_ms", "gzpx_inflate_batch_sizes_device",
     "gzpx_checksum_batch_device", "gzpx_dctx_set_checksum_width",
+    "gzpx_dlines_build_device", "gzpx_dlines_prefix", "gzpx_dlines_destroy", "gzpx_line_offsets_device",
+    "gzpx_read_lines_device", "gzpx_dctx_set_lines_batch", "gzpx_dctx_last_lines_members", "gzpx_dctx_last_lines_ms",
+    "gzpx_dctx_last_lines_build_ms",
 ]
 
 
@@ -253,6 +257,26 @@ class GzpxLib:
         L.gzpx_dctx_last_ranges_members.argtypes = [vp, psz]
         L.gzpx_dctx_last_ranges_ms.restype = i32
         L.gzpx_dctx_last_ranges_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_dlines_build_device.restype = i32
+        L.gzpx_dlines_build_device.argtypes = [vp, vp, vp, sz, ctypes.c_uint, ctypes.POINTER(vp), pu64, pu64,
+                                               ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dlines_prefix.restype = i32
+        L.gzpx_dlines_prefix.argtypes = [vp, vp, sz, psz]
+        L.gzpx_dlines_destroy.restype = None
+        L.gzpx_dlines_destroy.argtypes = [vp]
+        L.gzpx_line_offsets_device.restype = i32
+        L.gzpx_line_offsets_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, psz, ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_read_lines_device.restype = i32
+        L.gzpx_read_lines_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, sz, psz, vp, vp, psz,
+                                             ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_set_lines_batch.restype = i32
+        L.gzpx_dctx_set_lines_batch.argtypes = [vp, sz]
+        L.gzpx_dctx_last_lines_members.restype = i32
+        L.gzpx_dctx_last_lines_members.argtypes = [vp, psz]
+        L.gzpx_dctx_last_lines_ms.restype = i32
+        L.gzpx_dctx_last_lines_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_dctx_last_lines_build_ms.restype = i32
+        L.gzpx_dctx_last_lines_build_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_inflate_batch_device.restype = i32
         L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
                                                 ctypes.POINTER(GzpxCheckInfo), vp]
@@ -894,6 +918,81 @@ class DContext:
         self.lib.check(self.lib.L.gzpx_dctx_last_ranges_ms(self.h, ms))
         return ms[0], ms[1], ms[2]
 
+    # ---- reads by line (gzpx_lines.h)
+    def build_lines_device(self, index, d_in_ptr, in_len, delim=10, stream=None):
+        """The line table of the stream `index` was built from, for the delimiter byte `delim`: a DLines for
+        line_offsets_device / read_lines_device.  Every member is inflated and checked once."""
+        h = ctypes.c_void_p()
+        d, n = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_dlines_build_device(self.h, index.h, d_in_ptr, in_len, int(delim), ctypes.byref(h), ctypes.byref(d),
+                                                 ctypes.byref(n), ctypes.byref(info), stream)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        self.lib.check(rc)
+        return DLines(self.lib, h, d.value, n.value)
+
+    def line_offsets_device(self, index, lines, d_in_ptr, in_len, line_numbers, stream=None):
+        """start(k) for every k of line_numbers (0 <= k <= n_lines): uint64[n], byte offsets into the inflated stream.
+        Only the members that hold the boundaries' tiles are inflated.  A bad k raises GzpxError with .range_index."""
+        k = np.ascontiguousarray(np.asarray(line_numbers, dtype=np.uint64).reshape(-1))
+        offs = np.zeros(k.size, dtype=np.uint64)
+        bad = ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_line_offsets_device(self.h, index.h, lines.h, d_in_ptr, in_len, k.ctypes.data, k.size,
+                                                 offs.ctypes.data, ctypes.byref(bad), ctypes.byref(info), stream)
+        if rc == OK:
+            return offs
+        if bad.value != ctypes.c_size_t(-1).value:
+            raise GzpxError(rc, "line %d does not lie in the stream" % bad.value, range_index=bad.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def read_lines_device(self, index, lines, d_in_ptr, in_len, line_ranges, d_out_ptr, out_cap, stream=None):
+        """line_ranges[n, 2] = [a, b) in line numbers, into d_out back to back: (out_len, out_offsets uint64[n + 1],
+        byte_ranges uint64[n, 2] = what each range was in bytes of the inflated stream; an empty range is (0, 0)).  A
+        bad range raises GzpxError with .range_index; too small an out_cap raises it with .needed."""
+        r = np.ascontiguousarray(np.asarray(line_ranges, dtype=np.uint64).reshape(-1, 2))
+        offs = np.zeros(r.shape[0] + 1, dtype=np.uint64)
+        br = np.zeros((r.shape[0], 2), dtype=np.uint64)
+        out_len, bad = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_read_lines_device(self.h, index.h, lines.h, d_in_ptr, in_len, r.ctypes.data, r.shape[0], d_out_ptr,
+                                               out_cap, ctypes.byref(out_len), offs.ctypes.data, br.ctypes.data,
+                                               ctypes.byref(bad), ctypes.byref(info), stream)
+        if rc == OK:
+            return out_len.value, offs, br
+        if bad.value != ctypes.c_size_t(-1).value:
+            raise GzpxError(rc, "line range %d does not lie in the stream" % bad.value, range_index=bad.value)
+        if rc == ERR_INSUFFICIENT_SPACE and out_len.value:
+            raise GzpxError(rc, "the line ranges hold %d bytes" % out_len.value, needed=out_len.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def set_lines_batch(self, inflated_bytes):
+        """Inflated bytes a batch of build_lines_device holds at most (0: the default, 256 MiB)."""
+        self.lib.check(self.lib.L.gzpx_dctx_set_lines_batch(self.h, int(inflated_bytes)))
+
+    def last_lines_members(self):
+        """Members the last line_offsets_device / read_lines_device inflated: the union over the covers."""
+        n = ctypes.c_size_t(0)
+        self.lib.check(self.lib.L.gzpx_dctx_last_lines_members(self.h, ctypes.byref(n)))
+        return n.value
+
+    def last_lines_ms(self):
+        """HIP-event durations of the last line search: (boundary tiles + locate + select, inflate, boundary search, gather)."""
+        ms = (ctypes.c_float * 4)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_lines_ms(self.h, ms))
+        return tuple(ms)
+
+    def last_lines_build_ms(self):
+        """HIP-event durations of the last build_lines_device, summed over its batches: (inflate, count)."""
+        ms = (ctypes.c_float * 2)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_lines_build_ms(self.h, ms))
+        return ms[0], ms[1]
+
     # ---- batches of raw / zlib / gzip members that lie in device memory (gzpx_wrap.h)
     def inflate_batch_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr,
                              out_cap, d_out_offsets_ptr=None, d_results_ptr=None, short_ok=False, stream=None,
@@ -993,6 +1092,39 @@ class DIndex:
     def close(self):
         if getattr(self, "h", None):
             self.lib.L.gzpx_dindex_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class DLines:
+    """gzpx_dlines: the line table of a device-resident stream, in device memory (DContext.build_lines_device)."""
+
+    def __init__(self, lib, h, n_delims, n_lines):
+        self.lib, self.h = lib, h
+        self.n_delims, self.n_lines = n_delims, n_lines
+
+    def prefix(self):
+        """P: uint64[tiles + 1], the delimiters in front of every tile of LINES_TILE inflated bytes; P[-1] = n_delims."""
+        n = ctypes.c_size_t(0)
+        self.lib.check(self.lib.L.gzpx_dlines_prefix(self.h, None, 0, ctypes.byref(n)))
+        p = np.zeros(n.value, dtype=np.uint64)
+        self.lib.check(self.lib.L.gzpx_dlines_prefix(self.h, p.ctypes.data, p.size, ctypes.byref(n)))
+        return p
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.L.gzpx_dlines_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1468,6 +1468,19 @@ struct gzpx_dctx : NoCopy {
     Allocs ck_entries;  // ck.prefix, ck.part
     Allocs ck_wgs;      // ck.carry
     uint32_t ck_width = 0;  // gzpx_dctx_set_checksum_width
+    // reads by line (gzpx_dlines_build_device and the two searches): scratch of one call at a time, used under `mu`;
+    // the searches also use rr, the staging buffer and one slot, as a read by byte range does
+    size_t lines_batch = 0;  // gzpx_dctx_set_lines_batch (0: kLinesBatchDefault)
+    Event ev_l[7];           // tiles + select [0..1], inflate [2..3], search [3..4], gather [5..6]; a build: [0..1..2] per batch
+    int ln_stages = 0;       // how many of the four stages of the last search ev_l holds
+    size_t last_ln_members = 0;
+    float ln_build_ms[2] = {0.0f, 0.0f};  // the last build's inflate and count kernels, summed over its batches
+    LinesScratch ln;
+    uint32_t *h_lrec = nullptr;  // pinned: the search record
+    Allocs ln_once;              // ln.rec, h_lrec
+    size_t ln_cap = 0;           // boundaries
+    uint64_t *h_bpos = nullptr;  // pinned: the byte positions on their way out
+    Allocs ln_bounds;            // ln.bounds, btile, bpos and h_bpos
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -2300,6 +2313,337 @@ int gzpx_dctx_last_ranges_ms(gzpx_dctx *ctx, float ms[3]) {
     if (hipEventElapsedTime(&ms[1], ctx->ev_r[2], ctx->ev_r[3]) != hipSuccess ||
         hipEventElapsedTime(&ms[2], ctx->ev_r[3], ctx->ev_r[4]) != hipSuccess)
         return GZPX_ERR_DEVICE;
+    return GZPX_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- reads by line (gzpx_lines.h)
+struct gzpx_dlines : NoCopy {
+    int device = 0, format = 0;  // the index the table was built for
+    size_t n = 0, consumed = 0;
+    uint64_t inflated_len = 0;
+    uint32_t delim = 0, tiles = 0;
+    uint64_t n_delims = 0, n_lines = 0;
+    uint64_t *d_prefix = nullptr;  // [tiles + 1] P
+    uint32_t *d_rec = nullptr;     // [8] kLnRec*: D, L, whether the last byte is a delimiter
+    Allocs mem;
+};
+
+namespace {
+
+static_assert(kLnTile == GZPX_LINES_TILE, "the public constant states the kernels' tile");
+constexpr size_t kLinesBatchDefault = (size_t)256 << 20;
+
+int ln_reserve(gzpx_dctx *c, size_t n_bounds) {
+    LinesScratch &l = c->ln;
+    if (!l.rec) {
+        GZPX_TRY(c->ln_once.dev(l.rec, 64));
+        GZPX_TRY(c->ln_once.pinned(c->h_lrec, 64));
+        for (Event &e : c->ev_l) GZPX_TRY(e.create(true));
+    }
+    Allocs &a = c->ln_bounds;
+    return grow(a, c->ln_cap, n_bounds, n_bounds + n_bounds / 4 + 64, [&](size_t cap) -> int {
+        GZPX_TRY(a.dev(l.bounds, cap * 8));
+        GZPX_TRY(a.dev(l.btile, cap * 4));
+        GZPX_TRY(a.dev(l.bpos, cap * 8));
+        return a.pinned(c->h_bpos, cap * 8);
+    });
+}
+
+// a table, an index and a context that belong together, and a stream at least as long as the index says
+bool lines_match(const gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, size_t in_len) {
+    return ix->device == c->device && ix->format == c->format && in_len >= ix->consumed && lt->device == ix->device &&
+           lt->format == ix->format && lt->n == ix->n && lt->consumed == ix->consumed && lt->inflated_len == ix->inflated_len;
+}
+
+// What the two line calls share (c->mu held, slot `si` free and the caller's for the call): n items of `per`
+// boundaries each -- line numbers, or (a, b) of line ranges -- are validated, the covers of their tiles located and
+// selected, the selected members inflated into staging and the boundary tiles walked there.  Two round trips: the
+// record in front of the inflate, the positions behind the walk.  Returns with the stream idle; c->h_bpos then holds
+// start() of every boundary and, per == 2, c->rr / c->h_out_off / *total describe the gather that is still to run.
+int lines_search(gzpx_dctx *c, int si, const gzpx_dindex *ix, const gzpx_dlines *lt, const uint8_t *d_in, const uint64_t *bounds,
+                 size_t n, uint32_t per, size_t *bad, gzpx_check_info *info, hipStream_t after, uint64_t *total) {
+    DSlot &sl = c->slots[si];
+    GZPX_TRY(dslot_reserve(sl, ix->n ? ix->n : 1));
+    GZPX_TRY(rr_reserve(c, n, ix->n));
+    GZPX_TRY(ln_reserve(c, n * per));
+    hipStream_t stream = c->stream;
+    GZPX_TRY(order_behind(stream, after, c->ev_dep));
+    Drain drain{{stream}, 1};
+    const RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
+    const LnTable tb{lt->d_prefix, lt->tiles, lt->n_delims, lt->n_lines, lt->inflated_len};
+    memcpy(c->h_ranges, bounds, n * per * 8);  // (room for 16 bytes an item)
+    HIP_TRY(hipMemcpyAsync(c->ln.bounds, c->h_ranges, n * per * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->ev_l[0], stream));
+    launch_lines_tiles(tb, (uint32_t)n, per, c->ln, c->rr, stream);
+    launch_ranges_select(rix, (uint32_t)n, 0, c->rr, sl.d_offsets, sl.d_sizes, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_l[1], stream));
+    HIP_TRY(hipMemcpyAsync(c->h_lrec, c->ln.rec, 32, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(c->h_rrec, c->rr.rec, 32, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the record: the round trip in front of the inflate
+    c->ln_stages = 1;
+    if (c->h_lrec[kLnRecBad] != 0xFFFFFFFFu || c->h_rrec[kRrRecBad] != 0xFFFFFFFFu) {
+        if (bad) *bad = c->h_lrec[kLnRecBad] != 0xFFFFFFFFu ? c->h_lrec[kLnRecBad] : c->h_rrec[kRrRecBad];
+        return GZPX_ERR_INVALID_ARG;
+    }
+    const size_t nsel = c->h_rrec[kRrRecSelected];
+    const uint64_t stage_bytes = (uint64_t)c->h_rrec[kRrRecStage] | ((uint64_t)c->h_rrec[kRrRecStage + 1] << 32);
+    GZPX_TRY(grow(c->stage_mem, c->stage_cap, (size_t)(stage_bytes + 64), (size_t)(stage_bytes + stage_bytes / 8 + 4096),
+                  [&](size_t cap) { return c->stage_mem.dev(c->d_stage, cap); }));
+    HIP_TRY(hipEventRecord(c->ev_l[2], stream));
+    if (nsel) {  // (as gzpx_read_ranges_device sizes and launches it)
+        GZPX_TRY(dslot_prepare(c, sl, nsel, c->route, (size_t)stage_bytes, (uint64_t)(ix->consumed / ix->n) * nsel));
+        launch_inflate(header_bytes(c->format), d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nsel, sl.d_blk, sl.d_out_off,
+                       c->d_stage, stage_bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, sl.ev_tm);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipEventRecord(c->ev_l[3], stream));
+    // (enqueued behind the inflate without asking how it went: whatever staging holds, the walk stays inside its tiles)
+    launch_lines_find(tb, (uint32_t)n, per, lt->delim, c->ln, c->rr, c->d_stage, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_l[4], stream));
+    HIP_TRY(hipMemcpyAsync(c->h_bpos, c->ln.bpos, n * per * 8, hipMemcpyDeviceToHost, stream));
+    if (per == 2u) {
+        HIP_TRY(hipMemcpyAsync(c->h_lrec, c->ln.rec, 32, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(c->h_out_off, c->rr.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));  // the positions: the total is known only now
+    drain.armed = false;
+    c->ln_stages = 3;
+    if (nsel) {
+        c->last_slot = si;
+        c->last_nb = nsel;
+        gzpx_check_info failed = {0, 0, 0};  // the first failing member of the selection, in stream order
+        const int verdict = summary_verdict(sl.h_summary, false, &failed);
+        if (verdict != GZPX_OK) {
+            uint32_t member = 0;  // its index in the stream, through the rank map
+            HIP_TRY(hipMemcpy(&member, c->rr.map + failed.block, 4, hipMemcpyDeviceToHost));
+            failed.block = member;
+            if (info) *info = failed;
+            return verdict;
+        }
+    }
+    c->last_ln_members = nsel;
+    if (total) *total = (uint64_t)c->h_lrec[kLnRecTotal] | ((uint64_t)c->h_lrec[kLnRecTotal + 1] << 32);
+    return GZPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void gzpx_dlines_destroy(gzpx_dlines *lt) {
+    if (!lt) return;
+    (void)hipSetDevice(lt->device);
+    delete lt;
+}
+
+int gzpx_dlines_build_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len, unsigned delim,
+                             gzpx_dlines **out, uint64_t *n_delims, uint64_t *n_lines, gzpx_check_info *info, void *hip_stream) {
+    if (!c || !ix || !out || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (n_delims) *n_delims = 0;
+    if (n_lines) *n_lines = 0;
+    if (delim > 255u) return GZPX_ERR_INVALID_ARG;
+    if (ix->device != c->device || ix->format != c->format || in_len < ix->consumed) return GZPX_ERR_INVALID_ARG;
+    const uint64_t total = ix->inflated_len;
+    const uint64_t tiles = (total + kLnTile - 1u) / kLnTile;
+    if (tiles > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    c->ln_build_ms[0] = c->ln_build_ms[1] = 0.0f;
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(c, lk, true);
+    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
+    std::unique_ptr<gzpx_dlines> lt(new (std::nothrow) gzpx_dlines());  // (c's device is current: a return frees it)
+    if (!lt) return GZPX_ERR_DEVICE;
+    lt->device = ix->device;
+    lt->format = ix->format;
+    lt->n = ix->n;
+    lt->consumed = ix->consumed;
+    lt->inflated_len = total;
+    lt->delim = delim;
+    lt->tiles = (uint32_t)tiles;
+    const size_t n = ix->n;
+    uint32_t *d_cnt = nullptr;  // [tiles] the tiles' counters: the build's own
+    Allocs tmp;
+    hipStream_t stream = c->stream;
+    Drain drain{{stream}, 1};  // (a failure: nothing still runs on the arrays when they are freed)
+    GZPX_TRY(lt->mem.dev(lt->d_prefix, (size_t)(tiles + 1) * 8));
+    GZPX_TRY(lt->mem.dev(lt->d_rec, 64));
+    GZPX_TRY(tmp.dev(d_cnt, (size_t)(tiles ? tiles : 1) * 4));
+    GZPX_TRY(ln_reserve(c, 1));  // (the events)
+    // whole members in batches of at most `batch` inflated bytes, a larger member on its own: cut on the host from the
+    // index's prefix sums
+    std::vector<uint64_t> ustart(n + 1, 0);
+    if (n) HIP_TRY(hipMemcpy(ustart.data(), ix->d_ustart, (n + 1) * 8, hipMemcpyDeviceToHost));
+    const uint64_t batch = c->lines_batch ? c->lines_batch : kLinesBatchDefault;
+    std::vector<size_t> cuts(1, 0);
+    uint64_t max_bytes = 0;
+    size_t max_members = 1;
+    for (size_t m0 = 0; m0 < n;) {
+        size_t m1 = m0 + 1;
+        while (m1 < n && ustart[m1 + 1] - ustart[m0] <= batch) m1++;
+        if (ustart[m1] - ustart[m0] > max_bytes) max_bytes = ustart[m1] - ustart[m0];
+        if (m1 - m0 > max_members) max_members = m1 - m0;
+        cuts.push_back(m1);
+        m0 = m1;
+    }
+    GZPX_TRY(dslot_reserve(sl, max_members));
+    GZPX_TRY(grow(c->stage_mem, c->stage_cap, (size_t)(max_bytes + 64), (size_t)(max_bytes + max_bytes / 8 + 4096),
+                  [&](size_t cap) { return c->stage_mem.dev(c->d_stage, cap); }));
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(tiles ? tiles : 1) * 4, stream));
+    HIP_TRY(hipMemsetAsync(lt->d_rec, 0, 64, stream));
+    for (size_t k = 0; k + 1 < cuts.size(); k++) {
+        const size_t m0 = cuts[k], nb = cuts[k + 1] - m0;
+        const uint64_t base = ustart[m0], bytes = ustart[m0 + nb] - base;
+        // (the stream's average member stands for the batch's; the members' records stay on the device)
+        GZPX_TRY(dslot_prepare(c, sl, nb, c->route, (size_t)bytes, (uint64_t)(ix->consumed / n) * nb));
+        HIP_TRY(hipEventRecord(c->ev_l[0], stream));
+        launch_inflate(header_bytes(c->format), (const uint8_t *)d_in, ix->d_off + m0, ix->d_size + m0, (uint32_t)nb, sl.d_blk,
+                       sl.d_out_off, c->d_stage, bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route,
+                       sl.ev_tm);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(c->ev_l[1], stream));
+        launch_lines_count(c->d_stage, base, bytes, total, delim, d_cnt, lt->d_rec, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_l[2], stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // (staging is the next batch's too; its verdict decides whether there is one)
+        c->last_slot = si;
+        c->last_nb = nb;
+        float ms[2] = {0.0f, 0.0f};
+        if (hipEventElapsedTime(&ms[0], c->ev_l[0], c->ev_l[1]) == hipSuccess &&
+            hipEventElapsedTime(&ms[1], c->ev_l[1], c->ev_l[2]) == hipSuccess) {
+            c->ln_build_ms[0] += ms[0];
+            c->ln_build_ms[1] += ms[1];
+        }
+        gzpx_check_info failed = {0, 0, 0};
+        const int verdict = summary_verdict(sl.h_summary, false, &failed);
+        if (verdict != GZPX_OK) {
+            failed.block += m0;  // its index in the stream
+            if (info) *info = failed;
+            drain.armed = false;
+            return verdict;
+        }
+    }
+    launch_lines_prefix(d_cnt, (uint32_t)tiles, total, lt->d_prefix, lt->d_rec, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_lrec, lt->d_rec, 32, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    lt->n_delims = (uint64_t)c->h_lrec[kLnRecD] | ((uint64_t)c->h_lrec[kLnRecD + 1] << 32);
+    lt->n_lines = (uint64_t)c->h_lrec[kLnRecL] | ((uint64_t)c->h_lrec[kLnRecL + 1] << 32);
+    if (n_delims) *n_delims = lt->n_delims;
+    if (n_lines) *n_lines = lt->n_lines;
+    *out = lt.release();
+    return GZPX_OK;
+}
+
+int gzpx_dlines_prefix(const gzpx_dlines *lt, uint64_t *prefix, size_t max_entries, size_t *n_entries) {
+    if (!lt || !n_entries) return GZPX_ERR_INVALID_ARG;
+    *n_entries = (size_t)lt->tiles + 1;
+    const size_t n_copy = prefix ? (*n_entries < max_entries ? *n_entries : max_entries) : 0;
+    if (!n_copy) return GZPX_OK;
+    if (hipSetDevice(lt->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    HIP_TRY(hipMemcpy(prefix, lt->d_prefix, n_copy * 8, hipMemcpyDeviceToHost));
+    return GZPX_OK;
+}
+
+int gzpx_line_offsets_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                             const uint64_t *lines, size_t n, uint64_t *offsets, size_t *bad, gzpx_check_info *info,
+                             void *hip_stream) {
+    if (!c || !ix || !lt || (!lines && n) || (!offsets && n) || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    if (bad) *bad = (size_t)-1;
+    if (!lines_match(c, ix, lt, in_len) || n > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    c->ln_stages = 0;
+    c->last_ln_members = 0;
+    if (n == 0) return GZPX_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, lines, n, 1u, bad, info, (hipStream_t)hip_stream, nullptr));
+    memcpy(offsets, c->h_bpos, n * 8);
+    return GZPX_OK;
+}
+
+int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                           const gzpx_range *line_ranges, size_t n_ranges, void *d_out, size_t out_cap, size_t *out_len,
+                           uint64_t *out_offsets, gzpx_range *byte_ranges, size_t *bad_range, gzpx_check_info *info,
+                           void *hip_stream) {
+    static_assert(sizeof(gzpx_range) == 16, "the kernels read and write (begin, end) pairs");
+    if (!c || !ix || !lt || !out_len || (!line_ranges && n_ranges) || (!d_in && in_len) || (!d_out && out_cap))
+        return GZPX_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (bad_range) *bad_range = (size_t)-1;
+    if (!lines_match(c, ix, lt, in_len) || n_ranges > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    c->ln_stages = 0;
+    c->last_ln_members = 0;
+    if (n_ranges == 0) {
+        if (out_offsets) out_offsets[0] = 0;
+        return GZPX_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    uint64_t total = 0;
+    GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, (const uint64_t *)line_ranges, n_ranges, 2u, bad_range, info,
+                          (hipStream_t)hip_stream, &total));
+    if (byte_ranges) memcpy(byte_ranges, c->h_bpos, n_ranges * 16);
+    if (total > out_cap) {
+        *out_len = (size_t)total;
+        return GZPX_ERR_INSUFFICIENT_SPACE;
+    }
+    if (total >> 44) return GZPX_ERR_INVALID_ARG;  // (the gather's grid)
+    if (out_offsets) memcpy(out_offsets, c->h_out_off, (n_ranges + 1) * 8);
+    hipStream_t stream = c->stream;
+    Drain drain{{stream}, 1};
+    HIP_TRY(hipEventRecord(c->ev_l[5], stream));
+    launch_ranges_gather(c->d_stage, (uint32_t)n_ranges, c->rr, (uint8_t *)d_out, total, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_l[6], stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    c->ln_stages = 4;
+    *out_len = (size_t)total;
+    return GZPX_OK;
+}
+
+int gzpx_dctx_set_lines_batch(gzpx_dctx *ctx, size_t inflated_bytes) {
+    if (!ctx) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ctx->lines_batch = inflated_bytes;
+    return GZPX_OK;
+}
+
+int gzpx_dctx_last_lines_members(gzpx_dctx *ctx, size_t *n_members_read) {
+    if (!ctx || !n_members_read) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    *n_members_read = ctx->last_ln_members;
+    return GZPX_OK;
+}
+
+int gzpx_dctx_last_lines_ms(gzpx_dctx *ctx, float ms[4]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
+    const int have = ctx->ln_stages;
+    if (have >= 1 && hipEventElapsedTime(&ms[0], ctx->ev_l[0], ctx->ev_l[1]) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (have >= 3 && (hipEventElapsedTime(&ms[1], ctx->ev_l[2], ctx->ev_l[3]) != hipSuccess ||
+                      hipEventElapsedTime(&ms[2], ctx->ev_l[3], ctx->ev_l[4]) != hipSuccess))
+        return GZPX_ERR_DEVICE;
+    if (have >= 4 && hipEventElapsedTime(&ms[3], ctx->ev_l[5], ctx->ev_l[6]) != hipSuccess) return GZPX_ERR_DEVICE;
+    return GZPX_OK;
+}
+
+int gzpx_dctx_last_lines_build_ms(gzpx_dctx *ctx, float ms[2]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ms[0] = ctx->ln_build_ms[0];
+    ms[1] = ctx->ln_build_ms[1];
     return GZPX_OK;
 }
 

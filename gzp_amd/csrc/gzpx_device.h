@@ -302,6 +302,37 @@ void launch_ranges_select(const RrIndex &ix, uint32_t n_ranges, int virt, const 
 void launch_ranges_gather(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, uint8_t *d_out, uint64_t total,
                           hipStream_t stream);
 
+// Reads by line (gzpx_lines.h).  The table of a stream, in device memory: P[t] = delimiters in front of tile t of the
+// inflated stream (tiles of kLnTile bytes); D delimiters, L lines, `total` inflated bytes.
+constexpr uint32_t kLnTile = 16384;  // GZPX_LINES_TILE
+struct LnTable {
+    const uint64_t *P;  // [tiles + 1]
+    uint32_t tiles;
+    uint64_t D, L, total;
+};
+// the records (u32 words): a table's own holds [1] whether the stream's last byte is a delimiter, [2..3] D, [4..5] L;
+// a search's holds [0] the first invalid boundary or range (0xFFFFFFFF: none) and [6..7] the bytes of output
+enum { kLnRecBad = 0, kLnRecLast = 1, kLnRecD = 2, kLnRecL = 4, kLnRecTotal = 6 };
+struct LinesScratch {
+    uint64_t *bounds = nullptr;  // [boundaries] the caller's line numbers; of a read, (a, b) of every line range
+    uint32_t *btile = nullptr;   // [boundaries] the tile a boundary lies in, 0xFFFFFFFF where none has to be walked
+    uint64_t *bpos = nullptr;    // [boundaries] start(k); of a read, (begin, end) of every range in bytes
+    uint32_t *rec = nullptr;     // [8]
+};
+// the delimiters of staging = inflated bytes [base, base + len) of a stream of `total`, added to the tiles' counters
+void launch_lines_count(const uint8_t *d_stage, uint64_t base, uint64_t len, uint64_t total, uint32_t delim, uint32_t *d_cnt,
+                        uint32_t *d_rec, hipStream_t stream);
+void launch_lines_prefix(const uint32_t *d_cnt, uint32_t tiles, uint64_t total, uint64_t *d_prefix, uint32_t *d_rec,
+                         hipStream_t stream);
+// n items of `per` boundaries each (1: line numbers, 2: line ranges): l.rec is cleared, every item validated and its
+// cover written to r.ranges, for launch_ranges_select (n ranges, uncompressed coordinates) and launch_inflate
+void launch_lines_tiles(const LnTable &tb, uint32_t n, uint32_t per, const LinesScratch &l, const RangeScratch &r,
+                        hipStream_t stream);
+// behind the inflate of the selection into d_stage: l.bpos of every boundary; per == 2: then r.src / r.out_off in the
+// form launch_ranges_gather takes, and the total in l.rec
+void launch_lines_find(const LnTable &tb, uint32_t n, uint32_t per, uint32_t delim, const LinesScratch &l, const RangeScratch &r,
+                       const uint8_t *d_stage, hipStream_t stream);
+
 // gzpx_wrap.h (k_adler32_tiles): (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);
 

@@ -5668,6 +5668,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_snap.h"
 #include "gzpx_mscan.h"
 #include "gzpx_ranges.h"
+#include "gzpx_lines.h"
 #include "gzpx_wrap.h"
 #include "gzpx_cksum.h"
 
@@ -6141,6 +6142,39 @@ void launch_ranges_gather(const uint8_t *d_stage, uint32_t n_ranges, const Range
     const uint64_t tiles = (lead + total + kRrTile - 1u) / kRrTile;
     hipLaunchKernelGGL(k_rr_gather, dim3((uint32_t)tiles), dim3(kRrThreads), 0, stream, d_stage, (const uint64_t *)r.src,
                        (const uint64_t *)r.out_off, n_ranges, d_out, lead, total);
+}
+
+// Reads by line (gzpx_lines.h).  The build: a count behind every batch of the inflate, then the prefix sums.
+void launch_lines_count(const uint8_t *d_stage, uint64_t base, uint64_t len, uint64_t total, uint32_t delim, uint32_t *d_cnt,
+                        uint32_t *d_rec, hipStream_t stream) {
+    if (!len) return;
+    const uint64_t grid = (base + len + kLnTile - 1u) / kLnTile - base / kLnTile;  // the tiles the batch has bytes of
+    hipLaunchKernelGGL(k_ln_count, dim3((uint32_t)grid), dim3(kLnThreads), 0, stream, d_stage, base, len, total, delim, d_cnt,
+                       d_rec);
+}
+
+void launch_lines_prefix(const uint32_t *d_cnt, uint32_t tiles, uint64_t total, uint64_t *d_prefix, uint32_t *d_rec,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL(k_ln_prefix, dim3(1), dim3(kLnThreads), 0, stream, d_cnt, tiles, total, d_prefix, d_rec);
+}
+
+// The search: the covers go where k_rr_locate reads its ranges; the walk of the boundary tiles runs behind the inflate.
+void launch_lines_tiles(const LnTable &tb, uint32_t n, uint32_t per, const LinesScratch &l, const RangeScratch &r,
+                        hipStream_t stream) {
+    (void)hipMemsetAsync(l.rec, 0xFF, 32, stream);
+    hipLaunchKernelGGL(k_ln_tiles, dim3((n + kLnThreads - 1u) / kLnThreads), dim3(kLnThreads), 0, stream, tb, n, per,
+                       (const uint64_t *)l.bounds, r.ranges, l.btile, l.bpos, l.rec);
+}
+
+void launch_lines_find(const LnTable &tb, uint32_t n, uint32_t per, uint32_t delim, const LinesScratch &l, const RangeScratch &r,
+                       const uint8_t *d_stage, hipStream_t stream) {
+    const uint32_t n_bounds = n * per, waves = kLnThreads / 64u;
+    hipLaunchKernelGGL(k_ln_find, dim3((n_bounds + waves - 1u) / waves), dim3(kLnThreads), 0, stream, tb, n_bounds, per, delim,
+                       (const uint64_t *)l.bounds, (const uint64_t *)r.ranges, (const uint64_t *)r.src, d_stage,
+                       (const uint32_t *)l.btile, l.bpos);
+    if (per == 2u)
+        hipLaunchKernelGGL(k_ln_offsets, dim3(1), dim3(kLnThreads), 0, stream, n, (const uint64_t *)r.ranges,
+                           (const uint64_t *)l.bpos, r.src, r.out_off, l.rec);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

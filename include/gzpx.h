@@ -376,6 +376,65 @@ int gzpx_read_ranges_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const void *d
                             void *hip_stream);
 int gzpx_dctx_last_ranges_members(gzpx_dctx *ctx, size_t *n_members_read);
 int gzpx_dctx_last_ranges_ms(gzpx_dctx *ctx, float ms[3]);
+/* ---- reads by line (gzpx_lines.h): text in a device-resident BGZF / Mgzip stream -- FASTQ, VCF, CSV, JSONL -- is
+ * fetched by LINE numbers, without the detour of inflating everything and searching it on the host.  A table of
+ * delimiter counts is built once per stream; a read then inflates only the members that hold its boundaries' tiles
+ * and its bytes.
+ * Definitions.  `delim` is one byte (default '\n'; '\r' is an ordinary byte).  T = GZPX_LINES_TILE.  D = the number
+ *   of delimiter bytes in the inflated stream.  L = the number of lines: L = D when the stream is empty or its last
+ *   byte is `delim`, else L = D + 1 (the last line is unterminated).  A line includes its delimiter.
+ *   start(k) for 0 <= k <= L: start(0) = 0; start(k) = 1 + the position of the k-th delimiter (counting from 1) for
+ *   1 <= k <= D; start(D + 1) = inflated_len when L = D + 1.  The line range [a, b), a <= b <= L, is the bytes
+ *   [start(a), start(b)).
+ *   Tile t is the inflated bytes [T t, min(T (t + 1), inflated_len)): a grid fixed on the inflated stream, independent
+ *   of the members.  P[t] = the number of delimiters in tiles 0..t-1, uint64, tiles + 1 entries, P[tiles] = D.  The
+ *   tile of boundary k, 1 <= k <= D, is the t with P[t] < k <= P[t + 1].
+ * gzpx_dlines_build_device inflates EVERY member of the index into the context's staging buffer (CRC and ISIZE checked
+ *   as everywhere), in batches of whole members of at most gzpx_dctx_set_lines_batch inflated bytes (0 = the default,
+ *   256 MiB; a larger member is a batch of its own), counts the delimiters of every tile behind each batch (a tile that
+ *   two batches share gets both parts) and forms P.  P and a record (D, L, whether the last byte is a delimiter) stay
+ *   in device memory owned by *out; *n_delims = D, *n_lines = L (both optional).  A failing member: the inflate's
+ *   error, info->block = its index in the stream, *out = NULL.  An empty stream or an index of 0 members: a valid table
+ *   with D = L = 0.  delim > 255: GZPX_ERR_INVALID_ARG.  gzpx_dlines_prefix copies P out (gzpx_dindex_entries' shape).
+ *   A table remembers the index it was built for (device, format, members, consumed, inflated_len): with another
+ *   index or context the calls below return GZPX_ERR_INVALID_ARG.
+ * gzpx_read_lines_device follows gzpx_read_ranges_device: the ranges' bytes back to back in the order given, overlaps
+ *   and duplicates repeated, empty ranges allowed ([L, L) among them), n_ranges == 0 OK; hip_stream, the lock and the
+ *   slot likewise; it returns synchronised.  A range with a > b or b > L: GZPX_ERR_INVALID_ARG, *bad_range = the
+ *   first such range, nothing inflated.
+ *   Members read.  The cover of a non-empty range [a, b) is the inflated bytes from (a == 0 ? 0 : T tile(a)) to
+ *   (b > D ? inflated_len : min(T (tile(b) + 1), inflated_len)).  The members read are the union over the covers of
+ *   [first, last] by gzpx_read_ranges_device's rule, each once, and no byte of any other member
+ *   (gzpx_dctx_last_lines_members: the size of that union in the last call).  An empty range reads nothing; its
+ *   boundary is not searched for, and byte_ranges reports it as {0, 0}.
+ *   The total is known only behind the search: above out_cap the call returns GZPX_ERR_INSUFFICIENT_SPACE with
+ *   *out_len = the bytes needed and nothing written to d_out.  A member that fails its check: the error as for
+ *   gzpx_read_ranges_device, info->block = its index in the stream, d_out holds nothing of use.  out_offsets
+ *   (n_ranges + 1) and byte_ranges (n_ranges: [start(a), start(b)) of every range) are optional HOST arrays.
+ * gzpx_line_offsets_device is the same search without the gather: offsets[i] = start(lines[i]) (host arrays),
+ *   lines[i] <= L, else GZPX_ERR_INVALID_ARG with *bad = i.  lines[i] == 0 or > D needs no member; the members read
+ *   are the union over the other boundaries' own tiles [T t, min(T (t + 1), inflated_len)).
+ * gzpx_dctx_last_lines_ms: HIP-event durations of the last search's stages: [0] boundary tiles + locate + select,
+ *   [1] inflate, [2] boundary search, [3] gather.  gzpx_dctx_last_lines_build_ms: the last build's [0] inflate and
+ *   [1] count kernels, summed over its batches. */
+#define GZPX_LINES_TILE 16384
+typedef struct gzpx_dlines gzpx_dlines;
+int gzpx_dlines_build_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const void *d_in, size_t in_len, unsigned delim,
+                             gzpx_dlines **out, uint64_t *n_delims, uint64_t *n_lines, gzpx_check_info *info,
+                             void *hip_stream);
+int gzpx_dlines_prefix(const gzpx_dlines *lines, uint64_t *prefix, size_t max_entries, size_t *n_entries);
+void gzpx_dlines_destroy(gzpx_dlines *lines);
+int gzpx_line_offsets_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in, size_t in_len,
+                             const uint64_t *line_numbers, size_t n, uint64_t *offsets, size_t *bad, gzpx_check_info *info,
+                             void *hip_stream);
+int gzpx_read_lines_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in, size_t in_len,
+                           const gzpx_range *line_ranges, size_t n_ranges, void *d_out, size_t out_cap, size_t *out_len,
+                           uint64_t *out_offsets, gzpx_range *byte_ranges, size_t *bad_range, gzpx_check_info *info,
+                           void *hip_stream);
+int gzpx_dctx_set_lines_batch(gzpx_dctx *ctx, size_t inflated_bytes);
+int gzpx_dctx_last_lines_members(gzpx_dctx *ctx, size_t *n_members_read);
+int gzpx_dctx_last_lines_ms(gzpx_dctx *ctx, float ms[4]);
+int gzpx_dctx_last_lines_build_ms(gzpx_dctx *ctx, float ms[2]);
 /* ---- batches of independent DEFLATE members that this library did not write (gzpx_wrap.h): GZIP pages of Parquet,
  * zlib chunks of HDF5 / Zarr / ORC, PNG IDAT streams, members of a multi-member gzip file whose extents are known.
  * The counterpart of libdeflate_deflate_decompress / libdeflate_zlib_decompress / libdeflate_gzip_decompress for a

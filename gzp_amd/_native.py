@@ -45,6 +45,8 @@ WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # inflate_batch_device: RFC 1951 / 195
 BATCH_SHORT_OK = 1
 CHECK_CRC32, CHECK_ADLER32, CHECK_CRC32C = 0, 1, 2  # checksum_batch_device: zlib crc32 / zlib adler32 / Castagnoli
 LINES_TILE = 16384  # GZPX_LINES_TILE: the tile of the line table, in bytes of the inflated stream
+FIND_MAX_PATTERN = 256  # GZPX_FIND_MAX_PATTERN
+FIND_NO_LINES = -1      # GZPX_FIND_NO_LINES
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -74,6 +76,7 @@ EXPORTS = [
     "gzpx_dlines_build_device", "gzpx_dlines_prefix", "gzpx_dlines_destroy", "gzpx_line_offsets_device",
     "gzpx_read_lines_device", "gzpx_dctx_set_lines_batch", "gzpx_dctx_last_lines_members", "gzpx_dctx_last_lines_ms",
     "gzpx_dctx_last_lines_build_ms",
+    "gzpx_find_device", "gzpx_dctx_last_find_ms",
 ]
 
 
@@ -277,6 +280,10 @@ class GzpxLib:
         L.gzpx_dctx_last_lines_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_dctx_last_lines_build_ms.restype = i32
         L.gzpx_dctx_last_lines_build_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_find_device.restype = i32
+        L.gzpx_find_device.argtypes = [vp, vp, vp, sz, vp, sz, ctypes.c_int, vp, vp, sz, pu64, ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_find_ms.restype = i32
+        L.gzpx_dctx_last_find_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_inflate_batch_device.restype = i32
         L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
                                                 ctypes.POINTER(GzpxCheckInfo), vp]
@@ -972,7 +979,7 @@ class DContext:
         raise GzpxError(rc, self.lib.strerror(rc))
 
     def set_lines_batch(self, inflated_bytes):
-        """Inflated bytes a batch of build_lines_device holds at most (0: the default, 256 MiB)."""
+        """Inflated bytes a batch of build_lines_device and of find_device holds at most (0: the default, 256 MiB)."""
         self.lib.check(self.lib.L.gzpx_dctx_set_lines_batch(self.h, int(inflated_bytes)))
 
     def last_lines_members(self):
@@ -992,6 +999,32 @@ class DContext:
         ms = (ctypes.c_float * 2)()
         self.lib.check(self.lib.L.gzpx_dctx_last_lines_build_ms(self.h, ms))
         return ms[0], ms[1]
+
+    # ---- search (gzpx_find.h)
+    def find_device(self, index, d_in_ptr, in_len, pattern, delim=None, d_positions_ptr=None, d_lines_ptr=None, hits_cap=0,
+                    stream=None):
+        """Every position of the inflated stream at which the bytes `pattern` start, ascending, into the device array
+        d_positions_ptr (uint64[hits_cap]) and, for the delimiter byte `delim`, the line of each into d_lines_ptr; either
+        may be None, both None counts only.  Returns n_hits.  More hits than hits_cap: the first hits_cap are written and
+        GzpxError is raised with .needed = n_hits."""
+        pat = bytes(pattern)
+        n = ctypes.c_uint64(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_find_device(self.h, index.h, d_in_ptr, in_len, pat, len(pat), FIND_NO_LINES if delim is None else int(delim),
+                                         d_positions_ptr, d_lines_ptr, hits_cap, ctypes.byref(n), ctypes.byref(info), stream)
+        if rc == OK:
+            return n.value
+        if rc == ERR_INSUFFICIENT_SPACE and n.value:
+            raise GzpxError(rc, "the stream holds %d hits" % n.value, needed=n.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def last_find_ms(self):
+        """HIP-event durations of the last find_device, summed over its batches: (inflate, count, write)."""
+        ms = (ctypes.c_float * 3)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_find_ms(self.h, ms))
+        return ms[0], ms[1], ms[2]
 
     # ---- batches of raw / zlib / gzip members that lie in device memory (gzpx_wrap.h)
     def inflate_batch_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr,

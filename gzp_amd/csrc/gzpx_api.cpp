@@ -1481,6 +1481,16 @@ struct gzpx_dctx : NoCopy {
     size_t ln_cap = 0;           // boundaries
     uint64_t *h_bpos = nullptr;  // pinned: the byte positions on their way out
     Allocs ln_bounds;            // ln.bounds, btile, bpos and h_bpos
+    // search (gzpx_find_device): scratch of one call at a time, used under `mu`; the batches, the staging buffer and
+    // one slot as a line-table build uses them
+    Event ev_f[4];                         // per batch: inflate [0..1], count + scan [1..2], write + carry [2..3]
+    float fd_ms[3] = {0.0f, 0.0f, 0.0f};  // the last call's, summed over its batches
+    FindScratch fd;
+    uint32_t *h_fpat = nullptr;  // pinned: the pattern on its way in
+    uint64_t *h_frec = nullptr;  // pinned: the record on its way out
+    Allocs fd_once;              // fd.pat, fd.rec and the two pinned arrays above
+    size_t fd_piece_cap = 0;
+    Allocs fd_pieces;            // fd.cnt, fd.bases
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -2540,6 +2550,118 @@ int gzpx_dlines_build_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_
     if (n_delims) *n_delims = lt->n_delims;
     if (n_lines) *n_lines = lt->n_lines;
     *out = lt.release();
+    return GZPX_OK;
+}
+
+int gzpx_find_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *pattern,
+                     size_t pattern_len, int delim, uint64_t *d_positions, uint64_t *d_lines, size_t hits_cap, uint64_t *n_hits,
+                     gzpx_check_info *info, void *hip_stream) {
+    static_assert(kFdMaxPattern == GZPX_FIND_MAX_PATTERN, "the public constant states the kernels' limit");
+    if (!c || !ix || !n_hits || !pattern || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_hits = 0;
+    if (pattern_len == 0 || pattern_len > kFdMaxPattern || delim < GZPX_FIND_NO_LINES || delim > 255) return GZPX_ERR_INVALID_ARG;
+    if (d_lines && delim == GZPX_FIND_NO_LINES) return GZPX_ERR_INVALID_ARG;
+    if (ix->device != c->device || ix->format != c->format || in_len < ix->consumed) return GZPX_ERR_INVALID_ARG;
+    const uint64_t total = ix->inflated_len;
+    const size_t n = ix->n;
+    const uint32_t m = (uint32_t)pattern_len;
+    const bool writes = d_positions || d_lines;
+    const uint64_t cap = writes ? hits_cap : 0;
+    std::unique_lock<std::mutex> lk(c->mu);
+    c->fd_ms[0] = c->fd_ms[1] = c->fd_ms[2] = 0.0f;
+    if (!n || m > total) return GZPX_OK;  // (no position can hold the pattern: nothing is inflated)
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(c, lk, true);
+    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
+    FindScratch &f = c->fd;
+    if (!f.rec) {
+        GZPX_TRY(c->fd_once.dev(f.pat, kFdMaxPattern));
+        GZPX_TRY(c->fd_once.dev(f.rec, kFdRecWords * 8));
+        GZPX_TRY(c->fd_once.pinned(c->h_fpat, kFdMaxPattern));
+        GZPX_TRY(c->fd_once.pinned(c->h_frec, kFdRecWords * 8));
+        for (Event &e : c->ev_f) GZPX_TRY(e.create(true));
+    }
+    hipStream_t stream = c->stream;
+    Drain drain{{stream}, 1};
+    // whole members in batches, cut as gzpx_dlines_build_device cuts them
+    std::vector<uint64_t> ustart(n + 1, 0);
+    HIP_TRY(hipMemcpy(ustart.data(), ix->d_ustart, (n + 1) * 8, hipMemcpyDeviceToHost));
+    const uint64_t batch = c->lines_batch ? c->lines_batch : kLinesBatchDefault;
+    std::vector<size_t> cuts(1, 0);
+    uint64_t max_bytes = 0;
+    size_t max_members = 1;
+    for (size_t m0 = 0; m0 < n;) {
+        size_t m1 = m0 + 1;
+        while (m1 < n && ustart[m1 + 1] - ustart[m0] <= batch) m1++;
+        if (ustart[m1] - ustart[m0] > max_bytes) max_bytes = ustart[m1] - ustart[m0];
+        if (m1 - m0 > max_members) max_members = m1 - m0;
+        cuts.push_back(m1);
+        m0 = m1;
+    }
+    GZPX_TRY(dslot_reserve(sl, max_members));
+    const size_t stage_need = (size_t)(kFdPad + max_bytes + 64);
+    GZPX_TRY(grow(c->stage_mem, c->stage_cap, stage_need, stage_need + (size_t)(max_bytes / 8) + 4096,
+                  [&](size_t cap_bytes) { return c->stage_mem.dev(c->d_stage, cap_bytes); }));
+    const size_t pieces = (size_t)find_pieces(max_bytes);
+    GZPX_TRY(grow(c->fd_pieces, c->fd_piece_cap, pieces, pieces + pieces / 8 + 16, [&](size_t cap_pieces) -> int {
+        GZPX_TRY(c->fd_pieces.dev(f.cnt, cap_pieces * 8));
+        return c->fd_pieces.dev(f.bases, cap_pieces * 16);
+    }));
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    memset(c->h_fpat, 0, kFdMaxPattern);
+    memcpy(c->h_fpat, pattern, m);
+    HIP_TRY(hipMemcpyAsync(f.pat, c->h_fpat, kFdMaxPattern, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(f.rec, 0, kFdRecWords * 8, stream));
+    uint8_t *const out = c->d_stage + kFdPad;  // the inflate writes behind the pad
+    for (size_t k = 0; k + 1 < cuts.size(); k++) {
+        const size_t m0 = cuts[k], nb = cuts[k + 1] - m0;
+        const uint64_t base = ustart[m0], bytes = ustart[m0 + nb] - base;
+        const FindBatch fb{c->d_stage, base, bytes, (uint32_t)(base < m - 1u ? base : m - 1u), m, d_lines ? delim : GZPX_FIND_NO_LINES};
+        GZPX_TRY(dslot_prepare(c, sl, nb, c->route, (size_t)bytes, (uint64_t)(ix->consumed / n) * nb));
+        HIP_TRY(hipEventRecord(c->ev_f[0], stream));
+        launch_inflate(header_bytes(c->format), (const uint8_t *)d_in, ix->d_off + m0, ix->d_size + m0, (uint32_t)nb, sl.d_blk,
+                       sl.d_out_off, out, bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, sl.ev_tm);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(c->ev_f[1], stream));
+        // (enqueued behind the inflate without asking how it went: whatever staging holds, the search stays inside it)
+        if (bytes) launch_find_count(fb, f, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_f[2], stream));
+        if (bytes && cap) launch_find_write(fb, f, d_positions, d_lines, cap, stream);
+        const uint64_t seen = base + bytes;
+        const uint32_t carry = (uint32_t)(seen < m - 1u ? seen : m - 1u);  // (a batch shorter than that appends to the carry)
+        if (bytes && carry && k + 2 < cuts.size()) launch_find_carry(fb, f, carry, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_f[3], stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // (staging is the next batch's too; its verdict decides whether there is one)
+        c->last_slot = si;
+        c->last_nb = nb;
+        float ms[3] = {0.0f, 0.0f, 0.0f};
+        if (hipEventElapsedTime(&ms[0], c->ev_f[0], c->ev_f[1]) == hipSuccess &&
+            hipEventElapsedTime(&ms[1], c->ev_f[1], c->ev_f[2]) == hipSuccess &&
+            hipEventElapsedTime(&ms[2], c->ev_f[2], c->ev_f[3]) == hipSuccess)
+            for (int j = 0; j < 3; j++) c->fd_ms[j] += ms[j];
+        gzpx_check_info failed = {0, 0, 0};
+        const int verdict = summary_verdict(sl.h_summary, false, &failed);
+        if (verdict != GZPX_OK) {
+            failed.block += m0;  // its index in the stream
+            if (info) *info = failed;
+            drain.armed = false;
+            return verdict;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_frec, f.rec, kFdRecWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    *n_hits = c->h_frec[kFdRecHits];
+    return writes && *n_hits > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
+}
+
+int gzpx_dctx_last_find_ms(gzpx_dctx *ctx, float ms[3]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    for (int j = 0; j < 3; j++) ms[j] = ctx->fd_ms[j];
     return GZPX_OK;
 }
 

@@ -333,6 +333,35 @@ void launch_lines_tiles(const LnTable &tb, uint32_t n, uint32_t per, const Lines
 void launch_lines_find(const LnTable &tb, uint32_t n, uint32_t per, uint32_t delim, const LinesScratch &l, const RangeScratch &r,
                        const uint8_t *d_stage, hipStream_t stream);
 
+// Search (gzpx_find.h).  Staging of a batch: kFdPad bytes, of which the last `carry` are the end of the earlier
+// batches, then the batch's `len` inflated bytes (16 readable bytes behind them); `base` is where the batch starts in
+// the inflated stream.  The region [kFdPad - carry, kFdPad + len) is searched in pieces of kFdPiece bytes of staging.
+constexpr uint32_t kFdMaxPattern = 256;  // GZPX_FIND_MAX_PATTERN
+constexpr uint32_t kFdPad = 256;
+constexpr uint32_t kFdPiece = 16384;
+// the record (u64 words): hits and delimiters of the batches so far, and how many of those delimiters lie in the carry
+enum { kFdRecHits = 0, kFdRecDelims = 1, kFdRecCarry = 2, kFdRecWords = 4 };
+struct FindScratch {
+    uint32_t *pat = nullptr;    // [kFdMaxPattern / 4] the pattern, the tail zero
+    uint32_t *cnt = nullptr;    // [2 * pieces] (hits, delimiters) of every piece of a batch
+    uint64_t *bases = nullptr;  // [2 * pieces] (rank of the first hit, delimiters in front) of every piece
+    uint64_t *rec = nullptr;    // [kFdRecWords]
+};
+struct FindBatch {
+    uint8_t *stage;
+    uint64_t base, len;
+    uint32_t carry, m;
+    int delim;  // -1: no line numbers
+};
+inline uint64_t find_pieces(uint64_t len) { return (kFdPad + len + kFdPiece - 1u) / kFdPiece; }  // of a batch, at most
+// count + scan of one batch (len > 0): f.cnt, f.bases and the record
+void launch_find_count(const FindBatch &b, const FindScratch &f, hipStream_t stream);
+// behind launch_find_count: the batch's hits below rank `cap` into d_positions / d_lines (either may be null)
+void launch_find_write(const FindBatch &b, const FindScratch &f, uint64_t *d_positions, uint64_t *d_lines, uint64_t cap,
+                       hipStream_t stream);
+// behind both: the last `n` <= m - 1 bytes of the region become the next batch's carry
+void launch_find_carry(const FindBatch &b, const FindScratch &f, uint32_t n, hipStream_t stream);
+
 // gzpx_wrap.h (k_adler32_tiles): (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);
 

@@ -5669,6 +5669,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_mscan.h"
 #include "gzpx_ranges.h"
 #include "gzpx_lines.h"
+#include "gzpx_find.h"
 #include "gzpx_wrap.h"
 #include "gzpx_cksum.h"
 
@@ -6175,6 +6176,34 @@ void launch_lines_find(const LnTable &tb, uint32_t n, uint32_t per, uint32_t del
     if (per == 2u)
         hipLaunchKernelGGL(k_ln_offsets, dim3(1), dim3(kLnThreads), 0, stream, n, (const uint64_t *)r.ranges,
                            (const uint64_t *)l.bpos, r.src, r.out_off, l.rec);
+}
+
+// The search (gzpx_find.h), behind the inflate of a batch into staging.
+static FdArgs find_args(const FindBatch &b, uint32_t &x0, uint32_t &grid) {
+    const uint64_t r0 = kFdPad - b.carry, r1 = kFdPad + b.len;
+    x0 = (uint32_t)(r0 / kFdPiece);
+    grid = (uint32_t)((r1 + kFdPiece - 1u) / kFdPiece) - x0;
+    return FdArgs{b.stage, r0, r1, b.base, b.m, b.delim >= 0 ? 1u : 0u, b.delim >= 0 ? (uint32_t)b.delim : 0u};
+}
+
+void launch_find_count(const FindBatch &b, const FindScratch &f, hipStream_t stream) {
+    uint32_t x0, grid;
+    const FdArgs a = find_args(b, x0, grid);
+    hipLaunchKernelGGL(k_fd_count, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat, f.cnt);
+    hipLaunchKernelGGL(k_fd_scan, dim3(1), dim3(kFdThreads), 0, stream, (const uint32_t *)f.cnt, grid, f.bases, f.rec);
+}
+
+void launch_find_write(const FindBatch &b, const FindScratch &f, uint64_t *d_positions, uint64_t *d_lines, uint64_t cap,
+                       hipStream_t stream) {
+    uint32_t x0, grid;
+    const FdArgs a = find_args(b, x0, grid);
+    hipLaunchKernelGGL(k_fd_write, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat,
+                       (const uint32_t *)f.cnt, (const uint64_t *)f.bases, d_positions, d_lines, cap);
+}
+
+void launch_find_carry(const FindBatch &b, const FindScratch &f, uint32_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(k_fd_carry, dim3(1), dim3(kFdThreads), 0, stream, b.stage, kFdPad + b.len - n, n,
+                       b.delim >= 0 ? 1u : 0u, b.delim >= 0 ? (uint32_t)b.delim : 0u, f.rec);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

@@ -391,7 +391,7 @@ int gzpx_dctx_last_ranges_ms(gzpx_dctx *ctx, float ms[3]);
  *   tile of boundary k, 1 <= k <= D, is the t with P[t] < k <= P[t + 1].
  * gzpx_dlines_build_device inflates EVERY member of the index into the context's staging buffer (CRC and ISIZE checked
  *   as everywhere), in batches of whole members of at most gzpx_dctx_set_lines_batch inflated bytes (0 = the default,
- *   256 MiB; a larger member is a batch of its own), counts the delimiters of every tile behind each batch (a tile that
+ *   256 MiB; a larger member is a batch of its own; the value serves gzpx_find_device too), counts the delimiters of every tile behind each batch (a tile that
  *   two batches share gets both parts) and forms P.  P and a record (D, L, whether the last byte is a delimiter) stay
  *   in device memory owned by *out; *n_delims = D, *n_lines = L (both optional).  A failing member: the inflate's
  *   error, info->block = its index in the stream, *out = NULL.  An empty stream or an index of 0 members: a valid table
@@ -435,6 +435,41 @@ int gzpx_dctx_set_lines_batch(gzpx_dctx *ctx, size_t inflated_bytes);
 int gzpx_dctx_last_lines_members(gzpx_dctx *ctx, size_t *n_members_read);
 int gzpx_dctx_last_lines_ms(gzpx_dctx *ctx, float ms[4]);
 int gzpx_dctx_last_lines_build_ms(gzpx_dctx *ctx, float ms[2]);
+/* ---- search (gzpx_find.h): WHERE a byte string occurs in a device-resident BGZF / Mgzip stream -- the records whose
+ * name starts with a prefix, the lines of one contig ("\nchr7\t"), an adapter sequence -- as byte positions for
+ * gzpx_read_ranges_device and line numbers for gzpx_read_lines_device, with nothing but a table of hits leaving the
+ * device.
+ * Definitions.  `plain` is the inflated stream of the index, n = inflated_len.  The pattern is a HOST array of m bytes,
+ *   1 <= m <= GZPX_FIND_MAX_PATTERN, any byte values.  A HIT is a position p, 0 <= p <= n - m, with
+ *   plain[p .. p + m) == pattern.  Overlapping hits all count ("aa" in "aaaa": 0, 1, 2); hits are reported in
+ *   ascending p.  Where in the stream a hit lies plays no part: it may straddle 16-byte words, members (empty members
+ *   between them included) and the batches of the inflate.
+ *   The LINE of a hit is the number of `delim` bytes in plain[0 .. p): the line that holds the hit's FIRST byte, in the
+ *   numbering of the reads by line, start(line) <= p < start(line + 1).  A pattern may contain the delimiter
+ *   ("\n@SRR" anchors at a line start; its hits lie in the line that the "\n" ends).  No gzpx_dlines table is needed.
+ * gzpx_find_device inflates EVERY member of the index once into the context's staging buffer (CRC and ISIZE checked as
+ *   everywhere), in the batches of gzpx_dlines_build_device -- gzpx_dctx_set_lines_batch serves both calls -- and
+ *   searches each batch behind its inflate: a batch finds the hits whose last byte lies in it, from the last m - 1
+ *   bytes of the earlier batches kept in front of it.  A count-only call and a writing call inflate once each.
+ *   d_positions and d_lines are DEVICE arrays of hits_cap uint64 entries; each is optional.  Both NULL: count only,
+ *   hits_cap is ignored, GZPX_OK.  *n_hits is always the number of hits in the whole stream.  When it exceeds hits_cap
+ *   and an output array was given, the first hits_cap hits are written, nothing behind hits_cap entries is touched and
+ *   the call returns GZPX_ERR_INSUFFICIENT_SPACE: call again with the size now known.
+ *   delim is a byte value, or GZPX_FIND_NO_LINES; outside -1..255, or GZPX_FIND_NO_LINES with d_lines given:
+ *   GZPX_ERR_INVALID_ARG.  pattern_len 0 or above GZPX_FIND_MAX_PATTERN: GZPX_ERR_INVALID_ARG.  m > n, an empty stream
+ *   or an index of 0 members: GZPX_OK with 0 hits and nothing inflated.
+ *   Index and context as for gzpx_dlines_build_device: device, format and in_len >= consumed are checked, the
+ *   context's lock is taken, one slot is used, hip_stream is ordered in front, the call returns synchronised.  A
+ *   failing member ends the call with the inflate's error, info->block = its index in the stream, *n_hits = 0, and
+ *   the output arrays hold nothing of use.
+ * gzpx_dctx_last_find_ms: HIP-event durations of the last call, summed over its batches: [0] inflate, [1] counting
+ *   pass + scan, [2] writing pass + carry. */
+#define GZPX_FIND_MAX_PATTERN 256
+#define GZPX_FIND_NO_LINES (-1)
+int gzpx_find_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *pattern,
+                     size_t pattern_len, int delim, uint64_t *d_positions, uint64_t *d_lines, size_t hits_cap, uint64_t *n_hits,
+                     gzpx_check_info *info, void *hip_stream);
+int gzpx_dctx_last_find_ms(gzpx_dctx *ctx, float ms[3]);
 /* ---- batches of independent DEFLATE members that this library did not write (gzpx_wrap.h): GZIP pages of Parquet,
  * zlib chunks of HDF5 / Zarr / ORC, PNG IDAT streams, members of a multi-member gzip file whose extents are known.
  * The counterpart of libdeflate_deflate_decompress / libdeflate_zlib_decompress / libdeflate_gzip_decompress for a

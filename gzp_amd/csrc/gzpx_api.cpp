@@ -1355,6 +1355,8 @@ uint32_t gzpx_adler32(uint32_t adler, const void *buf, size_t n) {
     return t_last_status == GZPX_OK ? out : adler;
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------- ParDecompress side
 namespace {
 
@@ -1418,9 +1420,168 @@ int dslot_reserve(DSlot &c, size_t nb) {
     });
 }
 
+// What each kind of call keeps in its context: scratch, pinned mirrors, capacities, events and what the getters may
+// read of them, used by one call at a time under the context's mutex.  (Destroyed last to first: memory, then events.)
+
+// member discovery (gzpx_*_device calls that take no member table)
+struct ScanState : NoCopy {
+    Event ev0, ev1;  // around the scan kernels
+    bool have = false;
+    MemberScanScratch ms;
+    uint32_t *h_rec = nullptr;  // pinned: the scan record
+    Allocs once;                // ms.rec, h_rec
+    size_t seg_cap = 0;
+    Allocs seg;   // ms.seg_count, ms.seg_off
+    Allocs cand;  // the six candidate arrays of ms.cap entries
+    uint64_t *d_tab_off = nullptr;  // the walk's table for gzpx_scan_blocks_device
+    uint32_t *d_tab_size = nullptr;
+    size_t tab_cap = 0;
+    Allocs tab_mem;
+    int reserve(size_t n_seg, size_t cap) {
+        if (!ms.rec) {
+            GZPX_TRY(once.dev(ms.rec, 64));
+            GZPX_TRY(once.pinned(h_rec, 64));
+            GZPX_TRY(ev0.create(true));
+            GZPX_TRY(ev1.create(true));
+        }
+        GZPX_TRY(grow(seg, seg_cap, n_seg, n_seg, [&](size_t n) -> int {
+            GZPX_TRY(seg.dev(ms.seg_count, n * 4));
+            return seg.dev(ms.seg_off, n * 4);
+        }));
+        return grow(cand, ms.cap, cap, cap, [&](size_t n) -> int {
+            GZPX_TRY(cand.dev(ms.pos, n * 8));
+            GZPX_TRY(cand.dev(ms.size, n * 4));
+            GZPX_TRY(cand.dev(ms.succ, n * 4));
+            GZPX_TRY(cand.dev(ms.jump[0], n * 4));
+            GZPX_TRY(cand.dev(ms.jump[1], n * 4));
+            return cand.dev(ms.idx, n * 4);
+        });
+    }
+};
+
+// reads by range (gzpx_read_ranges_device); the line searches select their members with it too
+struct RangesState : NoCopy {
+    Event ev[5];        // select [0..1], inflate [2..3], gather [3..4]
+    bool have = false;  // ev[0..1] hold the last call's select; stages: [2..4] its inflate and gather
+    bool stages = false;
+    size_t last_members = 0;
+    RangeScratch rr;
+    uint32_t *h_rec = nullptr;  // pinned: the record of locate + select
+    Allocs once;                // rr.rec, h_rec
+    size_t range_cap = 0, member_cap = 0;
+    uint64_t *h_ranges = nullptr;   // pinned: the caller's ranges on their way in
+    uint64_t *h_out_off = nullptr;  // pinned: out_offsets on their way out
+    Allocs ranges;   // rr.ranges, first, len, src, out_off and the two pinned arrays above
+    Allocs members;  // rr.diff, map, soff
+    int reserve(size_t n_ranges, size_t n_members) {
+        if (!rr.rec) {
+            GZPX_TRY(once.dev(rr.rec, 64));
+            GZPX_TRY(once.pinned(h_rec, 64));
+            for (Event &e : ev) GZPX_TRY(e.create(true));
+        }
+        GZPX_TRY(grow(ranges, range_cap, n_ranges, n_ranges + n_ranges / 4 + 64, [&](size_t cap) -> int {
+            GZPX_TRY(ranges.dev(rr.ranges, cap * 16));
+            GZPX_TRY(ranges.dev(rr.first, cap * 4));
+            GZPX_TRY(ranges.dev(rr.len, cap * 8));
+            GZPX_TRY(ranges.dev(rr.src, cap * 8));
+            GZPX_TRY(ranges.dev(rr.out_off, (cap + 1) * 8));
+            GZPX_TRY(ranges.pinned(h_ranges, cap * 16));
+            return ranges.pinned(h_out_off, (cap + 1) * 8);
+        }));
+        return grow(members, member_cap, n_members + 1, n_members + n_members / 4 + 64, [&](size_t cap) -> int {
+            GZPX_TRY(members.dev(rr.diff, cap * 4));
+            GZPX_TRY(members.dev(rr.map, cap * 4));
+            return members.dev(rr.soff, cap * 8);
+        });
+    }
+};
+
+// members inflated back to back for a read by range, a line call or a search: room for `bytes` and 64 more
+struct Staging : NoCopy {
+    uint8_t *d = nullptr;
+    size_t cap = 0;
+    Allocs mem;
+    int reserve(uint64_t bytes) {
+        return grow(mem, cap, (size_t)(bytes + 64), (size_t)(bytes + bytes / 8 + 4096), [&](size_t n) { return mem.dev(d, n); });
+    }
+};
+
+// checksums of a table (gzpx_checksum_batch_device); the record and the events are a slot's
+struct CksumState : NoCopy {
+    CksumScratch ck;
+    size_t entry_cap = 0, wg_cap = 0;
+    Allocs entries;      // ck.prefix, ck.part
+    Allocs wgs;          // ck.carry
+    uint32_t width = 0;  // gzpx_dctx_set_checksum_width
+    int reserve(size_t n, uint32_t workgroups) {
+        GZPX_TRY(grow(entries, entry_cap, n, n + n / 4 + 64, [&](size_t cap) -> int {
+            GZPX_TRY(entries.dev(ck.prefix, (cap + 1) * 8));
+            return entries.dev(ck.part, cap * 4);
+        }));
+        return grow(wgs, wg_cap, workgroups, workgroups, [&](size_t cap) { return wgs.dev(ck.carry, cap * 8); });
+    }
+};
+
+static_assert(kLnTile == GZPX_LINES_TILE, "the public constant states the kernels' tile");
+constexpr size_t kLinesBatchDefault = (size_t)256 << 20;
+
+// reads by line (gzpx_dlines_build_device and the two searches); the searches also use the ranges' state, the staging
+// buffer and one slot, as a read by byte range does
+struct LinesState : NoCopy {
+    size_t batch = 0;  // gzpx_dctx_set_lines_batch (0: kLinesBatchDefault); the search's batches too
+    Event ev[7];       // tiles + select [0..1], inflate [2..3], search [3..4], gather [5..6]; a build: [0..1..2] per batch
+    int stages = 0;    // how many of the four stages of the last search ev holds
+    size_t last_members = 0;
+    float build_ms[2] = {0.0f, 0.0f};  // the last build's inflate and count kernels, summed over its batches
+    LinesScratch ln;
+    uint32_t *h_rec = nullptr;  // pinned: the search record
+    Allocs once;                // ln.rec, h_rec
+    size_t cap = 0;             // boundaries
+    uint64_t *h_bpos = nullptr;  // pinned: the byte positions on their way out
+    Allocs bounds;               // ln.bounds, btile, bpos and h_bpos
+    int reserve(size_t n_bounds) {
+        if (!ln.rec) {
+            GZPX_TRY(once.dev(ln.rec, 64));
+            GZPX_TRY(once.pinned(h_rec, 64));
+            for (Event &e : ev) GZPX_TRY(e.create(true));
+        }
+        return grow(bounds, cap, n_bounds, n_bounds + n_bounds / 4 + 64, [&](size_t n) -> int {
+            GZPX_TRY(bounds.dev(ln.bounds, n * 8));
+            GZPX_TRY(bounds.dev(ln.btile, n * 4));
+            GZPX_TRY(bounds.dev(ln.bpos, n * 8));
+            return bounds.pinned(h_bpos, n * 8);
+        });
+    }
+};
+
+// search (gzpx_find_device): the batches, the staging buffer and one slot as a line-table build uses them
+struct FindState : NoCopy {
+    Event ev[4];                       // per batch: inflate [0..1], count + scan [1..2], write + carry [2..3]
+    float ms[3] = {0.0f, 0.0f, 0.0f};  // the last call's, summed over its batches
+    FindScratch fd;
+    uint32_t *h_pat = nullptr;  // pinned: the pattern on its way in
+    uint64_t *h_rec = nullptr;  // pinned: the record on its way out
+    Allocs once;                // fd.pat, fd.rec and the two pinned arrays above
+    size_t piece_cap = 0;
+    Allocs pieces;  // fd.cnt, fd.bases
+    int reserve(size_t n_pieces) {
+        if (!fd.rec) {
+            GZPX_TRY(once.dev(fd.pat, kFdMaxPattern));
+            GZPX_TRY(once.dev(fd.rec, kFdRecWords * 8));
+            GZPX_TRY(once.pinned(h_pat, kFdMaxPattern));
+            GZPX_TRY(once.pinned(h_rec, kFdRecWords * 8));
+            for (Event &e : ev) GZPX_TRY(e.create(true));
+        }
+        return grow(pieces, piece_cap, n_pieces, n_pieces + n_pieces / 8 + 16, [&](size_t cap) -> int {
+            GZPX_TRY(pieces.dev(fd.cnt, cap * 8));
+            return pieces.dev(fd.bases, cap * 16);
+        });
+    }
+};
+
 }  // namespace
 
-// (members are destroyed last to first: memory, then events, then streams)
+// (members are destroyed last to first: memory and events of the slots and of each kind of call, then the streams)
 struct gzpx_dctx : NoCopy {
     int device = 0;
     int format = 0;
@@ -1433,70 +1594,21 @@ struct gzpx_dctx : NoCopy {
     int route = kInflateRouteSeg;  // GZPX_INFLATE_ROUTE=wave / gzpx_dctx_set_route: k_inflate for every member
     int last_slot = -1;  // the slot of the last completed launch (timing / debug counters)
     size_t last_nb = 0;
-    // member discovery (gzpx_*_device calls that take no member table): scratch of one scan at a time, used under `mu`
-    Event ev_s0, ev_s1;  // around the scan kernels (created with scan_once)
-    bool have_scan = false;
-    MemberScanScratch ms;
-    uint32_t *h_rec = nullptr;  // pinned: the scan record
-    Allocs scan_once;           // ms.rec, h_rec
-    size_t ms_seg_cap = 0;
-    Allocs scan_seg;   // ms.seg_count, ms.seg_off
-    Allocs scan_cand;  // the six candidate arrays of ms.cap entries
-    uint64_t *d_tab_off = nullptr;  // the walk's table for gzpx_scan_blocks_device
-    uint32_t *d_tab_size = nullptr;
-    size_t tab_cap = 0;
-    Allocs tab_mem;
-    // reads by range (gzpx_read_ranges_device): scratch of one call at a time, used under `mu`
-    Event ev_r[5];         // select [0..1], inflate [2..3], gather [3..4] (created with rr_once)
-    bool have_rr = false;  // ev_r[0..1] hold the last call's select; rr_stages: [2..4] its inflate and gather
-    bool rr_stages = false;
-    size_t last_rr_members = 0;
-    RangeScratch rr;
-    uint32_t *h_rrec = nullptr;  // pinned: the record of locate + select
-    Allocs rr_once;              // rr.rec, h_rrec
-    size_t rr_range_cap = 0, rr_member_cap = 0;
-    uint64_t *h_ranges = nullptr;   // pinned: the caller's ranges on their way in
-    uint64_t *h_out_off = nullptr;  // pinned: out_offsets on their way out
-    Allocs rr_ranges;   // rr.ranges, first, len, src, out_off and the two pinned arrays above
-    Allocs rr_members;  // rr.diff, map, soff
-    uint8_t *d_stage = nullptr;  // the selected members, inflated back to back
-    size_t stage_cap = 0;
-    Allocs stage_mem;
-    // checksums of a table (gzpx_checksum_batch_device): scratch of one call at a time, used under `mu`
-    CksumScratch ck;
-    size_t ck_entry_cap = 0, ck_wg_cap = 0;
-    Allocs ck_entries;  // ck.prefix, ck.part
-    Allocs ck_wgs;      // ck.carry
-    uint32_t ck_width = 0;  // gzpx_dctx_set_checksum_width
-    // reads by line (gzpx_dlines_build_device and the two searches): scratch of one call at a time, used under `mu`;
-    // the searches also use rr, the staging buffer and one slot, as a read by byte range does
-    size_t lines_batch = 0;  // gzpx_dctx_set_lines_batch (0: kLinesBatchDefault)
-    Event ev_l[7];           // tiles + select [0..1], inflate [2..3], search [3..4], gather [5..6]; a build: [0..1..2] per batch
-    int ln_stages = 0;       // how many of the four stages of the last search ev_l holds
-    size_t last_ln_members = 0;
-    float ln_build_ms[2] = {0.0f, 0.0f};  // the last build's inflate and count kernels, summed over its batches
-    LinesScratch ln;
-    uint32_t *h_lrec = nullptr;  // pinned: the search record
-    Allocs ln_once;              // ln.rec, h_lrec
-    size_t ln_cap = 0;           // boundaries
-    uint64_t *h_bpos = nullptr;  // pinned: the byte positions on their way out
-    Allocs ln_bounds;            // ln.bounds, btile, bpos and h_bpos
-    // search (gzpx_find_device): scratch of one call at a time, used under `mu`; the batches, the staging buffer and
-    // one slot as a line-table build uses them
-    Event ev_f[4];                         // per batch: inflate [0..1], count + scan [1..2], write + carry [2..3]
-    float fd_ms[3] = {0.0f, 0.0f, 0.0f};  // the last call's, summed over its batches
-    FindScratch fd;
-    uint32_t *h_fpat = nullptr;  // pinned: the pattern on its way in
-    uint64_t *h_frec = nullptr;  // pinned: the record on its way out
-    Allocs fd_once;              // fd.pat, fd.rec and the two pinned arrays above
-    size_t fd_piece_cap = 0;
-    Allocs fd_pieces;            // fd.cnt, fd.bases
+    ScanState scan;
+    RangesState ranges;
+    Staging stage;
+    CksumState cksum;
+    LinesState lines;
+    FindState find;
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
 };
 
 namespace {
+
+// the 64-bit field of a record of 32-bit words that starts at `word`
+uint64_t rec_u64(const uint32_t *rec, size_t word) { return (uint64_t)rec[word] | ((uint64_t)rec[word + 1] << 32); }
 
 // what the device's walk found (dscan_run): the table itself stays in the context's scratch for launch_member_emit
 struct ScanResult {
@@ -1527,6 +1639,28 @@ int dslot_prepare(gzpx_dctx *c, DSlot &sl, size_t nb, int route, size_t cap, uin
     sl.sc.n_cu = c->n_cu;
     sl.sc.in_bytes = in_bytes;
     return route == kInflateRouteSeg && writes ? dslot_seg_scratch(sl, cap, nb) : GZPX_OK;
+}
+
+// The framed inflate, enqueued on the context's stream: the slot made ready, nb members of d_in, listed by the device
+// tables `offsets` / `sizes`, into dst[0..cap) back to back, and k_dsummary's words (what the host needs of the members'
+// records: summary_verdict) on their way to sl.h_summary.  `ev_before`, if any, is recorded in front of the kernels.
+int inflate_enqueue(gzpx_dctx *c, DSlot &sl, const uint8_t *d_in, const uint64_t *offsets, const uint32_t *sizes, size_t nb,
+                    uint8_t *dst, size_t cap, uint64_t in_bytes, hipEvent_t ev_before = nullptr) {
+    GZPX_TRY(dslot_prepare(c, sl, nb, c->route, cap, in_bytes));
+    if (ev_before) HIP_TRY(hipEventRecord(ev_before, c->stream));
+    launch_inflate(header_bytes(c->format), d_in, offsets, sizes, (uint32_t)nb, sl.d_blk, sl.d_out_off, dst, cap, sl.d_crc, c->cc,
+                   c->debug, sl.ev_t0, sl.ev_t1, c->stream, sl.sc, sl.route, sl.ev_tm);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, c->stream));
+    return GZPX_OK;
+}
+
+// the members' records themselves, behind a launch: only for the debug counters, and only the calls that bring them back
+int debug_records(gzpx_dctx *c, DSlot &sl, size_t nb) {
+    if (!c->debug) return GZPX_OK;
+    HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, nb * sizeof(DBlockHost), hipMemcpyDeviceToHost, c->stream));
+    sl.have_blk = true;
+    return GZPX_OK;
 }
 
 // Enqueue the inflate of one slab (c->mu held): copies in, kernels, copies out, as the compress side's submit_enqueue.
@@ -1564,7 +1698,7 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
         }
         uint64_t csum = 0;  // the members' compressed bytes
         if (scan) {  // the table goes from the scan's scratch to the slot's on the device
-            launch_member_emit(c->ms, (uint32_t)nb, sl.d_offsets, sl.d_sizes, stream);
+            launch_member_emit(c->scan.ms, (uint32_t)nb, sl.d_offsets, sl.d_sizes, stream);
             csum = scan->consumed;  // (the members of a walk lie back to back from offset 0)
         } else {
             memcpy(sl.h_offsets, offsets, nb * 8);
@@ -1576,17 +1710,8 @@ int dsubmit_enqueue(gzpx_dctx *c, const uint8_t *host_in, const uint8_t *d_in, s
             for (size_t b = 0; b < nb; b++) csum += sizes[b];
         }
         // (the pair's scratch is sized by what the caller can take)
-        GZPX_TRY(dslot_prepare(c, sl, nb, c->route, out_cap, csum));
-        launch_inflate(hdr_len, d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nb, sl.d_blk, sl.d_out_off, d_out, out_cap,
-                       sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, sl.ev_tm);
-        HIP_TRY(hipGetLastError());
-        // what the host needs of the members' records is k_dsummary's 48 bytes; the records themselves only for the
-        // debug counters
-        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
-        if (c->debug) {
-            HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, nb * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
-            sl.have_blk = true;
-        }
+        GZPX_TRY(inflate_enqueue(c, sl, d_in, sl.d_offsets, sl.d_sizes, nb, d_out, out_cap, csum));
+        GZPX_TRY(debug_records(c, sl, nb));
         HIP_TRY(hipMemcpyAsync(sl.h_total, sl.d_out_off + nb, 8, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipEventRecord(sl.ev_kernels, stream));
         if (host_out) {
@@ -1658,38 +1783,16 @@ int dwait_ticket(gzpx_dctx *c, uint64_t ticket, size_t *out_len, gzpx_check_info
     return rc;
 }
 
-int dscan_reserve(gzpx_dctx *c, size_t n_seg, size_t cap) {
-    MemberScanScratch &m = c->ms;
-    if (!m.rec) {
-        GZPX_TRY(c->scan_once.dev(m.rec, 64));
-        GZPX_TRY(c->scan_once.pinned(c->h_rec, 64));
-        GZPX_TRY(c->ev_s0.create(true));
-        GZPX_TRY(c->ev_s1.create(true));
-    }
-    GZPX_TRY(grow(c->scan_seg, c->ms_seg_cap, n_seg, n_seg, [&](size_t n) -> int {
-        GZPX_TRY(c->scan_seg.dev(m.seg_count, n * 4));
-        return c->scan_seg.dev(m.seg_off, n * 4);
-    }));
-    Allocs &a = c->scan_cand;
-    return grow(a, m.cap, cap, cap, [&](size_t n) -> int {
-        GZPX_TRY(a.dev(m.pos, n * 8));
-        GZPX_TRY(a.dev(m.size, n * 4));
-        GZPX_TRY(a.dev(m.succ, n * 4));
-        GZPX_TRY(a.dev(m.jump[0], n * 4));
-        GZPX_TRY(a.dev(m.jump[1], n * 4));
-        return a.dev(m.idx, n * 4);
-    });
-}
-
 // gzpx_scan_blocks over d_in[0..in_len) on the device, without the cap: how many members the walk from offset 0
-// records and where it stops.  Returns synchronised; the table stays in c->ms (launch_member_emit) until the next
+// records and where it stops.  Returns synchronised; the table stays in c->scan.ms (launch_member_emit) until the next
 // scan of this context.  Called with c->mu held.  `slot_lk`: the caller goes on to use a slot and holds c->mu from
 // the scan until it is done with the table: a free slot is waited for first (the wait lets go of the mutex), r->slot.
 int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t after, ScanResult *r,
               std::unique_lock<std::mutex> *slot_lk = nullptr) {
     *r = ScanResult();
     if (slot_lk) r->slot = free_slot(c, *slot_lk, true);
-    c->have_scan = false;
+    ScanState &s = c->scan;
+    s.have = false;
     const size_t hdr = header_bytes(c->format);
     if (in_len < hdr) return GZPX_OK;  // read_exact(header) finds nothing to read
     hipStream_t stream = c->stream;
@@ -1705,57 +1808,33 @@ int dscan_run(gzpx_dctx *c, const uint8_t *d_in, size_t in_len, hipStream_t afte
     // record says by how much, and the scan runs once more.
     const size_t kCapMax = 0xFFFFFFF0ull;
     size_t cap = in_len / 2048 + 4096;
-    if (cap < c->ms.cap) cap = c->ms.cap;
+    if (cap < s.ms.cap) cap = s.ms.cap;
     if (cap > kCapMax) cap = kCapMax;
     for (int attempt = 0;; attempt++) {
-        const int rc = dscan_reserve(c, n_seg, cap);
+        const int rc = s.reserve(n_seg, cap);
         if (rc != GZPX_OK) return rc;
         // a walk has at most min(candidates, in_len / smallest member) members: that many indices to hand out
         size_t chain = in_len / (hdr + 8) + 1;
-        if (chain > c->ms.cap) chain = c->ms.cap;
+        if (chain > s.ms.cap) chain = s.ms.cap;
         uint32_t rounds = 0;
         while (rounds < 32 && ((size_t)1 << rounds) < chain) rounds++;
-        if (attempt == 0) HIP_TRY(hipEventRecord(c->ev_s0, stream));
-        launch_member_scan(c->format, d_in, in_len, (uint32_t)seg_bytes, (uint32_t)n_seg, rounds, c->ms, stream);
+        if (attempt == 0) HIP_TRY(hipEventRecord(s.ev0, stream));
+        launch_member_scan(c->format, d_in, in_len, (uint32_t)seg_bytes, (uint32_t)n_seg, rounds, s.ms, stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_s1, stream));
-        HIP_TRY(hipMemcpyAsync(c->h_rec, c->ms.rec, 32, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(s.ev1, stream));
+        HIP_TRY(hipMemcpyAsync(s.h_rec, s.ms.rec, 32, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        const size_t n_cand = c->h_rec[0];
-        if (n_cand <= c->ms.cap) break;
+        const size_t n_cand = s.h_rec[0];
+        if (n_cand <= s.ms.cap) break;
         if (n_cand > kCapMax || attempt) return GZPX_ERR_DEVICE;  // (more candidates than the 32-bit indices address)
         cap = n_cand + n_cand / 8 + 64;
         if (cap > kCapMax) cap = kCapMax;
     }
-    c->have_scan = true;
-    r->invalid = c->h_rec[2] != 0;
-    r->n_members = c->h_rec[1];
-    r->consumed = (size_t)((uint64_t)c->h_rec[4] | ((uint64_t)c->h_rec[5] << 32));
+    s.have = true;
+    r->invalid = s.h_rec[2] != 0;
+    r->n_members = s.h_rec[1];
+    r->consumed = (size_t)rec_u64(s.h_rec, 4);
     return GZPX_OK;
-}
-
-int rr_reserve(gzpx_dctx *c, size_t n_ranges, size_t n_members) {
-    RangeScratch &r = c->rr;
-    if (!r.rec) {
-        GZPX_TRY(c->rr_once.dev(r.rec, 64));
-        GZPX_TRY(c->rr_once.pinned(c->h_rrec, 64));
-        for (Event &e : c->ev_r) GZPX_TRY(e.create(true));
-    }
-    Allocs &a = c->rr_ranges, &b = c->rr_members;
-    GZPX_TRY(grow(a, c->rr_range_cap, n_ranges, n_ranges + n_ranges / 4 + 64, [&](size_t cap) -> int {
-        GZPX_TRY(a.dev(r.ranges, cap * 16));
-        GZPX_TRY(a.dev(r.first, cap * 4));
-        GZPX_TRY(a.dev(r.len, cap * 8));
-        GZPX_TRY(a.dev(r.src, cap * 8));
-        GZPX_TRY(a.dev(r.out_off, (cap + 1) * 8));
-        GZPX_TRY(a.pinned(c->h_ranges, cap * 16));
-        return a.pinned(c->h_out_off, (cap + 1) * 8);
-    }));
-    return grow(b, c->rr_member_cap, n_members + 1, n_members + n_members / 4 + 64, [&](size_t cap) -> int {
-        GZPX_TRY(b.dev(r.diff, cap * 4));
-        GZPX_TRY(b.dev(r.map, cap * 4));
-        return b.dev(r.soff, cap * 8);
-    });
 }
 
 }  // namespace
@@ -1879,16 +1958,17 @@ int gzpx_scan_blocks_device(gzpx_dctx *c, const void *d_in, size_t in_len, uint6
     // with the cap reached in front of a whole member the walk stops there: that member's offset is `consumed`
     const bool capped = max_blocks < r.n_members;
     const size_t n = capped ? max_blocks : r.n_members, n_emit = capped ? n + 1 : n;
-    GZPX_TRY(grow(c->tab_mem, c->tab_cap, n_emit, n_emit + n_emit / 4 + 64, [&](size_t cap) -> int {
-        GZPX_TRY(c->tab_mem.dev(c->d_tab_off, cap * 8));
-        return c->tab_mem.dev(c->d_tab_size, cap * 4);
+    ScanState &s = c->scan;
+    GZPX_TRY(grow(s.tab_mem, s.tab_cap, n_emit, n_emit + n_emit / 4 + 64, [&](size_t cap) -> int {
+        GZPX_TRY(s.tab_mem.dev(s.d_tab_off, cap * 8));
+        return s.tab_mem.dev(s.d_tab_size, cap * 4);
     }));
-    launch_member_emit(c->ms, (uint32_t)n_emit, c->d_tab_off, c->d_tab_size, c->stream);
+    launch_member_emit(s.ms, (uint32_t)n_emit, s.d_tab_off, s.d_tab_size, c->stream);
     HIP_TRY(hipGetLastError());
     uint64_t stop = 0;
-    if (n) HIP_TRY(hipMemcpyAsync(offsets, c->d_tab_off, n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (n) HIP_TRY(hipMemcpyAsync(sizes, c->d_tab_size, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (capped) HIP_TRY(hipMemcpyAsync(&stop, c->d_tab_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(offsets, s.d_tab_off, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(sizes, s.d_tab_size, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (capped) HIP_TRY(hipMemcpyAsync(&stop, s.d_tab_off + n, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *n_blocks = n;
     *consumed = capped ? (size_t)stop : r.consumed;
@@ -1941,7 +2021,7 @@ int gzpx_index_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx_index_
     const int rr = dslot_reserve(sl, r.n_members);
     if (rr != GZPX_OK) return rr;
     const uint32_t nb = (uint32_t)r.n_members;
-    launch_member_emit(c->ms, nb, sl.d_offsets, sl.d_sizes, c->stream);
+    launch_member_emit(c->scan.ms, nb, sl.d_offsets, sl.d_sizes, c->stream);
     launch_member_index((const uint8_t *)d_in, sl.d_offsets, sl.d_sizes, nb, sl.d_blk, sl.d_out_off, c->stream);
     HIP_TRY(hipGetLastError());
     const size_t n_copy = entries ? (r.n_members < max_entries ? r.n_members : max_entries) : 0;
@@ -1961,8 +2041,8 @@ int gzpx_dctx_last_scan_ms(gzpx_dctx *ctx, float *ms) {
     if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
     *ms = 0.0f;
-    if (!ctx->have_scan) return GZPX_OK;
-    return hipEventElapsedTime(ms, ctx->ev_s0, ctx->ev_s1) == hipSuccess ? GZPX_OK : GZPX_ERR_DEVICE;
+    if (!ctx->scan.have) return GZPX_OK;
+    return hipEventElapsedTime(ms, ctx->scan.ev0, ctx->scan.ev1) == hipSuccess ? GZPX_OK : GZPX_ERR_DEVICE;
 }
 
 }  // extern "C"
@@ -2016,7 +2096,7 @@ int gzpx_dindex_build_device(gzpx_dctx *c, const void *d_in, size_t in_len, gzpx
     } else {
         DSlot &sl = c->slots[r.slot];  // (its member records only; the slot stays free, the call returns synchronised under the lock)
         GZPX_TRY(dslot_reserve(sl, n));
-        launch_member_emit(c->ms, (uint32_t)n, ix->d_off, ix->d_size, c->stream);
+        launch_member_emit(c->scan.ms, (uint32_t)n, ix->d_off, ix->d_size, c->stream);
         launch_member_index((const uint8_t *)d_in, ix->d_off, ix->d_size, (uint32_t)n, sl.d_blk, ix->d_ustart, c->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(sl.h_total, ix->d_ustart + n, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2044,6 +2124,152 @@ int gzpx_dindex_entries(const gzpx_dindex *ix, gzpx_index_entry *entries, size_t
     return GZPX_OK;
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------- indexed reads: the steps the calls below share
+namespace {
+
+// an index and a context that belong together, and a stream at least as long as the index says
+bool index_matches(const gzpx_dctx *c, const gzpx_dindex *ix, size_t in_len) {
+    return ix->device == c->device && ix->format == c->format && in_len >= ix->consumed;
+}
+
+// (the stream's average member stands for each of nb members of it: InflateScratch::in_bytes)
+uint64_t average_in_bytes(const gzpx_dindex *ix, size_t nb) { return (uint64_t)(ix->consumed / ix->n) * nb; }
+
+// the ranges' record behind locate + select: the first bad item (0xFFFFFFFF: none), the members the items touch, what
+// those inflate to, the items' bytes
+struct Selection {
+    uint32_t bad;
+    size_t n;
+    uint64_t stage_bytes, total;
+};
+
+Selection selection_read(const gzpx_dctx *c) {
+    const uint32_t *rec = c->ranges.h_rec;
+    return Selection{rec[kRrRecBad], rec[kRrRecSelected], rec_u64(rec, kRrRecStage), rec_u64(rec, kRrRecTotal)};
+}
+
+// The first half of "select, then inflate the selection": `bytes` of the caller's items go through h_ranges to
+// `d_items`, and between ev[0] and ev[1] the kernels `pre` enqueues (the line calls': boundaries to tile covers) and
+// locate + select run, which leave the selected members' table in the slot's.  The caller copies the records it
+// reads back, synchronises -- the one round trip in front of the inflate -- and reads selection_read().
+template <class Pre>
+int select_enqueue(gzpx_dctx *c, DSlot &sl, const gzpx_dindex *ix, const void *items, size_t bytes, void *d_items, size_t n,
+                   int is_virtual, Event *ev, Pre &&pre) {
+    RangesState &r = c->ranges;
+    const RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
+    memcpy(r.h_ranges, items, bytes);  // (room for 16 bytes an item)
+    HIP_TRY(hipMemcpyAsync(d_items, r.h_ranges, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(ev[0], c->stream));
+    pre();
+    launch_ranges_select(rix, (uint32_t)n, is_virtual, r.rr, sl.d_offsets, sl.d_sizes, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1], c->stream));
+    return GZPX_OK;
+}
+
+// The second half: the selected members into staging, which the caller has reserved.  (The pair's scratch is sized by
+// the staging; the members' records stay on the device, under gzpx_debug_inflate too.)
+int inflate_selection(gzpx_dctx *c, DSlot &sl, const gzpx_dindex *ix, const uint8_t *d_in, const Selection &s,
+                      hipEvent_t ev_before = nullptr) {
+    return inflate_enqueue(c, sl, d_in, sl.d_offsets, sl.d_sizes, s.n, c->stage.d, (size_t)s.stage_bytes,
+                           average_in_bytes(ix, s.n), ev_before);
+}
+
+// The verdict on an inflated selection (the stream idle): a failure names the first failing member of the selection in
+// stream order by its index in the stream, through the rank map.
+int selection_verdict(gzpx_dctx *c, const DSlot &sl, gzpx_check_info *info) {
+    gzpx_check_info failed = {0, 0, 0};
+    const int verdict = summary_verdict(sl.h_summary, false, &failed);
+    if (verdict == GZPX_OK) return GZPX_OK;
+    uint32_t member = 0;
+    HIP_TRY(hipMemcpy(&member, c->ranges.rr.map + failed.block, 4, hipMemcpyDeviceToHost));
+    failed.block = member;
+    if (info) *info = failed;
+    return verdict;
+}
+
+// The whole members of an index in batches of at most the context's lines_batch inflated bytes, a larger member on
+// its own: batch k is members [cuts[k], cuts[k + 1]).  Cut on the host from the index's prefix sums.
+struct Batches {
+    std::vector<uint64_t> ustart;
+    std::vector<size_t> cuts;
+    uint64_t max_bytes = 0;
+    size_t max_members = 1;
+};
+
+int batches_of(const gzpx_dctx *c, const gzpx_dindex *ix, Batches &b) {
+    const size_t n = ix->n;
+    b.ustart.assign(n + 1, 0);
+    if (n) HIP_TRY(hipMemcpy(b.ustart.data(), ix->d_ustart, (n + 1) * 8, hipMemcpyDeviceToHost));
+    const uint64_t batch = c->lines.batch ? c->lines.batch : kLinesBatchDefault;
+    b.cuts.assign(1, 0);
+    for (size_t m0 = 0; m0 < n;) {
+        size_t m1 = m0 + 1;
+        while (m1 < n && b.ustart[m1 + 1] - b.ustart[m0] <= batch) m1++;
+        if (b.ustart[m1] - b.ustart[m0] > b.max_bytes) b.max_bytes = b.ustart[m1] - b.ustart[m0];
+        if (m1 - m0 > b.max_members) b.max_members = m1 - m0;
+        b.cuts.push_back(m1);
+        m0 = m1;
+    }
+    return GZPX_OK;
+}
+
+// One pass over every member of an index, batch by batch through staging (c->mu held, slot `si` free and the caller's
+// for the call, `drain` the caller's on the context's stream).  Slot and staging are reserved for the largest batch,
+// `pad` bytes in front of where the inflate writes.  Per batch: the caller's ev[0] is recorded, the batch inflated, and
+// enqueue(base, bytes, is_last) puts the caller's kernels behind it, each followed by the next of ev[1..n_ms] --
+// without asking how the inflate went: whatever staging holds, they stay inside it.  Then the stream is synchronised
+// (staging is the next batch's too; the verdict decides whether there is one), the n_ms times between the events are
+// added to the caller's sums (all of them or none), and a failing verdict ends the pass with the member's index in
+// the stream.
+template <class Enqueue>
+int batched_pass(gzpx_dctx *c, int si, const gzpx_dindex *ix, const Batches &b, const uint8_t *d_in, size_t pad,
+                 const Event *ev, int n_ms, float *ms_sums, gzpx_check_info *info, Drain &drain, Enqueue &&enqueue) {
+    DSlot &sl = c->slots[si];
+    GZPX_TRY(dslot_reserve(sl, b.max_members));
+    GZPX_TRY(c->stage.reserve(pad + b.max_bytes));
+    for (size_t k = 0; k + 1 < b.cuts.size(); k++) {
+        const size_t m0 = b.cuts[k], nb = b.cuts[k + 1] - m0;
+        const uint64_t base = b.ustart[m0], bytes = b.ustart[m0 + nb] - base;
+        GZPX_TRY(inflate_enqueue(c, sl, d_in, ix->d_off + m0, ix->d_size + m0, nb, c->stage.d + pad, (size_t)bytes,
+                                 average_in_bytes(ix, nb), ev[0]));
+        GZPX_TRY(enqueue(base, bytes, k + 2 == b.cuts.size()));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->last_slot = si;
+        c->last_nb = nb;
+        float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int timed = 0;
+        while (timed < n_ms && hipEventElapsedTime(&ms[timed], ev[timed], ev[timed + 1]) == hipSuccess) timed++;
+        for (int j = 0; timed == n_ms && j < n_ms; j++) ms_sums[j] += ms[j];
+        gzpx_check_info failed = {0, 0, 0};
+        const int verdict = summary_verdict(sl.h_summary, false, &failed);
+        if (verdict != GZPX_OK) {
+            failed.block += m0;
+            if (info) *info = failed;
+            drain.armed = false;
+            return verdict;
+        }
+    }
+    return GZPX_OK;
+}
+
+// The record of a call on a table of members (kWrRec*: k_dresult's, k_dresult_sizes', k_cksum_record's) as the call's
+// return code: how many failed, the total where the call has one, and the first failing member with its two
+// checksums -- `sums` false (the sizes call, which verifies none): 0 and 0.
+int result_verdict(const uint32_t *q, size_t *n_failed, uint64_t *total, gzpx_check_info *info, bool sums = true) {
+    if (total) *total = rec_u64(q, kWrRecTotal);
+    *n_failed = q[kWrRecFailed];
+    if (q[kWrRecFirst] == 0xFFFFFFFFu) return GZPX_OK;
+    if (info) *info = gzpx_check_info{q[kWrRecFirst], sums ? q[kWrRecFound] : 0u, sums ? q[kWrRecExpected] : 0u};
+    return (int)q[kWrRecStatus];
+}
+
+}  // namespace
+
+extern "C" {
+
 int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len,
                             const gzpx_range *ranges, size_t n_ranges, int coords, void *d_out, size_t out_cap,
                             size_t *out_len, uint64_t *out_offsets, size_t *bad_range, gzpx_check_info *info,
@@ -2054,11 +2280,12 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
     if (bad_range) *bad_range = (size_t)-1;
     if (coords != GZPX_RANGE_UNCOMPRESSED && coords != GZPX_RANGE_VIRTUAL) return GZPX_ERR_INVALID_ARG;
     if (coords == GZPX_RANGE_VIRTUAL && c->format != GZPX_FORMAT_BGZF) return GZPX_ERR_INVALID_ARG;
-    if (ix->device != c->device || ix->format != c->format || in_len < ix->consumed) return GZPX_ERR_INVALID_ARG;
+    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
     if (n_ranges > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
     std::unique_lock<std::mutex> lk(c->mu);
-    c->have_rr = c->rr_stages = false;
-    c->last_rr_members = 0;
+    RangesState &r = c->ranges;
+    r.have = r.stages = false;
+    r.last_members = 0;
     if (n_ranges == 0) {
         if (out_offsets) out_offsets[0] = 0;
         return GZPX_OK;
@@ -2067,72 +2294,47 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
     const int si = free_slot(c, lk, true);
     DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
     GZPX_TRY(dslot_reserve(sl, ix->n ? ix->n : 1));
-    GZPX_TRY(rr_reserve(c, n_ranges, ix->n));
+    GZPX_TRY(r.reserve(n_ranges, ix->n));
     hipStream_t stream = c->stream;
     GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
     Drain drain{{stream}, 1};
-    RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
-    memcpy(c->h_ranges, ranges, n_ranges * sizeof(gzpx_range));
-    HIP_TRY(hipMemcpyAsync(c->rr.ranges, c->h_ranges, n_ranges * 16, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->ev_r[0], stream));
-    launch_ranges_select(rix, (uint32_t)n_ranges, coords == GZPX_RANGE_VIRTUAL, c->rr, sl.d_offsets, sl.d_sizes, stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_r[1], stream));
-    HIP_TRY(hipMemcpyAsync(c->h_rrec, c->rr.rec, 32, hipMemcpyDeviceToHost, stream));
+    GZPX_TRY(select_enqueue(c, sl, ix, ranges, n_ranges * sizeof(gzpx_range), r.rr.ranges, n_ranges, coords == GZPX_RANGE_VIRTUAL,
+                            r.ev, [] {}));
+    HIP_TRY(hipMemcpyAsync(r.h_rec, r.rr.rec, 32, hipMemcpyDeviceToHost, stream));
     if (out_offsets)
-        HIP_TRY(hipMemcpyAsync(c->h_out_off, c->rr.out_off, (n_ranges + 1) * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(r.h_out_off, r.rr.out_off, (n_ranges + 1) * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));  // the record: the one round trip in front of the inflate
-    c->have_rr = true;
-    const uint32_t *rec = c->h_rrec;
-    if (rec[kRrRecBad] != 0xFFFFFFFFu) {
-        if (bad_range) *bad_range = rec[kRrRecBad];
+    r.have = true;
+    const Selection sel = selection_read(c);
+    if (sel.bad != 0xFFFFFFFFu) {
+        if (bad_range) *bad_range = sel.bad;
         return GZPX_ERR_INVALID_ARG;
     }
-    const size_t nsel = rec[kRrRecSelected];
-    const uint64_t stage_bytes = (uint64_t)rec[kRrRecStage] | ((uint64_t)rec[kRrRecStage + 1] << 32);
-    const uint64_t total = (uint64_t)rec[kRrRecTotal] | ((uint64_t)rec[kRrRecTotal + 1] << 32);
-    if (total > out_cap) {
-        *out_len = (size_t)total;
+    if (sel.total > out_cap) {
+        *out_len = (size_t)sel.total;
         return GZPX_ERR_INSUFFICIENT_SPACE;
     }
-    if (total >> 44) return GZPX_ERR_INVALID_ARG;  // (the gather's grid)
-    if (out_offsets) memcpy(out_offsets, c->h_out_off, (n_ranges + 1) * 8);
-    c->last_rr_members = nsel;
-    if (nsel == 0) {  // empty ranges only
+    if (sel.total >> 44) return GZPX_ERR_INVALID_ARG;  // (the gather's grid)
+    if (out_offsets) memcpy(out_offsets, r.h_out_off, (n_ranges + 1) * 8);
+    r.last_members = sel.n;
+    if (sel.n == 0) {  // empty ranges only
         drain.armed = false;
         return GZPX_OK;
     }
-    GZPX_TRY(grow(c->stage_mem, c->stage_cap, (size_t)(stage_bytes + 64), (size_t)(stage_bytes + stage_bytes / 8 + 4096),
-                  [&](size_t cap) { return c->stage_mem.dev(c->d_stage, cap); }));
-    // (the pair's scratch is sized by the staging; the stream's average member stands for the selection's.  The
-    // members' records stay on the device, under gzpx_debug_inflate too.)
-    GZPX_TRY(dslot_prepare(c, sl, nsel, c->route, (size_t)stage_bytes, (uint64_t)(ix->consumed / ix->n) * nsel));
-    HIP_TRY(hipEventRecord(c->ev_r[2], stream));
-    launch_inflate(header_bytes(c->format), (const uint8_t *)d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nsel, sl.d_blk,
-                   sl.d_out_off, c->d_stage, stage_bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route,
-                   sl.ev_tm);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(c->ev_r[3], stream));
+    GZPX_TRY(c->stage.reserve(sel.stage_bytes));
+    GZPX_TRY(inflate_selection(c, sl, ix, (const uint8_t *)d_in, sel, r.ev[2]));
+    HIP_TRY(hipEventRecord(r.ev[3], stream));
     // (enqueued behind the inflate without asking how it went: after a failed check d_out holds nothing of use)
-    launch_ranges_gather(c->d_stage, (uint32_t)n_ranges, c->rr, (uint8_t *)d_out, total, stream);
+    launch_ranges_gather(c->stage.d, (uint32_t)n_ranges, r.rr, (uint8_t *)d_out, sel.total, stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_r[4], stream));
+    HIP_TRY(hipEventRecord(r.ev[4], stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
-    c->rr_stages = true;
+    r.stages = true;
     c->last_slot = si;
-    c->last_nb = nsel;
-    gzpx_check_info failed = {0, 0, 0};  // the first failing member of the selection, in stream order
-    const int verdict = summary_verdict(sl.h_summary, false, &failed);
-    if (verdict != GZPX_OK) {
-        uint32_t member = 0;  // its index in the stream, through the rank map
-        HIP_TRY(hipMemcpy(&member, c->rr.map + failed.block, 4, hipMemcpyDeviceToHost));
-        failed.block = member;
-        if (info) *info = failed;
-        return verdict;
-    }
-    *out_len = (size_t)total;
+    c->last_nb = sel.n;
+    GZPX_TRY(selection_verdict(c, sl, info));
+    *out_len = (size_t)sel.total;
     return GZPX_OK;
 }
 
@@ -2176,25 +2378,16 @@ int gzpx_inflate_batch_device(gzpx_dctx *c, int wrap, unsigned flags, const void
                          sl.ev_tc);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
-    if (c->debug) {
-        HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, n * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
-        sl.have_blk = true;
-    }
+    GZPX_TRY(debug_records(c, sl, n));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
     sl.have_check = true;
     c->last_slot = si;
     c->last_nb = n;
-    const uint32_t *q = sl.h_summary;  // k_dresult's record
-    *out_len = (size_t)((uint64_t)q[kWrRecTotal] | ((uint64_t)q[kWrRecTotal + 1] << 32));
-    *n_failed = q[kWrRecFailed];
-    if (q[kWrRecFirst] == 0xFFFFFFFFu) return GZPX_OK;
-    if (info) {
-        info->block = q[kWrRecFirst];
-        info->found = q[kWrRecFound];
-        info->expected = q[kWrRecExpected];
-    }
-    return (int)q[kWrRecStatus];
+    uint64_t total = 0;
+    const int verdict = result_verdict(sl.h_summary, n_failed, &total, info);  // k_dresult's record
+    *out_len = (size_t)total;
+    return verdict;
 }
 
 int gzpx_inflate_batch_sizes_device(gzpx_dctx *c, int wrap, const void *d_in, size_t in_len, const uint64_t *d_in_offsets,
@@ -2222,24 +2415,12 @@ int gzpx_inflate_batch_sizes_device(gzpx_dctx *c, int wrap, const void *d_in, si
                          c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, d_out_sizes, d_in_used, d_results, sl.ev_tm);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
-    if (c->debug) {
-        HIP_TRY(hipMemcpyAsync(sl.h_blk, sl.d_blk, n * sizeof(DBlockHost), hipMemcpyDeviceToHost, stream));
-        sl.have_blk = true;
-    }
+    GZPX_TRY(debug_records(c, sl, n));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
     c->last_slot = si;
     c->last_nb = n;
-    const uint32_t *q = sl.h_summary;  // k_dresult_sizes' record
-    *total_out = (uint64_t)q[kWrRecTotal] | ((uint64_t)q[kWrRecTotal + 1] << 32);
-    *n_failed = q[kWrRecFailed];
-    if (q[kWrRecFirst] == 0xFFFFFFFFu) return GZPX_OK;
-    if (info) {
-        info->block = q[kWrRecFirst];
-        info->found = 0;
-        info->expected = 0;
-    }
-    return (int)q[kWrRecStatus];
+    return result_verdict(sl.h_summary, n_failed, total_out, info, false);  // k_dresult_sizes' record
 }
 
 int gzpx_checksum_batch_device(gzpx_dctx *c, int kind, const void *d_in, size_t in_len, const uint64_t *d_offsets,
@@ -2259,19 +2440,15 @@ int gzpx_checksum_batch_device(gzpx_dctx *c, int kind, const void *d_in, size_t 
     const int si = free_slot(c, lk, true);
     DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock; its events and record serve)
     GZPX_TRY(dslot_reserve(sl, 1));
-    const uint32_t wgs = cksum_workgroups(c->n_cu, c->ck_width);
-    GZPX_TRY(grow(c->ck_entries, c->ck_entry_cap, n, n + n / 4 + 64, [&](size_t cap) -> int {
-        GZPX_TRY(c->ck_entries.dev(c->ck.prefix, (cap + 1) * 8));
-        return c->ck_entries.dev(c->ck.part, cap * 4);
-    }));
-    GZPX_TRY(grow(c->ck_wgs, c->ck_wg_cap, wgs, wgs, [&](size_t cap) { return c->ck_wgs.dev(c->ck.carry, cap * 8); }));
-    c->ck.rec = sl.sc.summary;
+    const uint32_t wgs = cksum_workgroups(c->n_cu, c->cksum.width);
+    GZPX_TRY(c->cksum.reserve(n, wgs));
+    c->cksum.ck.rec = sl.sc.summary;
     GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
     Drain drain{{stream}, 1};
     sl.have_blk = sl.have_check = false;
     HIP_TRY(hipEventRecord(sl.ev_t1, stream));
     launch_cksum_batch(kind, (const uint8_t *)d_in, in_len, d_offsets, d_sizes, (uint32_t)n, d_seeds, d_expected, d_sums,
-                       d_results, c->ck, wgs, stream);
+                       d_results, c->cksum.ck, wgs, stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev_tc, stream));
     HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
@@ -2280,19 +2457,13 @@ int gzpx_checksum_batch_device(gzpx_dctx *c, int kind, const void *d_in, size_t 
     sl.have_check = true;
     c->last_slot = si;
     c->last_nb = 0;  // (no member was inflated: the inflate getters answer 0)
-    const uint32_t *q = sl.h_summary;  // k_cksum_record's record
-    *n_failed = q[kWrRecFailed];
-    if (q[kWrRecFirst] == 0xFFFFFFFFu) return GZPX_OK;
-    info->block = q[kWrRecFirst];
-    info->found = q[kWrRecFound];
-    info->expected = q[kWrRecExpected];
-    return (int)q[kWrRecStatus];
+    return result_verdict(sl.h_summary, n_failed, nullptr, info);  // k_cksum_record's record
 }
 
 int gzpx_dctx_set_checksum_width(gzpx_dctx *ctx, unsigned workgroups) {
     if (!ctx || workgroups > 65536u) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
-    ctx->ck_width = workgroups;
+    ctx->cksum.width = workgroups;
     return GZPX_OK;
 }
 
@@ -2309,7 +2480,7 @@ int gzpx_dctx_last_check_ms(gzpx_dctx *ctx, float *ms) {
 int gzpx_dctx_last_ranges_members(gzpx_dctx *ctx, size_t *n_members_read) {
     if (!ctx || !n_members_read) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
-    *n_members_read = ctx->last_rr_members;
+    *n_members_read = ctx->ranges.last_members;
     return GZPX_OK;
 }
 
@@ -2317,11 +2488,11 @@ int gzpx_dctx_last_ranges_ms(gzpx_dctx *ctx, float ms[3]) {
     if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
     ms[0] = ms[1] = ms[2] = 0.0f;
-    if (!ctx->have_rr) return GZPX_OK;
-    if (hipEventElapsedTime(&ms[0], ctx->ev_r[0], ctx->ev_r[1]) != hipSuccess) return GZPX_ERR_DEVICE;
-    if (!ctx->rr_stages) return GZPX_OK;
-    if (hipEventElapsedTime(&ms[1], ctx->ev_r[2], ctx->ev_r[3]) != hipSuccess ||
-        hipEventElapsedTime(&ms[2], ctx->ev_r[3], ctx->ev_r[4]) != hipSuccess)
+    const RangesState &r = ctx->ranges;
+    if (!r.have) return GZPX_OK;
+    if (hipEventElapsedTime(&ms[0], r.ev[0], r.ev[1]) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (!r.stages) return GZPX_OK;
+    if (hipEventElapsedTime(&ms[1], r.ev[2], r.ev[3]) != hipSuccess || hipEventElapsedTime(&ms[2], r.ev[3], r.ev[4]) != hipSuccess)
         return GZPX_ERR_DEVICE;
     return GZPX_OK;
 }
@@ -2342,102 +2513,63 @@ struct gzpx_dlines : NoCopy {
 
 namespace {
 
-static_assert(kLnTile == GZPX_LINES_TILE, "the public constant states the kernels' tile");
-constexpr size_t kLinesBatchDefault = (size_t)256 << 20;
-
-int ln_reserve(gzpx_dctx *c, size_t n_bounds) {
-    LinesScratch &l = c->ln;
-    if (!l.rec) {
-        GZPX_TRY(c->ln_once.dev(l.rec, 64));
-        GZPX_TRY(c->ln_once.pinned(c->h_lrec, 64));
-        for (Event &e : c->ev_l) GZPX_TRY(e.create(true));
-    }
-    Allocs &a = c->ln_bounds;
-    return grow(a, c->ln_cap, n_bounds, n_bounds + n_bounds / 4 + 64, [&](size_t cap) -> int {
-        GZPX_TRY(a.dev(l.bounds, cap * 8));
-        GZPX_TRY(a.dev(l.btile, cap * 4));
-        GZPX_TRY(a.dev(l.bpos, cap * 8));
-        return a.pinned(c->h_bpos, cap * 8);
-    });
-}
-
 // a table, an index and a context that belong together, and a stream at least as long as the index says
 bool lines_match(const gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, size_t in_len) {
-    return ix->device == c->device && ix->format == c->format && in_len >= ix->consumed && lt->device == ix->device &&
-           lt->format == ix->format && lt->n == ix->n && lt->consumed == ix->consumed && lt->inflated_len == ix->inflated_len;
+    return index_matches(c, ix, in_len) && lt->device == ix->device && lt->format == ix->format && lt->n == ix->n &&
+           lt->consumed == ix->consumed && lt->inflated_len == ix->inflated_len;
 }
 
 // What the two line calls share (c->mu held, slot `si` free and the caller's for the call): n items of `per`
 // boundaries each -- line numbers, or (a, b) of line ranges -- are validated, the covers of their tiles located and
 // selected, the selected members inflated into staging and the boundary tiles walked there.  Two round trips: the
-// record in front of the inflate, the positions behind the walk.  Returns with the stream idle; c->h_bpos then holds
-// start() of every boundary and, per == 2, c->rr / c->h_out_off / *total describe the gather that is still to run.
+// record in front of the inflate, the positions behind the walk.  Returns with the stream idle; l.h_bpos then holds
+// start() of every boundary and, per == 2, c->ranges (rr, h_out_off) and *total describe the gather that is still to run.
 int lines_search(gzpx_dctx *c, int si, const gzpx_dindex *ix, const gzpx_dlines *lt, const uint8_t *d_in, const uint64_t *bounds,
                  size_t n, uint32_t per, size_t *bad, gzpx_check_info *info, hipStream_t after, uint64_t *total) {
     DSlot &sl = c->slots[si];
+    RangesState &r = c->ranges;
+    LinesState &l = c->lines;
     GZPX_TRY(dslot_reserve(sl, ix->n ? ix->n : 1));
-    GZPX_TRY(rr_reserve(c, n, ix->n));
-    GZPX_TRY(ln_reserve(c, n * per));
+    GZPX_TRY(r.reserve(n, ix->n));
+    GZPX_TRY(l.reserve(n * per));
     hipStream_t stream = c->stream;
     GZPX_TRY(order_behind(stream, after, c->ev_dep));
     Drain drain{{stream}, 1};
-    const RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
     const LnTable tb{lt->d_prefix, lt->tiles, lt->n_delims, lt->n_lines, lt->inflated_len};
-    memcpy(c->h_ranges, bounds, n * per * 8);  // (room for 16 bytes an item)
-    HIP_TRY(hipMemcpyAsync(c->ln.bounds, c->h_ranges, n * per * 8, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->ev_l[0], stream));
-    launch_lines_tiles(tb, (uint32_t)n, per, c->ln, c->rr, stream);
-    launch_ranges_select(rix, (uint32_t)n, 0, c->rr, sl.d_offsets, sl.d_sizes, stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_l[1], stream));
-    HIP_TRY(hipMemcpyAsync(c->h_lrec, c->ln.rec, 32, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(c->h_rrec, c->rr.rec, 32, hipMemcpyDeviceToHost, stream));
+    GZPX_TRY(select_enqueue(c, sl, ix, bounds, n * per * 8, l.ln.bounds, n, 0, l.ev,
+                            [&] { launch_lines_tiles(tb, (uint32_t)n, per, l.ln, r.rr, stream); }));
+    HIP_TRY(hipMemcpyAsync(l.h_rec, l.ln.rec, 32, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(r.h_rec, r.rr.rec, 32, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));  // the record: the round trip in front of the inflate
-    c->ln_stages = 1;
-    if (c->h_lrec[kLnRecBad] != 0xFFFFFFFFu || c->h_rrec[kRrRecBad] != 0xFFFFFFFFu) {
-        if (bad) *bad = c->h_lrec[kLnRecBad] != 0xFFFFFFFFu ? c->h_lrec[kLnRecBad] : c->h_rrec[kRrRecBad];
+    l.stages = 1;
+    const Selection sel = selection_read(c);
+    if (l.h_rec[kLnRecBad] != 0xFFFFFFFFu || sel.bad != 0xFFFFFFFFu) {
+        if (bad) *bad = l.h_rec[kLnRecBad] != 0xFFFFFFFFu ? l.h_rec[kLnRecBad] : sel.bad;
         return GZPX_ERR_INVALID_ARG;
     }
-    const size_t nsel = c->h_rrec[kRrRecSelected];
-    const uint64_t stage_bytes = (uint64_t)c->h_rrec[kRrRecStage] | ((uint64_t)c->h_rrec[kRrRecStage + 1] << 32);
-    GZPX_TRY(grow(c->stage_mem, c->stage_cap, (size_t)(stage_bytes + 64), (size_t)(stage_bytes + stage_bytes / 8 + 4096),
-                  [&](size_t cap) { return c->stage_mem.dev(c->d_stage, cap); }));
-    HIP_TRY(hipEventRecord(c->ev_l[2], stream));
-    if (nsel) {  // (as gzpx_read_ranges_device sizes and launches it)
-        GZPX_TRY(dslot_prepare(c, sl, nsel, c->route, (size_t)stage_bytes, (uint64_t)(ix->consumed / ix->n) * nsel));
-        launch_inflate(header_bytes(c->format), d_in, sl.d_offsets, sl.d_sizes, (uint32_t)nsel, sl.d_blk, sl.d_out_off,
-                       c->d_stage, stage_bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, sl.ev_tm);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
-    }
-    HIP_TRY(hipEventRecord(c->ev_l[3], stream));
+    GZPX_TRY(c->stage.reserve(sel.stage_bytes));
+    HIP_TRY(hipEventRecord(l.ev[2], stream));  // (recorded with nothing selected too, unlike a read by byte range)
+    if (sel.n) GZPX_TRY(inflate_selection(c, sl, ix, d_in, sel));
+    HIP_TRY(hipEventRecord(l.ev[3], stream));
     // (enqueued behind the inflate without asking how it went: whatever staging holds, the walk stays inside its tiles)
-    launch_lines_find(tb, (uint32_t)n, per, lt->delim, c->ln, c->rr, c->d_stage, stream);
+    launch_lines_find(tb, (uint32_t)n, per, lt->delim, l.ln, r.rr, c->stage.d, stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_l[4], stream));
-    HIP_TRY(hipMemcpyAsync(c->h_bpos, c->ln.bpos, n * per * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(l.ev[4], stream));
+    HIP_TRY(hipMemcpyAsync(l.h_bpos, l.ln.bpos, n * per * 8, hipMemcpyDeviceToHost, stream));
     if (per == 2u) {
-        HIP_TRY(hipMemcpyAsync(c->h_lrec, c->ln.rec, 32, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(c->h_out_off, c->rr.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(l.h_rec, l.ln.rec, 32, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(r.h_out_off, r.rr.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));  // the positions: the total is known only now
     drain.armed = false;
-    c->ln_stages = 3;
-    if (nsel) {
+    l.stages = 3;
+    if (sel.n) {
         c->last_slot = si;
-        c->last_nb = nsel;
-        gzpx_check_info failed = {0, 0, 0};  // the first failing member of the selection, in stream order
-        const int verdict = summary_verdict(sl.h_summary, false, &failed);
-        if (verdict != GZPX_OK) {
-            uint32_t member = 0;  // its index in the stream, through the rank map
-            HIP_TRY(hipMemcpy(&member, c->rr.map + failed.block, 4, hipMemcpyDeviceToHost));
-            failed.block = member;
-            if (info) *info = failed;
-            return verdict;
-        }
+        c->last_nb = sel.n;
+        GZPX_TRY(selection_verdict(c, sl, info));
     }
-    c->last_ln_members = nsel;
-    if (total) *total = (uint64_t)c->h_lrec[kLnRecTotal] | ((uint64_t)c->h_lrec[kLnRecTotal + 1] << 32);
+    l.last_members = sel.n;
+    if (total) *total = rec_u64(l.h_rec, kLnRecTotal);
     return GZPX_OK;
 }
 
@@ -2458,15 +2590,15 @@ int gzpx_dlines_build_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_
     if (n_delims) *n_delims = 0;
     if (n_lines) *n_lines = 0;
     if (delim > 255u) return GZPX_ERR_INVALID_ARG;
-    if (ix->device != c->device || ix->format != c->format || in_len < ix->consumed) return GZPX_ERR_INVALID_ARG;
+    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
     const uint64_t total = ix->inflated_len;
     const uint64_t tiles = (total + kLnTile - 1u) / kLnTile;
     if (tiles > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
     std::unique_lock<std::mutex> lk(c->mu);
-    c->ln_build_ms[0] = c->ln_build_ms[1] = 0.0f;
+    LinesState &l = c->lines;
+    l.build_ms[0] = l.build_ms[1] = 0.0f;
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    const int si = free_slot(c, lk, true);
-    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
     std::unique_ptr<gzpx_dlines> lt(new (std::nothrow) gzpx_dlines());  // (c's device is current: a return frees it)
     if (!lt) return GZPX_ERR_DEVICE;
     lt->device = ix->device;
@@ -2476,7 +2608,6 @@ int gzpx_dlines_build_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_
     lt->inflated_len = total;
     lt->delim = delim;
     lt->tiles = (uint32_t)tiles;
-    const size_t n = ix->n;
     uint32_t *d_cnt = nullptr;  // [tiles] the tiles' counters: the build's own
     Allocs tmp;
     hipStream_t stream = c->stream;
@@ -2484,69 +2615,27 @@ int gzpx_dlines_build_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_
     GZPX_TRY(lt->mem.dev(lt->d_prefix, (size_t)(tiles + 1) * 8));
     GZPX_TRY(lt->mem.dev(lt->d_rec, 64));
     GZPX_TRY(tmp.dev(d_cnt, (size_t)(tiles ? tiles : 1) * 4));
-    GZPX_TRY(ln_reserve(c, 1));  // (the events)
-    // whole members in batches of at most `batch` inflated bytes, a larger member on its own: cut on the host from the
-    // index's prefix sums
-    std::vector<uint64_t> ustart(n + 1, 0);
-    if (n) HIP_TRY(hipMemcpy(ustart.data(), ix->d_ustart, (n + 1) * 8, hipMemcpyDeviceToHost));
-    const uint64_t batch = c->lines_batch ? c->lines_batch : kLinesBatchDefault;
-    std::vector<size_t> cuts(1, 0);
-    uint64_t max_bytes = 0;
-    size_t max_members = 1;
-    for (size_t m0 = 0; m0 < n;) {
-        size_t m1 = m0 + 1;
-        while (m1 < n && ustart[m1 + 1] - ustart[m0] <= batch) m1++;
-        if (ustart[m1] - ustart[m0] > max_bytes) max_bytes = ustart[m1] - ustart[m0];
-        if (m1 - m0 > max_members) max_members = m1 - m0;
-        cuts.push_back(m1);
-        m0 = m1;
-    }
-    GZPX_TRY(dslot_reserve(sl, max_members));
-    GZPX_TRY(grow(c->stage_mem, c->stage_cap, (size_t)(max_bytes + 64), (size_t)(max_bytes + max_bytes / 8 + 4096),
-                  [&](size_t cap) { return c->stage_mem.dev(c->d_stage, cap); }));
+    GZPX_TRY(l.reserve(1));  // (the events)
+    Batches b;
+    GZPX_TRY(batches_of(c, ix, b));
     GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
     HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(tiles ? tiles : 1) * 4, stream));
     HIP_TRY(hipMemsetAsync(lt->d_rec, 0, 64, stream));
-    for (size_t k = 0; k + 1 < cuts.size(); k++) {
-        const size_t m0 = cuts[k], nb = cuts[k + 1] - m0;
-        const uint64_t base = ustart[m0], bytes = ustart[m0 + nb] - base;
-        // (the stream's average member stands for the batch's; the members' records stay on the device)
-        GZPX_TRY(dslot_prepare(c, sl, nb, c->route, (size_t)bytes, (uint64_t)(ix->consumed / n) * nb));
-        HIP_TRY(hipEventRecord(c->ev_l[0], stream));
-        launch_inflate(header_bytes(c->format), (const uint8_t *)d_in, ix->d_off + m0, ix->d_size + m0, (uint32_t)nb, sl.d_blk,
-                       sl.d_out_off, c->d_stage, bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route,
-                       sl.ev_tm);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(c->ev_l[1], stream));
-        launch_lines_count(c->d_stage, base, bytes, total, delim, d_cnt, lt->d_rec, stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_l[2], stream));
-        HIP_TRY(hipStreamSynchronize(stream));  // (staging is the next batch's too; its verdict decides whether there is one)
-        c->last_slot = si;
-        c->last_nb = nb;
-        float ms[2] = {0.0f, 0.0f};
-        if (hipEventElapsedTime(&ms[0], c->ev_l[0], c->ev_l[1]) == hipSuccess &&
-            hipEventElapsedTime(&ms[1], c->ev_l[1], c->ev_l[2]) == hipSuccess) {
-            c->ln_build_ms[0] += ms[0];
-            c->ln_build_ms[1] += ms[1];
-        }
-        gzpx_check_info failed = {0, 0, 0};
-        const int verdict = summary_verdict(sl.h_summary, false, &failed);
-        if (verdict != GZPX_OK) {
-            failed.block += m0;  // its index in the stream
-            if (info) *info = failed;
-            drain.armed = false;
-            return verdict;
-        }
-    }
+    GZPX_TRY(batched_pass(
+        c, si, ix, b, (const uint8_t *)d_in, 0, l.ev, 2, l.build_ms, info, drain, [&](uint64_t base, uint64_t bytes, bool) -> int {
+            HIP_TRY(hipEventRecord(l.ev[1], stream));
+            launch_lines_count(c->stage.d, base, bytes, total, delim, d_cnt, lt->d_rec, stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(l.ev[2], stream));
+            return GZPX_OK;
+        }));
     launch_lines_prefix(d_cnt, (uint32_t)tiles, total, lt->d_prefix, lt->d_rec, stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_lrec, lt->d_rec, 32, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(l.h_rec, lt->d_rec, 32, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
-    lt->n_delims = (uint64_t)c->h_lrec[kLnRecD] | ((uint64_t)c->h_lrec[kLnRecD + 1] << 32);
-    lt->n_lines = (uint64_t)c->h_lrec[kLnRecL] | ((uint64_t)c->h_lrec[kLnRecL + 1] << 32);
+    lt->n_delims = rec_u64(l.h_rec, kLnRecD);
+    lt->n_lines = rec_u64(l.h_rec, kLnRecL);
     if (n_delims) *n_delims = lt->n_delims;
     if (n_lines) *n_lines = lt->n_lines;
     *out = lt.release();
@@ -2561,107 +2650,54 @@ int gzpx_find_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size
     *n_hits = 0;
     if (pattern_len == 0 || pattern_len > kFdMaxPattern || delim < GZPX_FIND_NO_LINES || delim > 255) return GZPX_ERR_INVALID_ARG;
     if (d_lines && delim == GZPX_FIND_NO_LINES) return GZPX_ERR_INVALID_ARG;
-    if (ix->device != c->device || ix->format != c->format || in_len < ix->consumed) return GZPX_ERR_INVALID_ARG;
+    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
     const uint64_t total = ix->inflated_len;
-    const size_t n = ix->n;
     const uint32_t m = (uint32_t)pattern_len;
     const bool writes = d_positions || d_lines;
     const uint64_t cap = writes ? hits_cap : 0;
     std::unique_lock<std::mutex> lk(c->mu);
-    c->fd_ms[0] = c->fd_ms[1] = c->fd_ms[2] = 0.0f;
-    if (!n || m > total) return GZPX_OK;  // (no position can hold the pattern: nothing is inflated)
+    FindState &f = c->find;
+    f.ms[0] = f.ms[1] = f.ms[2] = 0.0f;
+    if (!ix->n || m > total) return GZPX_OK;  // (no position can hold the pattern: nothing is inflated)
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    const int si = free_slot(c, lk, true);
-    DSlot &sl = c->slots[si];  // (stays free: the call returns synchronised under the lock)
-    FindScratch &f = c->fd;
-    if (!f.rec) {
-        GZPX_TRY(c->fd_once.dev(f.pat, kFdMaxPattern));
-        GZPX_TRY(c->fd_once.dev(f.rec, kFdRecWords * 8));
-        GZPX_TRY(c->fd_once.pinned(c->h_fpat, kFdMaxPattern));
-        GZPX_TRY(c->fd_once.pinned(c->h_frec, kFdRecWords * 8));
-        for (Event &e : c->ev_f) GZPX_TRY(e.create(true));
-    }
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
     hipStream_t stream = c->stream;
     Drain drain{{stream}, 1};
-    // whole members in batches, cut as gzpx_dlines_build_device cuts them
-    std::vector<uint64_t> ustart(n + 1, 0);
-    HIP_TRY(hipMemcpy(ustart.data(), ix->d_ustart, (n + 1) * 8, hipMemcpyDeviceToHost));
-    const uint64_t batch = c->lines_batch ? c->lines_batch : kLinesBatchDefault;
-    std::vector<size_t> cuts(1, 0);
-    uint64_t max_bytes = 0;
-    size_t max_members = 1;
-    for (size_t m0 = 0; m0 < n;) {
-        size_t m1 = m0 + 1;
-        while (m1 < n && ustart[m1 + 1] - ustart[m0] <= batch) m1++;
-        if (ustart[m1] - ustart[m0] > max_bytes) max_bytes = ustart[m1] - ustart[m0];
-        if (m1 - m0 > max_members) max_members = m1 - m0;
-        cuts.push_back(m1);
-        m0 = m1;
-    }
-    GZPX_TRY(dslot_reserve(sl, max_members));
-    const size_t stage_need = (size_t)(kFdPad + max_bytes + 64);
-    GZPX_TRY(grow(c->stage_mem, c->stage_cap, stage_need, stage_need + (size_t)(max_bytes / 8) + 4096,
-                  [&](size_t cap_bytes) { return c->stage_mem.dev(c->d_stage, cap_bytes); }));
-    const size_t pieces = (size_t)find_pieces(max_bytes);
-    GZPX_TRY(grow(c->fd_pieces, c->fd_piece_cap, pieces, pieces + pieces / 8 + 16, [&](size_t cap_pieces) -> int {
-        GZPX_TRY(c->fd_pieces.dev(f.cnt, cap_pieces * 8));
-        return c->fd_pieces.dev(f.bases, cap_pieces * 16);
-    }));
+    Batches b;
+    GZPX_TRY(batches_of(c, ix, b));
+    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
     GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
-    memset(c->h_fpat, 0, kFdMaxPattern);
-    memcpy(c->h_fpat, pattern, m);
-    HIP_TRY(hipMemcpyAsync(f.pat, c->h_fpat, kFdMaxPattern, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(f.rec, 0, kFdRecWords * 8, stream));
-    uint8_t *const out = c->d_stage + kFdPad;  // the inflate writes behind the pad
-    for (size_t k = 0; k + 1 < cuts.size(); k++) {
-        const size_t m0 = cuts[k], nb = cuts[k + 1] - m0;
-        const uint64_t base = ustart[m0], bytes = ustart[m0 + nb] - base;
-        const FindBatch fb{c->d_stage, base, bytes, (uint32_t)(base < m - 1u ? base : m - 1u), m, d_lines ? delim : GZPX_FIND_NO_LINES};
-        GZPX_TRY(dslot_prepare(c, sl, nb, c->route, (size_t)bytes, (uint64_t)(ix->consumed / n) * nb));
-        HIP_TRY(hipEventRecord(c->ev_f[0], stream));
-        launch_inflate(header_bytes(c->format), (const uint8_t *)d_in, ix->d_off + m0, ix->d_size + m0, (uint32_t)nb, sl.d_blk,
-                       sl.d_out_off, out, bytes, sl.d_crc, c->cc, c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, sl.ev_tm);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(c->ev_f[1], stream));
-        // (enqueued behind the inflate without asking how it went: whatever staging holds, the search stays inside it)
-        if (bytes) launch_find_count(fb, f, stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_f[2], stream));
-        if (bytes && cap) launch_find_write(fb, f, d_positions, d_lines, cap, stream);
-        const uint64_t seen = base + bytes;
-        const uint32_t carry = (uint32_t)(seen < m - 1u ? seen : m - 1u);  // (a batch shorter than that appends to the carry)
-        if (bytes && carry && k + 2 < cuts.size()) launch_find_carry(fb, f, carry, stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_f[3], stream));
-        HIP_TRY(hipStreamSynchronize(stream));  // (staging is the next batch's too; its verdict decides whether there is one)
-        c->last_slot = si;
-        c->last_nb = nb;
-        float ms[3] = {0.0f, 0.0f, 0.0f};
-        if (hipEventElapsedTime(&ms[0], c->ev_f[0], c->ev_f[1]) == hipSuccess &&
-            hipEventElapsedTime(&ms[1], c->ev_f[1], c->ev_f[2]) == hipSuccess &&
-            hipEventElapsedTime(&ms[2], c->ev_f[2], c->ev_f[3]) == hipSuccess)
-            for (int j = 0; j < 3; j++) c->fd_ms[j] += ms[j];
-        gzpx_check_info failed = {0, 0, 0};
-        const int verdict = summary_verdict(sl.h_summary, false, &failed);
-        if (verdict != GZPX_OK) {
-            failed.block += m0;  // its index in the stream
-            if (info) *info = failed;
-            drain.armed = false;
-            return verdict;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_frec, f.rec, kFdRecWords * 8, hipMemcpyDeviceToHost, stream));
+    memset(f.h_pat, 0, kFdMaxPattern);
+    memcpy(f.h_pat, pattern, m);
+    HIP_TRY(hipMemcpyAsync(f.fd.pat, f.h_pat, kFdMaxPattern, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(f.fd.rec, 0, kFdRecWords * 8, stream));
+    GZPX_TRY(batched_pass(
+        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, f.ev, 3, f.ms, info, drain,
+        [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
+            const FindBatch fb{c->stage.d, base, bytes, (uint32_t)(base < m - 1u ? base : m - 1u), m, d_lines ? delim : GZPX_FIND_NO_LINES};
+            HIP_TRY(hipEventRecord(f.ev[1], stream));
+            if (bytes) launch_find_count(fb, f.fd, stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(f.ev[2], stream));
+            if (bytes && cap) launch_find_write(fb, f.fd, d_positions, d_lines, cap, stream);
+            const uint64_t seen = base + bytes;
+            const uint32_t carry = (uint32_t)(seen < m - 1u ? seen : m - 1u);  // (a batch shorter than that appends to the carry)
+            if (bytes && carry && !is_last) launch_find_carry(fb, f.fd, carry, stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(f.ev[3], stream));
+            return GZPX_OK;
+        }));
+    HIP_TRY(hipMemcpyAsync(f.h_rec, f.fd.rec, kFdRecWords * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
-    *n_hits = c->h_frec[kFdRecHits];
+    *n_hits = f.h_rec[kFdRecHits];
     return writes && *n_hits > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
 }
 
 int gzpx_dctx_last_find_ms(gzpx_dctx *ctx, float ms[3]) {
     if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
-    for (int j = 0; j < 3; j++) ms[j] = ctx->fd_ms[j];
+    for (int j = 0; j < 3; j++) ms[j] = ctx->find.ms[j];
     return GZPX_OK;
 }
 
@@ -2682,13 +2718,13 @@ int gzpx_line_offsets_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dli
     if (bad) *bad = (size_t)-1;
     if (!lines_match(c, ix, lt, in_len) || n > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
     std::unique_lock<std::mutex> lk(c->mu);
-    c->ln_stages = 0;
-    c->last_ln_members = 0;
+    c->lines.stages = 0;
+    c->lines.last_members = 0;
     if (n == 0) return GZPX_OK;
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
     const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
     GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, lines, n, 1u, bad, info, (hipStream_t)hip_stream, nullptr));
-    memcpy(offsets, c->h_bpos, n * 8);
+    memcpy(offsets, c->lines.h_bpos, n * 8);
     return GZPX_OK;
 }
 
@@ -2703,8 +2739,8 @@ int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dline
     if (bad_range) *bad_range = (size_t)-1;
     if (!lines_match(c, ix, lt, in_len) || n_ranges > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
     std::unique_lock<std::mutex> lk(c->mu);
-    c->ln_stages = 0;
-    c->last_ln_members = 0;
+    c->lines.stages = 0;
+    c->lines.last_members = 0;
     if (n_ranges == 0) {
         if (out_offsets) out_offsets[0] = 0;
         return GZPX_OK;
@@ -2714,22 +2750,22 @@ int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dline
     uint64_t total = 0;
     GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, (const uint64_t *)line_ranges, n_ranges, 2u, bad_range, info,
                           (hipStream_t)hip_stream, &total));
-    if (byte_ranges) memcpy(byte_ranges, c->h_bpos, n_ranges * 16);
+    if (byte_ranges) memcpy(byte_ranges, c->lines.h_bpos, n_ranges * 16);
     if (total > out_cap) {
         *out_len = (size_t)total;
         return GZPX_ERR_INSUFFICIENT_SPACE;
     }
     if (total >> 44) return GZPX_ERR_INVALID_ARG;  // (the gather's grid)
-    if (out_offsets) memcpy(out_offsets, c->h_out_off, (n_ranges + 1) * 8);
+    if (out_offsets) memcpy(out_offsets, c->ranges.h_out_off, (n_ranges + 1) * 8);
     hipStream_t stream = c->stream;
     Drain drain{{stream}, 1};
-    HIP_TRY(hipEventRecord(c->ev_l[5], stream));
-    launch_ranges_gather(c->d_stage, (uint32_t)n_ranges, c->rr, (uint8_t *)d_out, total, stream);
+    HIP_TRY(hipEventRecord(c->lines.ev[5], stream));
+    launch_ranges_gather(c->stage.d, (uint32_t)n_ranges, c->ranges.rr, (uint8_t *)d_out, total, stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_l[6], stream));
+    HIP_TRY(hipEventRecord(c->lines.ev[6], stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
-    c->ln_stages = 4;
+    c->lines.stages = 4;
     *out_len = (size_t)total;
     return GZPX_OK;
 }
@@ -2737,14 +2773,14 @@ int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dline
 int gzpx_dctx_set_lines_batch(gzpx_dctx *ctx, size_t inflated_bytes) {
     if (!ctx) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
-    ctx->lines_batch = inflated_bytes;
+    ctx->lines.batch = inflated_bytes;
     return GZPX_OK;
 }
 
 int gzpx_dctx_last_lines_members(gzpx_dctx *ctx, size_t *n_members_read) {
     if (!ctx || !n_members_read) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
-    *n_members_read = ctx->last_ln_members;
+    *n_members_read = ctx->lines.last_members;
     return GZPX_OK;
 }
 
@@ -2752,20 +2788,20 @@ int gzpx_dctx_last_lines_ms(gzpx_dctx *ctx, float ms[4]) {
     if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
     ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
-    const int have = ctx->ln_stages;
-    if (have >= 1 && hipEventElapsedTime(&ms[0], ctx->ev_l[0], ctx->ev_l[1]) != hipSuccess) return GZPX_ERR_DEVICE;
-    if (have >= 3 && (hipEventElapsedTime(&ms[1], ctx->ev_l[2], ctx->ev_l[3]) != hipSuccess ||
-                      hipEventElapsedTime(&ms[2], ctx->ev_l[3], ctx->ev_l[4]) != hipSuccess))
+    const Event *ev = ctx->lines.ev;
+    const int have = ctx->lines.stages;
+    if (have >= 1 && hipEventElapsedTime(&ms[0], ev[0], ev[1]) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (have >= 3 && (hipEventElapsedTime(&ms[1], ev[2], ev[3]) != hipSuccess || hipEventElapsedTime(&ms[2], ev[3], ev[4]) != hipSuccess))
         return GZPX_ERR_DEVICE;
-    if (have >= 4 && hipEventElapsedTime(&ms[3], ctx->ev_l[5], ctx->ev_l[6]) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (have >= 4 && hipEventElapsedTime(&ms[3], ev[5], ev[6]) != hipSuccess) return GZPX_ERR_DEVICE;
     return GZPX_OK;
 }
 
 int gzpx_dctx_last_lines_build_ms(gzpx_dctx *ctx, float ms[2]) {
     if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
-    ms[0] = ctx->ln_build_ms[0];
-    ms[1] = ctx->ln_build_ms[1];
+    ms[0] = ctx->lines.build_ms[0];
+    ms[1] = ctx->lines.build_ms[1];
     return GZPX_OK;
 }
 
@@ -2857,6 +2893,8 @@ void gzpx_free_decompressor(gzpx_decompressor *d) {
 }  // extern "C"
 
 // ---------------------------------------------------------------- measurement / debug hooks
+extern "C" {
+
 int gzpx_ctx_set_profiling(gzpx_ctx *ctx, int on) {
     if (!ctx) return GZPX_ERR_INVALID_ARG;
     ctx->profiling = on == 2 ? 2 : on != 0 ? 1 : 0;

@@ -122,6 +122,39 @@ def _zlib_batch(emu_lib, d, mem):
     assert got == (45000, 0) and mem.get(keep[4][0], 45000) == b"".join(parts)
 
 
+def _line_reads_and_find(d, mem, ix, ptr, s, plain, batch):
+    """A line table built in batches of `batch` inflated bytes, one line_offsets, one read_lines and one find with
+    positions and line numbers, each against the host's answer."""
+    starts = [0] + [i + 1 for i, ch in enumerate(plain) if ch == 10]
+    d.set_lines_batch(batch)
+    with d.build_lines_device(ix, ptr, len(s)) as lt:
+        assert (lt.n_delims, lt.n_lines) == (len(starts) - 1, len(starts) - (plain[-1:] == b"\n"))
+        ks = [0, 1, len(starts) // 2, len(starts) - 1]
+        assert d.line_offsets_device(ix, lt, ptr, len(s), ks).tolist() == [starts[k] for k in ks]
+        ranges = [(0, 2), (len(starts) // 2, len(starts) // 2 + 3), (5, 5)]
+        want = b"".join(plain[starts[a]:starts[b]] for a, b in ranges)
+        out, p_out = mem.empty(len(want) + 64)
+        m, o, br = d.read_lines_device(ix, lt, ptr, len(s), ranges, p_out, len(want))
+        assert m == len(want) and mem.get(out, m) == want
+        assert o.tolist() == np.cumsum([0] + [starts[b] - starts[a] for a, b in ranges]).tolist()
+    pattern = plain[starts[1]:starts[1] + 3]
+    hits = [i for i in range(len(plain) - 2) if plain[i:i + 3] == pattern]
+    pos, p_pos = mem.empty(len(hits) * 8)
+    lns, p_lns = mem.empty(len(hits) * 8)
+    assert d.find_device(ix, ptr, len(s), pattern, 10, p_pos, p_lns, len(hits)) == len(hits) > 0
+    assert np.frombuffer(mem.get(pos, len(hits) * 8), dtype=np.uint64).tolist() == hits
+    assert np.frombuffer(mem.get(lns, len(hits) * 8), dtype=np.uint64).tolist() == \
+        (np.searchsorted(starts, hits, side="right") - 1).tolist()
+
+
+def _checksum_batch(d, mem):
+    parts = [_text(5000, 21).tobytes(), b"", _text(40000, 22).tobytes()]
+    keep = [mem.put(b"".join(parts)), mem.put(np.cumsum([0] + [len(p) for p in parts]).astype(np.uint64).view(np.uint8)),
+            mem.empty(3 * 4)]
+    assert d.checksum_batch_device(_native.CHECK_ADLER32, keep[0][1], 45000, keep[1][1], None, 3, keep[2][1]) == (0, None)
+    assert np.frombuffer(mem.get(keep[2][0], 12), dtype=np.uint32).tolist() == [zlib.adler32(p) for p in parts]
+
+
 def test_dcontext_gives_everything_back(emu_lib, oracle, live):
     before = live()
     mem = Mem(emu_lib)
@@ -149,8 +182,10 @@ def test_dcontext_gives_everything_back(emu_lib, oracle, live):
                     m, o = d.read_ranges_device(ix, ptr, len(s), ranges, p_out, len(want))
                     assert m == len(want) and mem.get(out, m) == want
                     assert o.tolist() == np.cumsum([0] + [e - b for b, e in ranges]).tolist()
+                _line_reads_and_find(d, mem, ix, ptr, s, plain, 20 * DBS)  # (40 members: two batches)
                 assert live() != before
             _zlib_batch(emu_lib, d, mem)
+            _checksum_batch(d, mem)
     assert live() == before
 
 
@@ -163,7 +198,25 @@ def _compress_steps(oracle, kind):
             [lambda c: _check_slab(oracle, c, level, 100), lambda c: _check_slab(oracle, c, level, SLAB3)])
 
 
+def _indexed_reads(emu_lib, oracle, d):
+    """index build -> read ranges -> lines build -> read lines -> find -> checksum batch, on a stream of three members."""
+    mem = Mem(emu_lib)
+    plain, s = _members(oracle, 3)
+    keep, ptr = mem.put(s)
+    with d.build_index_device(ptr, len(s)) as ix:
+        ranges = [(100, 877), (DBS - 5, DBS + 5), (len(plain) - 9, len(plain))]
+        want = b"".join(plain[b:e] for b, e in ranges)
+        out, p_out = mem.empty(len(want) + 64)
+        m, o = d.read_ranges_device(ix, ptr, len(s), ranges, p_out, len(want))
+        assert m == len(want) and mem.get(out, m) == want
+        _line_reads_and_find(d, mem, ix, ptr, s, plain, 2 * DBS)  # (two batches)
+    _checksum_batch(d, mem)
+
+
 def _sequence(oracle, kind):
+    if kind == "dreads":
+        return (lambda lib: _native.DContext(format=_native.FORMAT_BGZF, lib=lib),
+                [lambda d: _indexed_reads(d.lib, oracle, d)])
     if kind == "dctx":
         return (lambda lib: _native.DContext(format=_native.FORMAT_BGZF, lib=lib),
                 [lambda d: _check_inflate(oracle, d, 1), lambda d: _check_inflate(oracle, d, 40)])
@@ -177,7 +230,7 @@ def _run(emu_lib, make, steps):
             step(c)
 
 
-@pytest.mark.parametrize("kind", ["bgzf1", "bgzf6", "snap", "dctx"])
+@pytest.mark.parametrize("kind", ["bgzf1", "bgzf6", "snap", "dctx", "dreads"])
 def test_any_failing_allocation_leaves_nothing_behind(emu_lib, oracle, live, kind):
     L = _hooks(emu_lib)
     make, steps = _sequence(oracle, kind)

@@ -47,6 +47,7 @@ CHECK_CRC32, CHECK_ADLER32, CHECK_CRC32C = 0, 1, 2  # checksum_batch_device: zli
 LINES_TILE = 16384  # GZPX_LINES_TILE: the tile of the line table, in bytes of the inflated stream
 FIND_MAX_PATTERN = 256  # GZPX_FIND_MAX_PATTERN
 FIND_NO_LINES = -1      # GZPX_FIND_NO_LINES
+SELECT_INVERT = 1       # GZPX_SELECT_INVERT
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -77,6 +78,7 @@ EXPORTS = [
     "gzpx_read_lines_device", "gzpx_dctx_set_lines_batch", "gzpx_dctx_last_lines_members", "gzpx_dctx_last_lines_ms",
     "gzpx_dctx_last_lines_build_ms",
     "gzpx_find_device", "gzpx_dctx_last_find_ms",
+    "gzpx_select_lines_device", "gzpx_dctx_last_select_ms", "gzpx_read_lines_table_device",
 ]
 
 
@@ -284,6 +286,14 @@ class GzpxLib:
         L.gzpx_find_device.argtypes = [vp, vp, vp, sz, vp, sz, ctypes.c_int, vp, vp, sz, pu64, ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_dctx_last_find_ms.restype = i32
         L.gzpx_dctx_last_find_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_select_lines_device.restype = i32
+        L.gzpx_select_lines_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint64, ctypes.c_uint, vp, sz, pu64, pu64, pu64,
+                                               ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_select_ms.restype = i32
+        L.gzpx_dctx_last_select_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_read_lines_table_device.restype = i32
+        L.gzpx_read_lines_table_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, sz, psz, vp, vp, psz,
+                                                   ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_inflate_batch_device.restype = i32
         L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
                                                 ctypes.POINTER(GzpxCheckInfo), vp]
@@ -1025,6 +1035,54 @@ class DContext:
         ms = (ctypes.c_float * 3)()
         self.lib.check(self.lib.L.gzpx_dctx_last_find_ms(self.h, ms))
         return ms[0], ms[1], ms[2]
+
+    # ---- selection of lines by content (gzpx_select.h)
+    def select_lines_device(self, index, lines, d_in_ptr, in_len, pattern, group=1, invert=False, d_runs_ptr=None, runs_cap=0,
+                            stream=None):
+        """The records of `group` lines in which a hit of `pattern` lies (invert: in which none does), as runs of
+        consecutive records: line ranges (begin, end) uint64 pairs, ascending, into the device array d_runs_ptr
+        (runs_cap entries; None counts only).  Returns (n_runs, n_records, n_hits).  More runs than runs_cap: the first
+        runs_cap are written and GzpxError is raised with .needed = n_runs."""
+        pat = bytes(pattern)
+        runs, records, hits = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_select_lines_device(self.h, index.h, lines.h, d_in_ptr, in_len, pat, len(pat), int(group),
+                                                 SELECT_INVERT if invert else 0, d_runs_ptr, runs_cap, ctypes.byref(runs),
+                                                 ctypes.byref(records), ctypes.byref(hits), ctypes.byref(info), stream)
+        if rc == OK:
+            return runs.value, records.value, hits.value
+        if rc == ERR_INSUFFICIENT_SPACE and runs.value:
+            raise GzpxError(rc, "the selection has %d runs" % runs.value, needed=runs.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def last_select_ms(self):
+        """HIP-event durations of the last select_lines_device: (inflate, count + scan + mark, runs); the first two summed
+        over its batches."""
+        ms = (ctypes.c_float * 3)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_select_ms(self.h, ms))
+        return ms[0], ms[1], ms[2]
+
+    def read_lines_table_device(self, index, lines, d_in_ptr, in_len, d_line_ranges_ptr, n_ranges, d_out_ptr, out_cap,
+                                d_out_offsets_ptr=None, d_byte_ranges_ptr=None, stream=None):
+        """read_lines_device with its tables in device memory: d_line_ranges_ptr is uint64[n_ranges, 2], and the optional
+        d_out_offsets_ptr (uint64[n_ranges + 1]) and d_byte_ranges_ptr (uint64[n_ranges, 2]) are written there.  Returns
+        out_len.  A bad range raises GzpxError with .range_index; too small an out_cap raises it with .needed."""
+        out_len, bad = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_read_lines_table_device(self.h, index.h, lines.h, d_in_ptr, in_len, d_line_ranges_ptr, n_ranges,
+                                                     d_out_ptr, out_cap, ctypes.byref(out_len), d_out_offsets_ptr,
+                                                     d_byte_ranges_ptr, ctypes.byref(bad), ctypes.byref(info), stream)
+        if rc == OK:
+            return out_len.value
+        if bad.value != ctypes.c_size_t(-1).value:
+            raise GzpxError(rc, "line range %d does not lie in the stream" % bad.value, range_index=bad.value)
+        if rc == ERR_INSUFFICIENT_SPACE and out_len.value:
+            raise GzpxError(rc, "the line ranges hold %d bytes" % out_len.value, needed=out_len.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
 
     # ---- batches of raw / zlib / gzip members that lie in device memory (gzpx_wrap.h)
     def inflate_batch_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr,

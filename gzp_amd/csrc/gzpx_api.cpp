@@ -1468,12 +1468,13 @@ struct RangesState : NoCopy {
     RangeScratch rr;
     uint32_t *h_rec = nullptr;  // pinned: the record of locate + select
     Allocs once;                // rr.rec, h_rec
-    size_t range_cap = 0, member_cap = 0;
+    size_t range_cap = 0, host_cap = 0, member_cap = 0;
     uint64_t *h_ranges = nullptr;   // pinned: the caller's ranges on their way in
     uint64_t *h_out_off = nullptr;  // pinned: out_offsets on their way out
-    Allocs ranges;   // rr.ranges, first, len, src, out_off and the two pinned arrays above
+    Allocs ranges;   // rr.ranges, first, len, src, out_off
+    Allocs host;     // the two pinned arrays above: a call whose tables lie in device memory needs none
     Allocs members;  // rr.diff, map, soff
-    int reserve(size_t n_ranges, size_t n_members) {
+    int reserve(size_t n_ranges, size_t n_members, bool host_tables = true) {
         if (!rr.rec) {
             GZPX_TRY(once.dev(rr.rec, 64));
             GZPX_TRY(once.pinned(h_rec, 64));
@@ -1484,9 +1485,11 @@ struct RangesState : NoCopy {
             GZPX_TRY(ranges.dev(rr.first, cap * 4));
             GZPX_TRY(ranges.dev(rr.len, cap * 8));
             GZPX_TRY(ranges.dev(rr.src, cap * 8));
-            GZPX_TRY(ranges.dev(rr.out_off, (cap + 1) * 8));
-            GZPX_TRY(ranges.pinned(h_ranges, cap * 16));
-            return ranges.pinned(h_out_off, (cap + 1) * 8);
+            return ranges.dev(rr.out_off, (cap + 1) * 8);
+        }));
+        GZPX_TRY(grow(host, host_cap, host_tables ? n_ranges : 0, n_ranges + n_ranges / 4 + 64, [&](size_t cap) -> int {
+            GZPX_TRY(host.pinned(h_ranges, cap * 16));
+            return host.pinned(h_out_off, (cap + 1) * 8);
         }));
         return grow(members, member_cap, n_members + 1, n_members + n_members / 4 + 64, [&](size_t cap) -> int {
             GZPX_TRY(members.dev(rr.diff, cap * 4));
@@ -1536,21 +1539,23 @@ struct LinesState : NoCopy {
     LinesScratch ln;
     uint32_t *h_rec = nullptr;  // pinned: the search record
     Allocs once;                // ln.rec, h_rec
-    size_t cap = 0;             // boundaries
-    uint64_t *h_bpos = nullptr;  // pinned: the byte positions on their way out
-    Allocs bounds;               // ln.bounds, btile, bpos and h_bpos
-    int reserve(size_t n_bounds) {
+    size_t cap = 0, host_cap = 0;  // boundaries
+    uint64_t *h_bpos = nullptr;    // pinned: the byte positions on their way out
+    Allocs bounds;                 // ln.bounds, btile, bpos
+    Allocs host;                   // h_bpos: a call whose tables lie in device memory needs none
+    int reserve(size_t n_bounds, bool host_tables = true) {
         if (!ln.rec) {
             GZPX_TRY(once.dev(ln.rec, 64));
             GZPX_TRY(once.pinned(h_rec, 64));
             for (Event &e : ev) GZPX_TRY(e.create(true));
         }
-        return grow(bounds, cap, n_bounds, n_bounds + n_bounds / 4 + 64, [&](size_t n) -> int {
+        GZPX_TRY(grow(bounds, cap, n_bounds, n_bounds + n_bounds / 4 + 64, [&](size_t n) -> int {
             GZPX_TRY(bounds.dev(ln.bounds, n * 8));
             GZPX_TRY(bounds.dev(ln.btile, n * 4));
-            GZPX_TRY(bounds.dev(ln.bpos, n * 8));
-            return bounds.pinned(h_bpos, n * 8);
-        });
+            return bounds.dev(ln.bpos, n * 8);
+        }));
+        return grow(host, host_cap, host_tables ? n_bounds : 0, n_bounds + n_bounds / 4 + 64,
+                    [&](size_t n) { return host.pinned(h_bpos, n * 8); });
     }
 };
 
@@ -1579,6 +1584,33 @@ struct FindState : NoCopy {
     }
 };
 
+// selection of lines by content (gzpx_select_lines_device): the search's state for the counting pass of every batch, and
+// its own for the record bitmap and the runs
+struct SelectState : NoCopy {
+    Event ev[5];                       // per batch: inflate [0..1], count + scan + mark + carry [1..2]; the runs [3..4]
+    float ms[3] = {0.0f, 0.0f, 0.0f};  // the last call's, the first two summed over its batches
+    SelectScratch sl;
+    uint64_t *h_rec = nullptr;  // pinned: the record on its way out
+    uint64_t *h_run = nullptr;  // pinned: the one run of a call that inflates nothing, on its way in
+    Allocs once;                // sl.rec and the two pinned arrays above
+    size_t record_cap = 0;
+    Allocs records;  // sl.bitmap, cnt, bases
+    int reserve(uint64_t n_records) {
+        if (!sl.rec) {
+            GZPX_TRY(once.dev(sl.rec, kSlRecWords * 8));
+            GZPX_TRY(once.pinned(h_rec, kSlRecWords * 8));
+            GZPX_TRY(once.pinned(h_run, 16));
+            for (Event &e : ev) GZPX_TRY(e.create(true));
+        }
+        return grow(records, record_cap, (size_t)n_records, (size_t)(n_records + n_records / 8 + 4096), [&](size_t cap) -> int {
+            const size_t groups = (size_t)select_groups(cap);
+            GZPX_TRY(records.dev(sl.bitmap, (cap + 31) / 32 * 4));
+            GZPX_TRY(records.dev(sl.cnt, groups * 8));
+            return records.dev(sl.bases, groups * 4);
+        });
+    }
+};
+
 }  // namespace
 
 // (members are destroyed last to first: memory and events of the slots and of each kind of call, then the streams)
@@ -1600,6 +1632,7 @@ struct gzpx_dctx : NoCopy {
     CksumState cksum;
     LinesState lines;
     FindState find;
+    SelectState select;
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -2154,13 +2187,19 @@ Selection selection_read(const gzpx_dctx *c) {
 // `d_items`, and between ev[0] and ev[1] the kernels `pre` enqueues (the line calls': boundaries to tile covers) and
 // locate + select run, which leave the selected members' table in the slot's.  The caller copies the records it
 // reads back, synchronises -- the one round trip in front of the inflate -- and reads selection_read().
+// `on_device`: the items lie in device memory and come by a device-to-device copy behind whatever the context's stream
+// was ordered behind; nothing of them touches the host.
 template <class Pre>
-int select_enqueue(gzpx_dctx *c, DSlot &sl, const gzpx_dindex *ix, const void *items, size_t bytes, void *d_items, size_t n,
-                   int is_virtual, Event *ev, Pre &&pre) {
+int select_enqueue(gzpx_dctx *c, DSlot &sl, const gzpx_dindex *ix, const void *items, bool on_device, size_t bytes, void *d_items,
+                   size_t n, int is_virtual, Event *ev, Pre &&pre) {
     RangesState &r = c->ranges;
     const RrIndex rix{ix->d_off, ix->d_size, ix->d_ustart, (uint32_t)ix->n};
-    memcpy(r.h_ranges, items, bytes);  // (room for 16 bytes an item)
-    HIP_TRY(hipMemcpyAsync(d_items, r.h_ranges, bytes, hipMemcpyHostToDevice, c->stream));
+    if (on_device) {
+        HIP_TRY(hipMemcpyAsync(d_items, items, bytes, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        memcpy(r.h_ranges, items, bytes);  // (room for 16 bytes an item)
+        HIP_TRY(hipMemcpyAsync(d_items, r.h_ranges, bytes, hipMemcpyHostToDevice, c->stream));
+    }
     HIP_TRY(hipEventRecord(ev[0], c->stream));
     pre();
     launch_ranges_select(rix, (uint32_t)n, is_virtual, r.rr, sl.d_offsets, sl.d_sizes, c->stream);
@@ -2298,8 +2337,8 @@ int gzpx_read_ranges_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_i
     hipStream_t stream = c->stream;
     GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
     Drain drain{{stream}, 1};
-    GZPX_TRY(select_enqueue(c, sl, ix, ranges, n_ranges * sizeof(gzpx_range), r.rr.ranges, n_ranges, coords == GZPX_RANGE_VIRTUAL,
-                            r.ev, [] {}));
+    GZPX_TRY(select_enqueue(c, sl, ix, ranges, false, n_ranges * sizeof(gzpx_range), r.rr.ranges, n_ranges,
+                            coords == GZPX_RANGE_VIRTUAL, r.ev, [] {}));
     HIP_TRY(hipMemcpyAsync(r.h_rec, r.rr.rec, 32, hipMemcpyDeviceToHost, stream));
     if (out_offsets)
         HIP_TRY(hipMemcpyAsync(r.h_out_off, r.rr.out_off, (n_ranges + 1) * 8, hipMemcpyDeviceToHost, stream));
@@ -2524,19 +2563,23 @@ bool lines_match(const gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *l
 // selected, the selected members inflated into staging and the boundary tiles walked there.  Two round trips: the
 // record in front of the inflate, the positions behind the walk.  Returns with the stream idle; l.h_bpos then holds
 // start() of every boundary and, per == 2, c->ranges (rr, h_out_off) and *total describe the gather that is still to run.
+// `on_device`: `bounds` lies in device memory and is read where it lies, behind `after`; l.h_bpos and r.h_out_off stay
+// unwritten (the caller copies l.ln.bpos and r.rr.out_off on the device), so no table sized by n touches the host.  The
+// two records and their round trips are the same.
 int lines_search(gzpx_dctx *c, int si, const gzpx_dindex *ix, const gzpx_dlines *lt, const uint8_t *d_in, const uint64_t *bounds,
-                 size_t n, uint32_t per, size_t *bad, gzpx_check_info *info, hipStream_t after, uint64_t *total) {
+                 size_t n, uint32_t per, size_t *bad, gzpx_check_info *info, hipStream_t after, uint64_t *total,
+                 bool on_device = false) {
     DSlot &sl = c->slots[si];
     RangesState &r = c->ranges;
     LinesState &l = c->lines;
     GZPX_TRY(dslot_reserve(sl, ix->n ? ix->n : 1));
-    GZPX_TRY(r.reserve(n, ix->n));
-    GZPX_TRY(l.reserve(n * per));
+    GZPX_TRY(r.reserve(n, ix->n, !on_device));
+    GZPX_TRY(l.reserve(n * per, !on_device));
     hipStream_t stream = c->stream;
     GZPX_TRY(order_behind(stream, after, c->ev_dep));
     Drain drain{{stream}, 1};
     const LnTable tb{lt->d_prefix, lt->tiles, lt->n_delims, lt->n_lines, lt->inflated_len};
-    GZPX_TRY(select_enqueue(c, sl, ix, bounds, n * per * 8, l.ln.bounds, n, 0, l.ev,
+    GZPX_TRY(select_enqueue(c, sl, ix, bounds, on_device, n * per * 8, l.ln.bounds, n, 0, l.ev,
                             [&] { launch_lines_tiles(tb, (uint32_t)n, per, l.ln, r.rr, stream); }));
     HIP_TRY(hipMemcpyAsync(l.h_rec, l.ln.rec, 32, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(r.h_rec, r.rr.rec, 32, hipMemcpyDeviceToHost, stream));
@@ -2555,10 +2598,10 @@ int lines_search(gzpx_dctx *c, int si, const gzpx_dindex *ix, const gzpx_dlines 
     launch_lines_find(tb, (uint32_t)n, per, lt->delim, l.ln, r.rr, c->stage.d, stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(l.ev[4], stream));
-    HIP_TRY(hipMemcpyAsync(l.h_bpos, l.ln.bpos, n * per * 8, hipMemcpyDeviceToHost, stream));
+    if (!on_device) HIP_TRY(hipMemcpyAsync(l.h_bpos, l.ln.bpos, n * per * 8, hipMemcpyDeviceToHost, stream));
     if (per == 2u) {
         HIP_TRY(hipMemcpyAsync(l.h_rec, l.ln.rec, 32, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(r.h_out_off, r.rr.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
+        if (!on_device) HIP_TRY(hipMemcpyAsync(r.h_out_off, r.rr.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));  // the positions: the total is known only now
     drain.armed = false;
@@ -2728,10 +2771,15 @@ int gzpx_line_offsets_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dli
     return GZPX_OK;
 }
 
-int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
-                           const gzpx_range *line_ranges, size_t n_ranges, void *d_out, size_t out_cap, size_t *out_len,
-                           uint64_t *out_offsets, gzpx_range *byte_ranges, size_t *bad_range, gzpx_check_info *info,
-                           void *hip_stream) {
+}  // extern "C"
+
+namespace {
+
+// gzpx_read_lines_device, and with `on_device` gzpx_read_lines_table_device: line_ranges, out_offsets and byte_ranges
+// are then device arrays, and the two that are written are filled by device-to-device copies on the context's stream.
+int read_lines(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+               const gzpx_range *line_ranges, bool on_device, size_t n_ranges, void *d_out, size_t out_cap, size_t *out_len,
+               uint64_t *out_offsets, gzpx_range *byte_ranges, size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
     static_assert(sizeof(gzpx_range) == 16, "the kernels read and write (begin, end) pairs");
     if (!c || !ix || !lt || !out_len || (!line_ranges && n_ranges) || (!d_in && in_len) || (!d_out && out_cap))
         return GZPX_ERR_INVALID_ARG;
@@ -2742,23 +2790,32 @@ int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dline
     c->lines.stages = 0;
     c->lines.last_members = 0;
     if (n_ranges == 0) {
-        if (out_offsets) out_offsets[0] = 0;
+        if (out_offsets && !on_device) out_offsets[0] = 0;
+        if (out_offsets && on_device) {
+            if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+            HIP_TRY(hipMemset(out_offsets, 0, 8));
+        }
         return GZPX_OK;
     }
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
     const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
     uint64_t total = 0;
     GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, (const uint64_t *)line_ranges, n_ranges, 2u, bad_range, info,
-                          (hipStream_t)hip_stream, &total));
-    if (byte_ranges) memcpy(byte_ranges, c->lines.h_bpos, n_ranges * 16);
+                          (hipStream_t)hip_stream, &total, on_device));
+    hipStream_t stream = c->stream;
+    Drain drain{{stream}, 1, on_device && byte_ranges};  // (armed while a copy to the caller's device arrays may run)
+    if (byte_ranges && !on_device) memcpy(byte_ranges, c->lines.h_bpos, n_ranges * 16);
+    if (byte_ranges && on_device)
+        HIP_TRY(hipMemcpyAsync(byte_ranges, c->lines.ln.bpos, n_ranges * 16, hipMemcpyDeviceToDevice, stream));
     if (total > out_cap) {
         *out_len = (size_t)total;
         return GZPX_ERR_INSUFFICIENT_SPACE;
     }
     if (total >> 44) return GZPX_ERR_INVALID_ARG;  // (the gather's grid)
-    if (out_offsets) memcpy(out_offsets, c->ranges.h_out_off, (n_ranges + 1) * 8);
-    hipStream_t stream = c->stream;
-    Drain drain{{stream}, 1};
+    drain.armed = true;
+    if (out_offsets && !on_device) memcpy(out_offsets, c->ranges.h_out_off, (n_ranges + 1) * 8);
+    if (out_offsets && on_device)
+        HIP_TRY(hipMemcpyAsync(out_offsets, c->ranges.rr.out_off, (n_ranges + 1) * 8, hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipEventRecord(c->lines.ev[5], stream));
     launch_ranges_gather(c->stage.d, (uint32_t)n_ranges, c->ranges.rr, (uint8_t *)d_out, total, stream);
     HIP_TRY(hipGetLastError());
@@ -2767,6 +2824,111 @@ int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dline
     drain.armed = false;
     c->lines.stages = 4;
     *out_len = (size_t)total;
+    return GZPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gzpx_read_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                           const gzpx_range *line_ranges, size_t n_ranges, void *d_out, size_t out_cap, size_t *out_len,
+                           uint64_t *out_offsets, gzpx_range *byte_ranges, size_t *bad_range, gzpx_check_info *info,
+                           void *hip_stream) {
+    return read_lines(c, ix, lt, d_in, in_len, line_ranges, false, n_ranges, d_out, out_cap, out_len, out_offsets, byte_ranges,
+                      bad_range, info, hip_stream);
+}
+
+int gzpx_read_lines_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                                 const gzpx_range *d_line_ranges, size_t n_ranges, void *d_out, size_t out_cap, size_t *out_len,
+                                 uint64_t *d_out_offsets, gzpx_range *d_byte_ranges, size_t *bad_range, gzpx_check_info *info,
+                                 void *hip_stream) {
+    return read_lines(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, d_out, out_cap, out_len, d_out_offsets,
+                      d_byte_ranges, bad_range, info, hip_stream);
+}
+
+int gzpx_select_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                             const void *pattern, size_t pattern_len, uint64_t group, unsigned flags, gzpx_range *d_runs,
+                             size_t runs_cap, uint64_t *n_runs, uint64_t *n_records, uint64_t *n_hits, gzpx_check_info *info,
+                             void *hip_stream) {
+    if (!c || !ix || !lt || !n_runs || !n_records || !pattern || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_runs = *n_records = 0;
+    if (n_hits) *n_hits = 0;
+    if (group == 0 || (flags & ~GZPX_SELECT_INVERT) || pattern_len == 0 || pattern_len > kFdMaxPattern) return GZPX_ERR_INVALID_ARG;
+    if (!lines_match(c, ix, lt, in_len)) return GZPX_ERR_INVALID_ARG;
+    const uint64_t L = lt->n_lines, total = ix->inflated_len;
+    const uint64_t R = L / group + (L % group ? 1u : 0u);
+    if (R > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    const uint32_t m = (uint32_t)pattern_len;
+    const int invert = (flags & GZPX_SELECT_INVERT) ? 1 : 0;
+    const uint64_t cap = d_runs ? runs_cap : 0;
+    std::unique_lock<std::mutex> lk(c->mu);
+    SelectState &s = c->select;
+    FindState &f = c->find;
+    s.ms[0] = s.ms[1] = s.ms[2] = 0.0f;
+    if (L == 0) return GZPX_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    hipStream_t stream = c->stream;
+    if (m > total) {  // no position can hold the pattern: nothing is inflated, and every record is one run under INVERT
+        if (!invert) return GZPX_OK;
+        *n_runs = 1;
+        *n_records = R;
+        if (!d_runs) return GZPX_OK;
+        if (!cap) return GZPX_ERR_INSUFFICIENT_SPACE;
+        GZPX_TRY(s.reserve(1));
+        GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+        Drain drain{{stream}, 1};
+        s.h_run[0] = 0;
+        s.h_run[1] = L;
+        HIP_TRY(hipMemcpyAsync(d_runs, s.h_run, 16, hipMemcpyHostToDevice, stream));
+        return GZPX_OK;  // (the drain synchronises)
+    }
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    Drain drain{{stream}, 1};
+    Batches b;
+    GZPX_TRY(batches_of(c, ix, b));
+    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
+    GZPX_TRY(s.reserve(R));
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    memset(f.h_pat, 0, kFdMaxPattern);
+    memcpy(f.h_pat, pattern, m);
+    HIP_TRY(hipMemcpyAsync(f.fd.pat, f.h_pat, kFdMaxPattern, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(f.fd.rec, 0, kFdRecWords * 8, stream));
+    HIP_TRY(hipMemsetAsync(s.sl.bitmap, 0, (size_t)((R + 31) / 32 * 4), stream));
+    GZPX_TRY(batched_pass(
+        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, s.ev, 2, s.ms, info, drain,
+        [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
+            const FindBatch fb{c->stage.d, base, bytes, (uint32_t)(base < m - 1u ? base : m - 1u), m, (int)lt->delim};
+            HIP_TRY(hipEventRecord(s.ev[1], stream));
+            if (bytes) {
+                launch_find_count(fb, f.fd, stream);
+                launch_select_mark(fb, f.fd, s.sl, group, R, stream);
+            }
+            const uint64_t seen = base + bytes;
+            const uint32_t carry = (uint32_t)(seen < m - 1u ? seen : m - 1u);  // (a batch shorter than that appends to the carry)
+            if (bytes && carry && !is_last) launch_find_carry(fb, f.fd, carry, stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(s.ev[2], stream));
+            return GZPX_OK;
+        }));
+    HIP_TRY(hipEventRecord(s.ev[3], stream));
+    launch_select_runs(s.sl, f.fd, R, group, L, invert, (uint64_t *)d_runs, cap, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s.ev[4], stream));
+    HIP_TRY(hipMemcpyAsync(s.h_rec, s.sl.rec, kSlRecWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    if (hipEventElapsedTime(&s.ms[2], s.ev[3], s.ev[4]) != hipSuccess) s.ms[2] = 0.0f;
+    *n_runs = s.h_rec[kSlRecRuns];
+    *n_records = s.h_rec[kSlRecRecords];
+    if (n_hits) *n_hits = s.h_rec[kSlRecHits];
+    return d_runs && *n_runs > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
+}
+
+int gzpx_dctx_last_select_ms(gzpx_dctx *ctx, float ms[3]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    for (int j = 0; j < 3; j++) ms[j] = ctx->select.ms[j];
     return GZPX_OK;
 }
 

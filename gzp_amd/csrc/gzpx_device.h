@@ -362,6 +362,28 @@ void launch_find_write(const FindBatch &b, const FindScratch &f, uint64_t *d_pos
 // behind both: the last `n` <= m - 1 bytes of the region become the next batch's carry
 void launch_find_carry(const FindBatch &b, const FindScratch &f, uint32_t n, hipStream_t stream);
 
+// Selection of lines by content (gzpx_select.h).  The record bitmap holds one bit per record of `group` lines; behind
+// the last batch its runs of set (INVERT: clear) bits are counted kSlRunRecords records a workgroup, the counts scanned
+// kSlScanStep workgroups a step, and the runs written as line ranges.
+constexpr uint32_t kSlRunRecords = 512;  // records per workgroup of k_sl_runs_count / k_sl_runs_write
+constexpr uint32_t kSlScanStep = 256;    // workgroups of them per step of k_sl_runs_scan
+// the record (u64 words): runs, selected records, hits
+enum { kSlRecRuns = 0, kSlRecRecords = 1, kSlRecHits = 2, kSlRecWords = 4 };
+struct SelectScratch {
+    uint32_t *bitmap = nullptr;  // [(records + 31) / 32] bit r: a hit's line lies in record r
+    uint32_t *cnt = nullptr;     // [2 * groups] (rising edges, set bits) of every kSlRunRecords records
+    uint32_t *bases = nullptr;   // [groups] the rank of a group's first rising edge
+    uint64_t *rec = nullptr;     // [kSlRecWords]
+};
+inline uint64_t select_groups(uint64_t n_records) { return (n_records + kSlRunRecords - 1u) / kSlRunRecords; }
+// behind launch_find_count of a batch with a delimiter: the records of the batch's hits into s.bitmap
+void launch_select_mark(const FindBatch &b, const FindScratch &f, const SelectScratch &s, uint64_t group, uint64_t n_records,
+                        hipStream_t stream);
+// behind the last batch (n_records > 0): s.rec, and the runs below rank `cap` into d_runs (null: counts only) as
+// (begin, end) pairs of line numbers
+void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n_records, uint64_t group, uint64_t n_lines,
+                        int invert, uint64_t *d_runs, uint64_t cap, hipStream_t stream);
+
 // gzpx_wrap.h (k_adler32_tiles): (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);
 

@@ -5670,6 +5670,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_ranges.h"
 #include "gzpx_lines.h"
 #include "gzpx_find.h"
+#include "gzpx_select.h"
 #include "gzpx_wrap.h"
 #include "gzpx_cksum.h"
 
@@ -6204,6 +6205,27 @@ void launch_find_write(const FindBatch &b, const FindScratch &f, uint64_t *d_pos
 void launch_find_carry(const FindBatch &b, const FindScratch &f, uint32_t n, hipStream_t stream) {
     hipLaunchKernelGGL(k_fd_carry, dim3(1), dim3(kFdThreads), 0, stream, b.stage, kFdPad + b.len - n, n,
                        b.delim >= 0 ? 1u : 0u, b.delim >= 0 ? (uint32_t)b.delim : 0u, f.rec);
+}
+
+// The selection (gzpx_select.h): the marking pass behind the count and the scan of a batch, the runs behind the last.
+void launch_select_mark(const FindBatch &b, const FindScratch &f, const SelectScratch &s, uint64_t group, uint64_t n_records,
+                        hipStream_t stream) {
+    uint32_t x0, grid;
+    const FdArgs a = find_args(b, x0, grid);
+    hipLaunchKernelGGL(k_sl_mark, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat,
+                       (const uint32_t *)f.cnt, (const uint64_t *)f.bases, s.bitmap, group, n_records);
+}
+
+void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n_records, uint64_t group, uint64_t n_lines,
+                        int invert, uint64_t *d_runs, uint64_t cap, hipStream_t stream) {
+    const uint32_t groups = (uint32_t)select_groups(n_records), inv = invert ? 1u : 0u;
+    const uint8_t *bits = (const uint8_t *)s.bitmap;
+    hipLaunchKernelGGL(k_sl_runs_count, dim3(groups), dim3(kSlRunThreads), 0, stream, bits, n_records, inv, s.cnt);
+    hipLaunchKernelGGL(k_sl_runs_scan, dim3(1), dim3(kFdThreads), 0, stream, (const uint32_t *)s.cnt, groups, s.bases,
+                       (const uint64_t *)f.rec, s.rec);
+    if (d_runs && cap)
+        hipLaunchKernelGGL(k_sl_runs_write, dim3(groups), dim3(kSlRunThreads), 0, stream, bits, n_records, inv,
+                           (const uint32_t *)s.cnt, (const uint32_t *)s.bases, group, n_lines, d_runs, cap);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

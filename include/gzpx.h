@@ -470,6 +470,53 @@ int gzpx_find_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const void *d_in, si
                      size_t pattern_len, int delim, uint64_t *d_positions, uint64_t *d_lines, size_t hits_cap, uint64_t *n_hits,
                      gzpx_check_info *info, void *hip_stream);
 int gzpx_dctx_last_find_ms(gzpx_dctx *ctx, float ms[3]);
+/* ---- selection of lines by content (gzpx_select.h): grep, grep -v and record-wise grep on a device-resident BGZF /
+ * Mgzip stream -- the FASTQ records whose name starts with a prefix, the VCF rows of one contig, every line that does
+ * not hold a string -- as a table of LINE RANGES that stays in device memory, and a form of the read by line that takes
+ * such a table where it lies.  Only fixed-size records cross to the host.
+ * Definitions.  `plain`, n, the pattern, m and HIT are exactly as for gzpx_find_device.  `delim`, D, L, start(k) and
+ *   "line" are exactly as for the reads by line, taken from the gzpx_dlines table that is passed in: the selection has
+ *   no delimiter argument of its own.
+ *   The LINE of a hit is the line of its first byte (gzpx_find_device's rule).  A pattern may hold the delimiter:
+ *   "\nchr7\t" selects the line that the "\n" ends, as the search reports it.
+ *   `group` = g >= 1 lines form a RECORD: record r is the lines [g r, min(g (r + 1), L)); R = ceil(L / g); the last
+ *   record may be short.  A record is HIT when the line of at least one hit lies in it.  The selected set S is the hit
+ *   records; with GZPX_SELECT_INVERT it is the records of [0, R) that are not hit.
+ *   A RUN is a maximal interval [r0, r1) of consecutive selected records.  Runs are reported in ascending order as LINE
+ *   ranges {g r0, min(g r1, L)} in gzpx_range.  There are at most ceil(R / 2) runs, so a table can always be sized in
+ *   advance.
+ * gzpx_select_lines_device.  Context, lock, slot, hip_stream, "returns synchronised", the batches
+ *   (gzpx_dctx_set_lines_batch) and the report of a failing member (the inflate's error, info->block = its index in the
+ *   stream) are as for gzpx_find_device; on a failing member *n_runs = *n_records = 0.  Every member is inflated once
+ *   per call, whatever runs_cap is.  The pattern is a HOST array; d_runs is a DEVICE array of runs_cap entries.
+ *   *n_runs and *n_records (the selected records) are always the totals; *n_hits (optional) is what gzpx_find_device
+ *   reports.  d_runs == NULL: count only, runs_cap is ignored.  Otherwise, when there are more than runs_cap runs, the
+ *   first runs_cap are written, nothing behind runs_cap entries is touched and the call returns
+ *   GZPX_ERR_INSUFFICIENT_SPACE.
+ *   GZPX_ERR_INVALID_ARG: group == 0; a flag bit other than GZPX_SELECT_INVERT; pattern_len 0 or above
+ *   GZPX_FIND_MAX_PATTERN; a lines table that does not belong to the index and context (gzpx_read_lines_device's
+ *   check); R > 0xFFFFFFF0.
+ *   L == 0: GZPX_OK, 0 runs, nothing inflated.  m > n: no hit can exist and nothing is inflated; without INVERT that is
+ *   0 runs, with INVERT the one run {0, L}.
+ *   gzpx_dctx_last_select_ms: HIP-event durations of the last call: [0] inflate and [1] counting pass + scan + marking
+ *   pass, summed over its batches, [2] the runs.
+ * gzpx_read_lines_table_device is gzpx_read_lines_device with its tables in device memory: validation and *bad_range,
+ *   the covers and the members read, GZPX_ERR_INSUFFICIENT_SPACE with *out_len = the bytes needed and d_out untouched,
+ *   empty ranges reported as {0, 0}, gzpx_dctx_last_lines_members and gzpx_dctx_last_lines_ms are the same, word for
+ *   word.  d_line_ranges (n_ranges entries) is read where it lies, ordered behind hip_stream like d_in;
+ *   d_out_offsets (n_ranges + 1) and d_byte_ranges (n_ranges), both optional, are written in device memory, by the
+ *   time the call returns, under the conditions under which gzpx_read_lines_device writes its host arrays.  No table
+ *   sized by n_ranges crosses to the host in either direction: two 32-byte records do. */
+#define GZPX_SELECT_INVERT 1u
+int gzpx_select_lines_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in, size_t in_len,
+                             const void *pattern, size_t pattern_len, uint64_t group, unsigned flags, gzpx_range *d_runs,
+                             size_t runs_cap, uint64_t *n_runs, uint64_t *n_records, uint64_t *n_hits, gzpx_check_info *info,
+                             void *hip_stream);
+int gzpx_dctx_last_select_ms(gzpx_dctx *ctx, float ms[3]);
+int gzpx_read_lines_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in,
+                                 size_t in_len, const gzpx_range *d_line_ranges, size_t n_ranges, void *d_out, size_t out_cap,
+                                 size_t *out_len, uint64_t *d_out_offsets, gzpx_range *d_byte_ranges, size_t *bad_range,
+                                 gzpx_check_info *info, void *hip_stream);
 /* ---- batches of independent DEFLATE members that this library did not write (gzpx_wrap.h): GZIP pages of Parquet,
  * zlib chunks of HDF5 / Zarr / ORC, PNG IDAT streams, members of a multi-member gzip file whose extents are known.
  * The counterpart of libdeflate_deflate_decompress / libdeflate_zlib_decompress / libdeflate_gzip_decompress for a

@@ -145,8 +145,10 @@ def skewed(ratio, nsym, n, seed):
 
 def long_codes(oracle):
     """Geometric symbol frequencies (ratio 1.5, 30 symbols): 14-bit litlen codes and 10-bit offset codes in the oracle's
-    level-1 stream.  (Ratios 1.3-1.55 with 30-44 symbols, seeds 1-3: none reached 15 bits -- the matches take the
-    frequent symbols' counts away and the tree stays at 14.)"""
+    level-1 stream.  14 bits is the literal/length code's limit, and this input reaches it without the limit: built
+    without one, its tree is exactly 14 deep, so make_code never takes its clamp here.  (Ratios 1.3-1.55 with 30-44
+    symbols, seeds 1-3: none went deeper -- the matches take the frequent symbols' counts away.)  The inputs whose trees
+    are deeper than the limits are in tests/huffman_limit_cases.py."""
     a = skewed(1.5, 30, BLOCK, 3)
     blocks, toks = walk_first_member(oracle, a)
     assert max(max(ll) for _, _, _, ll, _ in blocks if ll) >= 14

@@ -82,6 +82,14 @@ def test_huffman_code_is_prefix_free_and_length_limited(oracle):
             assert np.sum(2.0 ** -used) == pytest.approx(1.0)  # complete code
 
 
+def test_length_limited_codes_match_libdeflate_vectors(oracle):
+    """The oracle's length-limit rule (the clamp on the length counts and the hand-out behind it) against the v1.10
+    binary, on inputs whose literal/length, offset and precode trees are deeper than 14, 15 and 7 without it
+    (tests/huffman_limit_cases.py, tests/golden/huffman_limit_vectors.json)."""
+    import huffman_limit_cases
+    huffman_limit_cases.check_oracle_vectors(oracle)
+
+
 def test_levels_2_to_4_match_libdeflate_vectors(oracle, golden_hc):
     for e in golden_hc["raw_deflate"]:
         a = synth.make(e["class"], e["n"], e["seed"])

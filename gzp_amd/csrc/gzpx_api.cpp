@@ -30,41 +30,13 @@ constexpr size_t kDictSize = 32768;  // DICT_SIZE, src/lib.rs:108
 constexpr uint32_t kMaxBatchBlocks = 16384;
 constexpr size_t kMaxScratchBytes = (size_t)24 << 30;  // per-context cap of the per-block scratch
 
-// ---- GF(2) polynomial helpers for CRC-32 combination (reflected representation) ----
-uint32_t multmodp(uint32_t a, uint32_t b) {
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return p;
-}
+// ---- CRC-32 combination over the host half of gzpx_crc.h: sq[k] = x^(8 * 2^k) mod P
+#include "gzpx_crc.h"
+const CrcPow kCrc32Pow = crc_pow_table<kCrcPoly32>();
 
-// x^(2^k) mod P
-uint32_t x2k(unsigned k) {
-    uint32_t p = 1u << 30;  // x^1
-    for (unsigned i = 0; i < k; i++) p = multmodp(p, p);
-    return p;
-}
-
-// x^(8 * len) mod P
-uint32_t x8n(uint64_t len) {
-    uint32_t r = 1u << 31;  // x^0
-    unsigned k = 3;
-    while (len) {
-        if (len & 1) r = multmodp(x2k(k), r);
-        len >>= 1;
-        k++;
-    }
-    return r;
-}
-
+// crc(A || B) = crc(A) * x^(8 |B|) mod P  xor  crc(B)
 uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
-    return multmodp(x8n(len2), crc1) ^ crc2;
+    return crc_mulmod<kCrcPoly32>(crc_xpow8<kCrcPoly32>(kCrc32Pow.sq, len2), crc1) ^ crc2;
 }
 
 constexpr size_t kTrailerBytes = 8;  // CRC-32 + ISIZE behind a member's payload
@@ -73,9 +45,8 @@ constexpr size_t kEofMarkerBytes = header_bytes(GZPX_FORMAT_BGZF) + 2 + kTrailer
 
 CrcConsts crc_consts() {
     CrcConsts cc;
-    for (unsigned l = 0; l < 10; l++) cc.pow64[l] = x2k(9 + l);
-    cc.pow_tile = x2k(19);   // x^(8 * 65536) = x^(2^19)
-    cc.pow_small = x2k(17);  // x^(8 * 16384)
+    for (unsigned l = 0; l < 10; l++) cc.pow64[l] = kCrc32Pow.sq[6 + l];  // x^(8 * 64 * 2^l)
+    cc.pow_tile = kCrc32Pow.sq[16];                                       // x^(8 * 65536)
     return cc;
 }
 
@@ -1295,7 +1266,7 @@ uint32_t gzpx_crc32(uint32_t crc, const void *buf, size_t n) {
 
 int gzpx_last_status(void) { return t_last_status; }
 
-// ---- Crc32::combine, Adler32::update / combine (src/check.rs:85-164): see gzpx_check.hip
+// ---- Crc32::combine, Adler32::update / combine (src/check.rs:85-164): the device side of Adler32::update is in gzpx_wrap.h
 uint32_t gzpx_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) { return crc32_combine(crc1, crc2, len2); }
 
 uint32_t gzpx_adler32_combine(uint32_t adler1, uint32_t adler2, uint64_t len2) {

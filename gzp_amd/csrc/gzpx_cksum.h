@@ -1,6 +1,6 @@
 // gzpx_cksum.h -- checksums of a table of device-resident buffers (gzpx_checksum_batch_device): CRC-32, CRC-32C and
 // Adler-32 of n entries of one input, tables in, sums out.  Included from gzpx_kernels.hip, namespace gzpx, behind
-// gzpx_wrap.h (adler_workgroup, the status values of a report) and the dword4 loads of the match kernels.
+// gzpx_wrap.h (adler_workgroup, the status values of a report) and gzpx_crc.h (the CRC arithmetic).
 //
 // The work is cut into 64 KiB tiles counted from every entry's first byte, and the tiles of all entries form one flat
 // index space, so that a table of one 2 GiB entry and a table of 30,000 small ones load the device alike:
@@ -31,46 +31,12 @@
 #pragma once
 
 constexpr uint32_t kCkCrc32 = 0, kCkAdler32 = 1, kCkCrc32c = 2;  // GZPX_CHECK_*
-constexpr uint32_t kCkPolyCrc32 = 0xEDB88320u, kCkPolyCrc32c = 0x82F63B78u;  // reflected
 constexpr uint32_t kCkTile = 65536u;    // bytes per tile
 constexpr uint32_t kCkThreads = 256u;   // a lane owns one 256-byte segment of a tile
 constexpr uint32_t kCkSeg = kCkTile / kCkThreads;
 constexpr uint32_t kCkWgPerCu = 6u;     // the persistent launch: workgroups per compute unit (77 VGPRs: six waves a SIMD)
 constexpr uint32_t kCkPlanThreads = 1024u;
 static_assert(kCkThreads == kAdlerThreads, "k_cksum_tiles calls adler_workgroup");
-
-// a * b mod P, both in the reflected representation of the CRC register (bit 31 is x^0)
-template <uint32_t P>
-__host__ __device__ __forceinline__ uint32_t ck_mulmod(uint32_t a, uint32_t b) {
-    uint32_t m = 1u << 31, p = 0;
-    for (int i = 0; i < 32; i++) {
-        if (a & m) p ^= b;
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ P : b >> 1;
-    }
-    return p;
-}
-
-// sq[k] = x^(8 * 2^k) mod P: what x^(8 m) is a product of, for any 64-bit m.  Made once per polynomial on the host
-// (ck_pow_table) and handed to the kernels by value; they keep it in LDS.
-struct CkPow {
-    uint32_t sq[64];
-};
-template <uint32_t P>
-inline CkPow ck_pow_table() {
-    CkPow t;
-    t.sq[0] = 0x00800000u;  // x^8
-    for (int k = 1; k < 64; k++) t.sq[k] = ck_mulmod<P>(t.sq[k - 1], t.sq[k - 1]);
-    return t;
-}
-// x^(8 m) mod P
-template <uint32_t P>
-__device__ __forceinline__ uint32_t ck_xpow8(const uint32_t *sq, uint64_t m) {
-    uint32_t r = 0x80000000u;  // 1
-    for (uint32_t k = 0; m; k++, m >>= 1)
-        if (m & 1u) r = ck_mulmod<P>(r, sq[k]);
-    return r;
-}
 
 // ------------------------------------------------------------------------------------------
 // the table
@@ -174,11 +140,9 @@ __global__ __launch_bounds__(kCkPlanThreads) void k_cksum_plan(CkTable t, uint64
 
 // ------------------------------------------------------------------------------------------
 // One tile of a CRC.  crc32_direct's shape: lane t owns the 256-byte segment that ENDS 256 (255 - t) bytes in front of
-// the tile's end, so only the first used segment is short; a whole segment is sixteen 16-byte loads of dword-aligned
-// addresses, 128 bytes in flight per step (narrower steps fetch the lines again: see crc32_direct), the byte
-// alignment taken out with v_alignbyte, slice-by-4 out of LDS.  The registers are plain remainders -- no inversion in
-// here -- and the lane whose segment starts the tile starts from `init`.  Returns the register behind the tile's
-// last byte, in every lane.
+// the tile's end, so only the first used segment is short; a whole segment is crc_seg256, a short one crc_bytes
+// (gzpx_crc.h).  The registers are plain remainders -- no inversion in here -- and the lane whose segment starts the
+// tile starts from `init`.  Returns the register behind the tile's last byte, in every lane.
 // Reads: the dwords that hold bytes of p[0, len), and nothing else; `at_end` (the tile ends its entry) keeps the last
 // segment's look-ahead load in front of the tile's end where the end is dword-aligned.
 // ------------------------------------------------------------------------------------------
@@ -190,33 +154,11 @@ struct CkCrcLds {
 };
 
 template <uint32_t P>
-__device__ __forceinline__ void ck_crc_setup(CkCrcLds &l, const CkPow &pw, uint32_t tid) {
-    {
-        uint32_t c = tid;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (P & (0u - (c & 1u)));
-        l.table[0][tid] = c;
-    }
+__device__ __forceinline__ void ck_crc_setup(CkCrcLds &l, const CrcPow &pw, uint32_t tid) {
     if (tid < 64) l.sq[tid] = pw.sq[tid];
+    crc_tables_fill<P>(l.table, tid, kCkThreads);  // (its barrier is the one behind sq[] too)
+    l.segpow[tid] = crc_xpow8<P>(l.sq, (uint64_t)kCkSeg * (kCkThreads - 1u - tid));
     __syncthreads();
-    {
-        const uint32_t t0 = l.table[0][tid];
-        const uint32_t t1 = (t0 >> 8) ^ l.table[0][t0 & 0xFFu];
-        const uint32_t t2 = (t1 >> 8) ^ l.table[0][t1 & 0xFFu];
-        const uint32_t t3 = (t2 >> 8) ^ l.table[0][t2 & 0xFFu];
-        l.table[1][tid] = t1;
-        l.table[2][tid] = t2;
-        l.table[3][tid] = t3;
-    }
-    l.segpow[tid] = ck_xpow8<P>(l.sq, (uint64_t)kCkSeg * (kCkThreads - 1u - tid));
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t ck_crc_byte(const CkCrcLds &l, uint32_t c, uint32_t byte) {
-    return (c >> 8) ^ l.table[0][(c ^ byte) & 0xFFu];
-}
-__device__ __forceinline__ uint32_t ck_crc_word(const CkCrcLds &l, uint32_t c, uint32_t w) {
-    c ^= w;
-    return l.table[3][c & 0xFFu] ^ l.table[2][(c >> 8) & 0xFFu] ^ l.table[1][(c >> 16) & 0xFFu] ^ l.table[0][c >> 24];
 }
 
 template <uint32_t P>
@@ -229,40 +171,9 @@ __device__ __forceinline__ uint32_t ck_crc_tile(CkCrcLds &l, const uint8_t *__re
         const uint32_t n = (uint32_t)seg_end_i - sb;
         const uint8_t *s = p + sb;
         if (sb == 0) c = init;
-        if (n == kCkSeg) {
-            const uint32_t mis = (uint32_t)((uintptr_t)s & 3u);
-            const uint32_t *q = (const uint32_t *)(s - mis);
-            const bool last_short = at_end && (uint32_t)seg_end_i == len && mis == 0;  // q[64] is not the tile's
-            uint32_t carry = q[0];
-            for (uint32_t g = 0; g < 2; g++) {
-                dword4 v[8];
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++) {
-                    if (g == 1 && k == 7 && last_short) {
-                        v[k].x = q[61];
-                        v[k].y = q[62];
-                        v[k].z = q[63];
-                        v[k].w = 0;
-                    } else {
-                        v[k] = *(const dword4 *)(q + 1 + 32 * g + 4 * k);
-                    }
-                }
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++) {
-                    c = ck_crc_word(l, c, __builtin_amdgcn_alignbyte(v[k].x, carry, mis));
-                    c = ck_crc_word(l, c, __builtin_amdgcn_alignbyte(v[k].y, v[k].x, mis));
-                    c = ck_crc_word(l, c, __builtin_amdgcn_alignbyte(v[k].z, v[k].y, mis));
-                    c = ck_crc_word(l, c, __builtin_amdgcn_alignbyte(v[k].w, v[k].z, mis));
-                    carry = v[k].w;
-                }
-            }
-        } else {  // the short first segment of the tile: bytes up to a dword boundary, whole dwords, bytes
-            uint32_t i = 0;
-            for (; i < n && ((uintptr_t)(s + i) & 3u); i++) c = ck_crc_byte(l, c, s[i]);
-            for (; i + 4 <= n; i += 4) c = ck_crc_word(l, c, *(const uint32_t *)(s + i));
-            for (; i < n; i++) c = ck_crc_byte(l, c, s[i]);
-        }
-        c = ck_mulmod<P>(c, l.segpow[tid]);
+        if (n == kCkSeg) c = crc_seg256(l.table, s, at_end && (uint32_t)seg_end_i == len, c);
+        else c = crc_bytes(l.table, s, n, c);  // the short first segment of the tile
+        c = crc_mulmod<P>(c, l.segpow[tid]);
     }
     for (int m = 32; m >= 1; m >>= 1) c ^= __shfl_xor(c, m);
     // (red[] alternates from tile to tile: a wave that is a tile ahead writes the other half, and it cannot be two
@@ -278,9 +189,9 @@ __device__ __forceinline__ uint32_t ck_crc_tile(CkCrcLds &l, const uint8_t *__re
 template <uint32_t KIND>
 __global__ __launch_bounds__(kCkThreads) void k_cksum_tiles(CkTable t, const uint32_t *__restrict__ seeds,
                                                            const uint64_t *__restrict__ prefix, uint32_t *__restrict__ part,
-                                                           uint32_t *__restrict__ carry, CkPow pw) {
+                                                           uint32_t *__restrict__ carry, CrcPow pw) {
     constexpr bool kAdler = KIND == kCkAdler32;
-    constexpr uint32_t P = KIND == kCkCrc32c ? kCkPolyCrc32c : kCkPolyCrc32;
+    constexpr uint32_t P = KIND == kCkCrc32c ? kCrcPoly32c : kCrcPoly32;
     __shared__ typename std::conditional<kAdler, AdlerLds, CkCrcLds>::type l;
     const uint32_t tid = threadIdx.x;
     const uint64_t total = prefix[t.n], g = gridDim.x, w = blockIdx.x;
@@ -316,7 +227,7 @@ __global__ __launch_bounds__(kCkThreads) void k_cksum_tiles(CkTable t, const uin
         if (done < len) {  // the run ends inside the entry: the value moves to the entry's end
             const uint64_t behind = len - done;
             if constexpr (kAdler) b = (uint32_t)((b + (behind % kAdlerBase) * a) % kAdlerBase);
-            else a = ck_mulmod<P>(a, ck_xpow8<P>(l.sq, behind));
+            else a = crc_mulmod<P>(a, crc_xpow8<P>(l.sq, behind));
         }
         if (tid == 0) {
             const uint32_t v = kAdler ? (a | (b << 16)) : a;

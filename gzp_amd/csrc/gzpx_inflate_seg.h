@@ -1126,23 +1126,13 @@ __global__ __launch_bounds__(kLcThreads, GZPX_LC_WAVES) void k_lzcopy(DBlock *__
         l.gave_up = 0;
         l.crc_total = 0;
     }
-    {  // CRC tables (one entry of each per thread) and the thread's shift: the product of the x^(512 * 2^k) of its bits
-        uint32_t c = tid;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-        l.crc_tab[0][tid] = c;
+    {  // the thread's shift: the product of the x^(512 * 2^k) of its bits; and the CRC tables (one entry of each per thread)
         uint32_t pw = 0x80000000u;  // x^0
         const uint32_t q = kLcThreads - 1u - tid;
         for (uint32_t k = 0; k < 8; k++)
-            if ((q >> k) & 1u) pw = gf2_multmodp(cc.pow64[k], pw);
+            if ((q >> k) & 1u) pw = crc_mulmod<kCrcPoly32>(cc.pow64[k], pw);
         l.crc_pw[tid] = pw;
-        __syncthreads();
-        const uint32_t t0 = l.crc_tab[0][tid];
-        const uint32_t t1 = (t0 >> 8) ^ l.crc_tab[0][t0 & 0xFFu];
-        const uint32_t t2 = (t1 >> 8) ^ l.crc_tab[0][t1 & 0xFFu];
-        const uint32_t t3 = (t2 >> 8) ^ l.crc_tab[0][t2 & 0xFFu];
-        l.crc_tab[1][tid] = t1;
-        l.crc_tab[2][tid] = t2;
-        l.crc_tab[3][tid] = t3;
+        crc_tables_fill<kCrcPoly32>(l.crc_tab, tid, kLcThreads);
     }
     uint32_t spins = 0;
     bool give_up = false;
@@ -1370,20 +1360,10 @@ __global__ __launch_bounds__(kLcThreads, GZPX_LC_WAVES) void k_lzcopy(DBlock *__
                 uint32_t pos = a0 + (e_i > 64 ? (uint32_t)(e_i - 64) : 0u);
                 const uint32_t end = a0 + (uint32_t)e_i;
                 uint32_t c = 0xFFFFFFFFu;
-                while (pos < end && (pos & 3u)) {
-                    c = (c >> 8) ^ l.crc_tab[0][(c ^ tile8[pos]) & 0xFFu];
-                    pos++;
-                }
-                while (pos + 4 <= end) {
-                    c ^= l.tile[pos >> 2];
-                    c = l.crc_tab[3][c & 0xFFu] ^ l.crc_tab[2][(c >> 8) & 0xFFu] ^ l.crc_tab[1][(c >> 16) & 0xFFu] ^ l.crc_tab[0][c >> 24];
-                    pos += 4;
-                }
-                while (pos < end) {
-                    c = (c >> 8) ^ l.crc_tab[0][(c ^ tile8[pos]) & 0xFFu];
-                    pos++;
-                }
-                piece = gf2_multmodp(l.crc_pw[tid], ~c);
+                for (; pos < end && (pos & 3u); pos++) c = crc_byte(l.crc_tab, c, tile8[pos]);
+                for (; pos + 4 <= end; pos += 4) c = crc_word(l.crc_tab, c, l.tile[pos >> 2]);
+                for (; pos < end; pos++) c = crc_byte(l.crc_tab, c, tile8[pos]);
+                piece = crc_mulmod<kCrcPoly32>(l.crc_pw[tid], ~c);
             }
             for (int m = 32; m >= 1; m >>= 1) piece ^= __shfl_xor(piece, m);
             if (lane == 0) l.crc_part[tid >> 6] = piece;
@@ -1394,8 +1374,8 @@ __global__ __launch_bounds__(kLcThreads, GZPX_LC_WAVES) void k_lzcopy(DBlock *__
                 uint32_t tot = l.crc_total;
                 if (t > 0) {  // crc(A || B) = crc(A) x^(8 |B|) + crc(B): 64-byte steps from the table, the rest byte by byte
                     const uint32_t q = tl >> 6;
-                    tot = gf2_multmodp(q >= kLcThreads ? cc.pow64[8] : l.crc_pw[kLcThreads - 1u - q], tot);
-                    for (uint32_t r = 0; r < (tl & 63u); r++) tot = (tot >> 8) ^ l.crc_tab[0][tot & 0xFFu];
+                    tot = crc_mulmod<kCrcPoly32>(q >= kLcThreads ? cc.pow64[8] : l.crc_pw[kLcThreads - 1u - q], tot);
+                    for (uint32_t r = 0; r < (tl & 63u); r++) tot = crc_byte(l.crc_tab, tot, 0);
                 }
                 l.crc_total = tot ^ tile_crc;
             }

@@ -4195,67 +4195,40 @@ __global__ __launch_bounds__(64, GZPX_HUFF_WAVES) void k_huffman(Config cfg, Blo
 }
 
 // ------------------------------------------------------------------------------------------
-// k_crc32: gzip CRC-32 of every block.  The block is staged in LDS with coalesced dword loads
-// (one HBM read of the input, no strided re-fetching).  1024 threads: thread t owns the 64-byte
-// segment that ENDS at n - 64*(1023 - t) (so only the first used segment is short), runs
-// slice-by-4 over it out of LDS (16 dependent steps; segments are laid out 17 dwords apart), and
-// the 1024 CRCs are merged by a log-tree of zlib-style crc32_combine steps:
+// CRC-32 of a buffer by one workgroup, two ways (the arithmetic both are made of: gzpx_crc.h).
+// crc32_workgroup (k_dcrc32): the buffer is staged in LDS with coalesced dword loads (one HBM read of
+// the input, no strided re-fetching).  1024 threads: thread t owns the 64-byte segment that ENDS at
+// n - 64*(1023 - t) (so only the first used segment is short), runs slice-by-4 over it out of LDS
+// (16 dependent steps; segments are laid out 17 dwords apart), and the 1024 CRCs are merged by a
+// log-tree of zlib-style crc32_combine steps:
 // crc(A||B) = crc(A) * x^(8|B|) mod P  xor  crc(B), with |B| = 64 * 2^level at every level.
-// Two workgroups (32 waves) share a CU.
+// crc32_direct (k_crc32): 256 threads, 256-byte segments read straight from global memory, the same tree.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t gf2_multmodp(uint32_t a, uint32_t bv) {
-    uint32_t m = 1u << 31, p = 0;
-    for (int i = 0; i < 32; i++) {
-        if (a & m) p ^= bv;
-        m >>= 1;
-        bv = (bv & 1u) ? (bv >> 1) ^ 0xEDB88320u : bv >> 1;
-    }
-    return p;
-}
+#define GZPX_CRC_KERNELS
+#include "gzpx_crc.h"
 
 constexpr uint32_t kCrcThreads = 1024;  // one 64-byte segment per thread and chunk (k_dcrc32)
-constexpr uint32_t kCrcSmall = 256;     // the compressor's k_crc32: 21 KiB of LDS (see k_crc32)
-constexpr uint32_t kCrcSeg = 64;        // bytes per thread and chunk
+constexpr uint32_t kCrcSmall = 256;     // the compressor's k_crc32: one 256-byte segment per thread and chunk
+constexpr uint32_t kCrcSeg = 64;        // bytes per thread and chunk of crc32_workgroup
 constexpr uint32_t kCrcSegWords = kCrcSeg / 4;  // 16
+constexpr uint32_t kCrcChunk = kCrcThreads * kCrcSeg;  // 64 KiB; crc32_direct's 256 * 256 is the same
 
 // dword index -> padded LDS index (one pad word after every 16: segments lie 17 dwords apart, so
 // the 64 lanes of a wave, each in its own segment, spread evenly over the banks)
 __device__ __forceinline__ uint32_t crc_pad(uint32_t w) { return w + (w / kCrcSegWords); }
 
-template <uint32_t T>
-struct CrcLdsT {
-    static constexpr uint32_t kChunk = T * kCrcSeg;  // bytes per chunk: 64 KiB (T = 1024) / 16 KiB (T = 256)
-    static constexpr uint32_t kDataWords = (kChunk / 4 + 2) + (kChunk / 4 + 2) / kCrcSegWords + 2;
+struct CrcWgLds {
     uint32_t table[4][256];
-    uint32_t data[kDataWords];
-    uint32_t part[T];
+    uint32_t data[(kCrcChunk / 4 + 2) + (kCrcChunk / 4 + 2) / kCrcSegWords + 2];
+    uint32_t part[kCrcThreads];
 };
-using CrcLds = CrcLdsT<kCrcThreads>;
 
-// CRC-32 of in[0..n) by a T-thread workgroup (T = 1024: log2 = 10 combine levels, chunk constant
-// cc.pow_tile; T = 256: 8 levels, cc.pow_small); the result is valid in every thread.
-template <uint32_t T>
-__device__ uint32_t crc32_workgroup(CrcLdsT<T> &l, const uint8_t *__restrict__ in, uint32_t n,
-                                    const CrcConsts &cc, uint32_t tid) {
-    constexpr uint32_t kChunk = CrcLdsT<T>::kChunk;
-    constexpr uint32_t kLevels = T == 1024 ? 10 : 8;
-    static_assert(T == 1024 || T == 256, "combine constants exist for these two");
-    const uint32_t pow_chunk = T == 1024 ? cc.pow_tile : cc.pow_small;
-    for (uint32_t i = tid; i < 256; i += T) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-        l.table[0][i] = c;
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < 256; i += T) {
-        const uint32_t t0 = l.table[0][i];
-        const uint32_t t1 = (t0 >> 8) ^ l.table[0][t0 & 0xFFu];
-        const uint32_t t2 = (t1 >> 8) ^ l.table[0][t1 & 0xFFu];
-        const uint32_t t3 = (t2 >> 8) ^ l.table[0][t2 & 0xFFu];
-        l.table[1][i] = t1;
-        l.table[2][i] = t2;
-        l.table[3][i] = t3;
-    }
+// CRC-32 of in[0..n) by a workgroup of kCrcThreads (ten combine levels, chunk constant cc.pow_tile); the
+// result is valid in every thread.
+__device__ uint32_t crc32_workgroup(CrcWgLds &l, const uint8_t *__restrict__ in, uint32_t n, const CrcConsts &cc,
+                                    uint32_t tid) {
+    constexpr uint32_t T = kCrcThreads, kChunk = kCrcChunk;
+    crc_tables_fill<kCrcPoly32>(l.table, tid, T);
     // Inputs above one chunk are cut into chunks aligned to the END of the input (only the first
     // chunk is short), so every chunk-to-chunk combine uses the same x^(8 * chunk) constant.
     uint32_t total = 0;
@@ -4279,40 +4252,29 @@ __device__ uint32_t crc32_workgroup(CrcLdsT<T> &l, const uint8_t *__restrict__ i
             const uint32_t seg_end = (uint32_t)seg_end_i + mis;
             uint32_t pos = (seg_end_i > (int32_t)kCrcSeg ? (uint32_t)(seg_end_i - (int32_t)kCrcSeg) : 0u) + mis;
             uint32_t c = 0xFFFFFFFFu;
-            while (pos < seg_end && (pos & 3u)) {  // head bytes up to a dword boundary
-                const uint32_t byte = (l.data[crc_pad(pos >> 2)] >> (8u * (pos & 3u))) & 0xFFu;
-                c = (c >> 8) ^ l.table[0][(c ^ byte) & 0xFFu];
-                pos++;
-            }
-            while (pos + 4 <= seg_end) {  // slice-by-4
-                c ^= l.data[crc_pad(pos >> 2)];
-                c = l.table[3][c & 0xFFu] ^ l.table[2][(c >> 8) & 0xFFu] ^ l.table[1][(c >> 16) & 0xFFu] ^
-                    l.table[0][c >> 24];
-                pos += 4;
-            }
-            while (pos < seg_end) {  // tail bytes
-                const uint32_t byte = (l.data[crc_pad(pos >> 2)] >> (8u * (pos & 3u))) & 0xFFu;
-                c = (c >> 8) ^ l.table[0][(c ^ byte) & 0xFFu];
-                pos++;
-            }
+            auto byte_at = [&](uint32_t at) { return (l.data[crc_pad(at >> 2)] >> (8u * (at & 3u))) & 0xFFu; };
+            for (; pos < seg_end && (pos & 3u); pos++) c = crc_byte(l.table, c, byte_at(pos));  // up to a dword boundary
+            for (; pos + 4 <= seg_end; pos += 4) c = crc_word(l.table, c, l.data[crc_pad(pos >> 2)]);
+            for (; pos < seg_end; pos++) c = crc_byte(l.table, c, byte_at(pos));
             crc = ~c;
         }
         l.part[tid] = crc;
         __syncthreads();
         // the pairs of a level are handled by the LOWEST threads, so that a level keeps only as many
         // waves busy as it has work for
-        for (uint32_t level = 0; level < kLevels; level++) {
+        for (uint32_t level = 0; level < 10; level++) {
             const uint32_t stride = 1u << level;
             const uint32_t left = 2 * stride * tid;  // index of the pair's left part
             uint32_t merged = 0;
             const bool act = left < T;
-            if (act) merged = gf2_multmodp(cc.pow64[level], l.part[left]) ^ l.part[left + stride];
+            if (act) merged = crc_mulmod<kCrcPoly32>(cc.pow64[level], l.part[left]) ^ l.part[left + stride];
             __syncthreads();
             if (act) l.part[left] = merged;
             __syncthreads();
         }
-        // crc(A || chunk) = crc(A) * x^(8 * chunk) + crc(chunk); the first chunk has no A
-        total = cb == 0 ? l.part[0] : (gf2_multmodp(pow_chunk, total) ^ l.part[0]);
+        // crc(A || chunk) = crc(A) * x^(8 * chunk) + crc(chunk); the first chunk has no A.  (The constant is the
+        // second factor: as the first, its 32 bit tests are hoisted out of the loop as 64-bit masks, which spill.)
+        total = cb == 0 ? l.part[0] : (crc_mulmod<kCrcPoly32>(total, cc.pow_tile) ^ l.part[0]);
         if (n == 0) break;
     }
     return total;
@@ -4320,11 +4282,11 @@ __device__ uint32_t crc32_workgroup(CrcLdsT<T> &l, const uint8_t *__restrict__ i
 
 // CRC-32 of in[0..n) by a 256-thread workgroup whose threads read their bytes straight from global
 // memory: thread t owns ONE contiguous 256-byte segment per 64 KiB chunk (segments aligned to the end of
-// the input, so only the first is short), runs slice-by-4 over it out of registers -- sixteen 16-byte
-// loads, the byte alignment taken out with v_alignbyte -- and the 256 partial CRCs are combined by the
-// GF(2) log-tree once per chunk.  Against crc32_workgroup<256> (64-byte segments staged in LDS, a tree
-// per 16 KiB): a BGZF block needs one tree instead of four to five (the tree was more than half of that
-// routine's instructions), no staging traffic through LDS, and 5 KiB of LDS instead of 21.
+// the input, so only the first is short), runs slice-by-4 over it out of registers (crc_seg256), and the
+// 256 partial CRCs are combined by the GF(2) log-tree once per chunk.  Against 64-byte segments staged in
+// LDS with a tree per 16 KiB, which this replaced: a BGZF block needs one tree instead of four to five (the
+// tree was more than half of that routine's instructions), no staging traffic through LDS, and 5 KiB of
+// LDS instead of 21.
 struct CrcDirectLds {
     uint32_t table[4][256];
     uint32_t part[kCrcSmall];
@@ -4333,21 +4295,7 @@ struct CrcDirectLds {
 __device__ uint32_t crc32_direct(CrcDirectLds &l, const uint8_t *__restrict__ in, uint32_t n, const CrcConsts &cc,
                                  uint32_t tid) {
     constexpr uint32_t T = kCrcSmall, kSegB = 256, kChunk = T * kSegB;  // 64 KiB per chunk
-    for (uint32_t i = tid; i < 256; i += T) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-        l.table[0][i] = c;
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < 256; i += T) {
-        const uint32_t t0 = l.table[0][i];
-        const uint32_t t1 = (t0 >> 8) ^ l.table[0][t0 & 0xFFu];
-        const uint32_t t2 = (t1 >> 8) ^ l.table[0][t1 & 0xFFu];
-        const uint32_t t3 = (t2 >> 8) ^ l.table[0][t2 & 0xFFu];
-        l.table[1][i] = t1;
-        l.table[2][i] = t2;
-        l.table[3][i] = t3;
-    }
+    crc_tables_fill<kCrcPoly32>(l.table, tid, T);
     uint32_t total = 0;
     const uint32_t first_len = n ? ((n - 1) % kChunk) + 1 : 0;
     for (uint32_t cb = 0; cb < n || cb == 0; cb += (cb == 0 ? first_len : kChunk)) {
@@ -4359,49 +4307,8 @@ __device__ uint32_t crc32_direct(CrcDirectLds &l, const uint8_t *__restrict__ in
             const uint32_t sb = seg_end_i > (int32_t)kSegB ? (uint32_t)seg_end_i - kSegB : 0u;
             const uint32_t len = (uint32_t)seg_end_i - sb;
             const uint8_t *p = in + cb + sb;
-            uint32_t c = 0xFFFFFFFFu;
-            if (len == kSegB) {
-                const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
-                const uint32_t *q = (const uint32_t *)(p - mis);
-                // the input's very last dword pair: nothing behind the input may be read
-                const bool at_end = cb + (uint32_t)seg_end_i == n && mis == 0;
-                uint32_t carry = q[0];
-                // 128 bytes (eight 16-byte loads in flight) per step: a lane uses every cache line it
-                // fetches while it is still on chip -- with one 16-byte load per step the lanes' 256-byte
-                // stride made the kernel fetch the input four times over (PMC: 2.26 GB for 0.58 GB; 64
-                // bytes per step: 1.21 GB)
-                for (uint32_t g = 0; g < 2; g++) {
-                    dword4 v[8];
-#pragma unroll
-                    for (uint32_t k = 0; k < 8; k++) {
-                        if (g == 1 && k == 7 && at_end) {
-                            v[k].x = q[61];
-                            v[k].y = q[62];
-                            v[k].z = q[63];
-                            v[k].w = 0;
-                        } else {
-                            v[k] = *(const dword4 *)(q + 1 + 32 * g + 4 * k);
-                        }
-                    }
-#pragma unroll
-                    for (uint32_t k = 0; k < 8; k++) {
-                        const uint32_t w[4] = {__builtin_amdgcn_alignbyte(v[k].x, carry, mis),
-                                               __builtin_amdgcn_alignbyte(v[k].y, v[k].x, mis),
-                                               __builtin_amdgcn_alignbyte(v[k].z, v[k].y, mis),
-                                               __builtin_amdgcn_alignbyte(v[k].w, v[k].z, mis)};
-                        carry = v[k].w;
-#pragma unroll
-                        for (uint32_t j = 0; j < 4; j++) {
-                            c ^= w[j];
-                            c = l.table[3][c & 0xFFu] ^ l.table[2][(c >> 8) & 0xFFu] ^ l.table[1][(c >> 16) & 0xFFu] ^
-                                l.table[0][c >> 24];
-                        }
-                    }
-                }
-            } else {  // the short first segment of the input (one thread per input)
-                for (uint32_t i = 0; i < len; i++) c = (c >> 8) ^ l.table[0][(c ^ p[i]) & 0xFFu];
-            }
-            crc = ~c;
+            if (len == kSegB) crc = ~crc_seg256(l.table, p, cb + (uint32_t)seg_end_i == n, 0xFFFFFFFFu);
+            else crc = ~crc_bytes(l.table, p, len, 0xFFFFFFFFu);  // the short first segment of the input (one thread per input)
         }
         l.part[tid] = crc;
         __syncthreads();
@@ -4412,20 +4319,21 @@ __device__ uint32_t crc32_direct(CrcDirectLds &l, const uint8_t *__restrict__ in
             const uint32_t left = 2 * stride * tid;
             uint32_t merged = 0;
             const bool act = left < T;
-            if (act) merged = gf2_multmodp(cc.pow64[level + 2], l.part[left]) ^ l.part[left + stride];
+            if (act) merged = crc_mulmod<kCrcPoly32>(cc.pow64[level + 2], l.part[left]) ^ l.part[left + stride];
             __syncthreads();
             if (act) l.part[left] = merged;
             __syncthreads();
         }
-        // crc(A || chunk) = crc(A) * x^(8 * chunk) + crc(chunk); the first chunk has no A
-        total = cb == 0 ? l.part[0] : (gf2_multmodp(cc.pow_tile, total) ^ l.part[0]);
+        // crc(A || chunk) = crc(A) * x^(8 * chunk) + crc(chunk); the first chunk has no A.  (The constant is the
+        // second factor: as the first, its 32 bit tests are hoisted out of the loop as 64-bit masks, which spill.)
+        total = cb == 0 ? l.part[0] : (crc_mulmod<kCrcPoly32>(total, cc.pow_tile) ^ l.part[0]);
         if (n == 0) break;
     }
     return total;
 }
 
 // The compressor's CRC kernel needs nothing but the input, so it runs on a low-priority SIDE STREAM
-// beside k_hist / k_huffman (gzpx_api.cpp, enqueue_batch): small workgroups (256 threads, 21 KiB of
+// beside k_hist / k_huffman (gzpx_api.cpp, enqueue_batch): small workgroups (256 threads, 5 KiB of
 // LDS) that slip in between k_huffman's one-wave workgroups.  (The 1024-thread routine of k_dcrc32
 // in the same place: the join waits 0.24 ms for it, step 4.86 -> 5.00 ms.)
 __global__ __launch_bounds__(kCrcSmall) void k_crc32(Config cfg, const uint8_t *__restrict__ slab,
@@ -5675,15 +5583,15 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_cksum.h"
 
 // CRC-32 of the inflated blocks (LibDeflateCrc over the whole orig_size buffer, src/check.rs:45-71):
-// the workgroup routine of k_crc32, blocks addressed through their output offsets.
+// crc32_workgroup, blocks addressed through their output offsets.
 __global__ __launch_bounds__(kCrcThreads, 8) void k_dcrc32(const uint8_t *__restrict__ out_all,
                                                 const uint64_t *__restrict__ out_off,
                                                 const DBlock *__restrict__ blk_all,
                                                 uint32_t *__restrict__ crc_found, CrcConsts cc) {
-    __shared__ CrcLds l;
+    __shared__ CrcWgLds l;
     const uint32_t b = blockIdx.x;
     if (blk_all[b].nmatch & 0x80000000u) return;  // (kLcCrcDone: k_lzcopy took the member's CRC from its tiles in LDS)
-    const uint32_t total = crc32_workgroup<kCrcThreads>(l, out_all + out_off[b], blk_all[b].isize, cc, threadIdx.x);
+    const uint32_t total = crc32_workgroup(l, out_all + out_off[b], blk_all[b].isize, cc, threadIdx.x);
     if (threadIdx.x == 0) crc_found[b] = total;
 }
 
@@ -6062,7 +5970,7 @@ uint32_t cksum_workgroups(int n_cu, uint32_t width) { return width ? width : (ui
 void launch_cksum_batch(int kind, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
                         uint32_t n, const uint32_t *d_seeds, const uint32_t *d_expected, uint32_t *d_sums, void *d_results,
                         const CksumScratch &s, uint32_t workgroups, hipStream_t stream) {
-    static const CkPow pw_crc32 = ck_pow_table<kCkPolyCrc32>(), pw_crc32c = ck_pow_table<kCkPolyCrc32c>();
+    static const CrcPow pw_crc32 = crc_pow_table<kCrcPoly32>(), pw_crc32c = crc_pow_table<kCrcPoly32c>();
     const CkTable t{d_in, in_len, d_offsets, d_sizes, n};
     const CkOut o{d_seeds, d_expected, d_sums, (WrapResult *)d_results};
     hipLaunchKernelGGL(k_cksum_plan, dim3(1), dim3(kCkPlanThreads), 0, stream, t, s.prefix, s.rec);

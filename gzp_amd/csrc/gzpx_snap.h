@@ -23,7 +23,6 @@ constexpr uint32_t kSnapMaxTable = 16384;                             // snappy'
 constexpr uint32_t kSnapStageStride = kSnapStageBytes;
 static_assert(kSnapStageBytes >= 32u + kSnapChunk + kSnapChunk / 6u, "MaxCompressedLength");
 constexpr uint32_t kSnapMargin = 15;                                  // kInputMarginBytes
-constexpr uint32_t kSnapCrcPoly = 0x82F63B78u;                        // CRC-32C, reflected
 constexpr uint32_t kSnapEmitThreads = 256;
 
 // The literal scan's probe j lies kSnapProbe.off[j] bytes behind the scan's start: skip starts at 32 and grows by
@@ -56,22 +55,12 @@ __device__ __forceinline__ uint32_t snap_chunk_len(uint64_t slab_len, uint32_t b
 
 __device__ __forceinline__ bool snap_stored(uint32_t n, uint32_t clen) { return clen >= n - n / 8u; }
 
-// GF(2) product of two CRC-32C remainders (reflected)
-__device__ __forceinline__ uint32_t crc32c_mul(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; i++) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b >> 1) ^ (kSnapCrcPoly & (0u - (b & 1u)));
-    }
-    return p;
-}
-
-// x^(8 m) mod P
+// x^(8 m) mod P of CRC-32C, squared up on the fly (a wave has no table to keep)
 __device__ __forceinline__ uint32_t crc32c_x8n(uint32_t m) {
     uint32_t r = 0x80000000u, sq = 0x00800000u;  // x^0, x^8
     while (m) {
-        if (m & 1u) r = crc32c_mul(r, sq);
-        sq = crc32c_mul(sq, sq);
+        if (m & 1u) r = crc_mulmod<kCrcPoly32c>(r, sq);
+        sq = crc_mulmod<kCrcPoly32c>(sq, sq);
         m >>= 1;
     }
     return r;
@@ -85,10 +74,10 @@ __device__ uint32_t snap_crc32c_wave(const uint8_t *__restrict__ src, uint32_t n
     uint32_t r = 0;
     for (uint32_t i = lo; i < hi; i++) {
         r ^= src[i];
-        for (int t = 0; t < 8; t++) r = (r >> 1) ^ (kSnapCrcPoly & (0u - (r & 1u)));
+        for (int t = 0; t < 8; t++) r = (r >> 1) ^ (kCrcPoly32c & (0u - (r & 1u)));
     }
-    uint32_t v = hi > lo ? crc32c_mul(crc32c_x8n(n - hi), r) : 0u;
-    if (lane == 0) v ^= crc32c_mul(crc32c_x8n(n), 0xFFFFFFFFu);
+    uint32_t v = hi > lo ? crc_mulmod<kCrcPoly32c>(crc32c_x8n(n - hi), r) : 0u;
+    if (lane == 0) v ^= crc_mulmod<kCrcPoly32c>(crc32c_x8n(n), 0xFFFFFFFFu);
     for (int m = 32; m >= 1; m >>= 1) v ^= __shfl_xor(v, m);
     const uint32_t c = ~v;
     return ((c >> 15) | (c << 17)) + 0xa282ead8u;

@@ -42,6 +42,13 @@ enum { kWrapRaw = 0, kWrapZlib = 1, kWrapGzip = 2 };
 // every kAdlerFold chunks: with 0xFF bytes throughout a stays below 65521 + 256 * 4080 < 2^21 and b below
 // 65521 + 256 * (4096 * 2^21 + 34680) < 2^42 between folds.  What a lane holds at the end moves to the buffer's end with
 // (n - E) a -- below 2^32 * 2^16.  Then a wave reduction by shuffles and the four waves through LDS.
+//
+// It lives here because the zlib wrapper needs the same sum over every inflated member as gzpx_adler32
+// (Adler32::update, src/check.rs:85-164, pinned on Python's zlib module in tests/test_checks.py and
+// tests/test_gpu_checks.py): adler_workgroup is the one device routine, and k_adler32_tiles (one (s1, s2, n) per
+// 64 KiB tile, combined on the host; launch_adler32 is with the other launchers in gzpx_kernels.hip), k_dadler32 (a
+// workgroup per member) and k_cksum_tiles (gzpx_cksum.h) are its callers.  Adler32::combine and Crc32::combine are
+// plain arithmetic in gzpx_api.cpp.
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kAdlerBase = 65521u;
 constexpr uint32_t kAdlerThreads = 256u;

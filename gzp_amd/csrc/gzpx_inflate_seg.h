@@ -66,27 +66,12 @@ __device__ __forceinline__ uint32_t seg_entry(uint32_t sym, uint32_t cl) {
         if (sym < 256) return cl | kSegLit | (sym << 16) | (cl << 25);
         if (sym == 256) return cl | kSegEob | (cl << 25);
         if (sym > 285) return kSegBadL;
-        const uint32_t slot = sym - 257;
-        uint32_t base, xb = 0;
-        if (slot < 8) {
-            base = 3 + slot;
-        } else if (slot == 28) {
-            base = 258;
-        } else {
-            xb = (slot - 4) >> 2;
-            base = 3 + ((4 + (slot & 3)) << xb);
-        }
-        return cl | kSegLen | (xb << 8) | (base << 16) | ((cl + xb) << 25);
+        const DeflateSym y = length_sym(sym - 257);
+        return cl | kSegLen | (y.xbits << 8) | (y.base << 16) | ((cl + y.xbits) << 25);
     }
     if (sym > 29) return kSegBadO;
-    uint32_t base, xb = 0;
-    if (sym < 4) {
-        base = 1 + sym;
-    } else {
-        xb = (sym - 2) >> 1;
-        base = 1 + ((2 + (sym & 1)) << xb);
-    }
-    return cl | (xb << 8) | (base << 16);
+    const DeflateSym y = offset_sym(sym);
+    return cl | (y.xbits << 8) | (y.base << 16);
 }
 
 struct InfSegLds {
@@ -120,14 +105,7 @@ __device__ __attribute__((noinline)) bool seg_build(InfSegLds &h, uint16_t *cwta
     const uint64_t lane_below = (1ull << lane) - 1ull;
     const uint32_t rounds = (nsyms + 63) >> 6;
     uint32_t cnt[16];
-#pragma unroll
-    for (uint32_t l = 0; l < 16; l++) cnt[l] = 0;
-    for (uint32_t r = 0; r < rounds; r++) {
-        const uint32_t s = 64 * r + lane;
-        const uint32_t myl = s < nsyms ? lens[s] : 0;
-#pragma unroll
-        for (uint32_t l = 1; l <= 15; l++) cnt[l] += (uint32_t)__popcll(__ballot(myl == l));
-    }
+    code_count_lengths(lens, nsyms, lane, cnt);
     uint32_t code = 0, kraft = 0;
     wave_sync();
 #pragma unroll
@@ -137,14 +115,10 @@ __device__ __attribute__((noinline)) bool seg_build(InfSegLds &h, uint16_t *cwta
         code += cnt[l];
         kraft += cnt[l] << (15 - l);
     }
-    if (kraft > (1u << 15)) return false;
-    if (kraft < (1u << 15)) {
-        if (kraft != 0 && (kraft != (1u << 14) || cnt[1] != 1)) return false;
-        uint32_t only = 0;  // the one symbol of the code (symbol 0 for the empty code)
-        for (uint32_t r = 0; r < rounds && kraft; r++) {
-            const uint64_t m = __ballot(64 * r + lane < nsyms && lens[64 * r + lane] == 1);
-            if (m) only = 64 * r + (uint32_t)__ffsll((long long)m) - 1;
-        }
+    const CodeShape shape = code_shape(kraft, cnt[1]);
+    if (shape == kCodeRefused) return false;
+    if (shape == kCodeDegenerate) {
+        const uint32_t only = kraft ? code_only_symbol(lens, nsyms, lane) : 0;  // the one symbol of the code (symbol 0 for the empty code)
         const uint32_t e = seg_entry<KIND>(only, 1);
         for (uint32_t i = lane; i < (1u << root); i += 64) main[i] = e;  // (no pointer entries: the second level is never read through them)
         if (sub)
@@ -165,15 +139,9 @@ __device__ __attribute__((noinline)) bool seg_build(InfSegLds &h, uint16_t *cwta
     for (uint32_t r = 0; r < rounds; r++) {
         const uint32_t s = 64 * r + lane;
         const uint32_t myl = s < nsyms ? lens[s] : 0;
-        uint32_t rank = 0;
-#pragma unroll
-        for (uint32_t l = 1; l <= 15; l++) {
-            const uint64_t m = __ballot(myl == l);
-            if (myl == l) rank = run[l] + (uint32_t)__popcll(m & lane_below);
-            run[l] += (uint32_t)__popcll(m);
-        }
+        const uint32_t rank = code_rank_step<15>(myl, run, lane_below);
         if (myl) {
-            const uint32_t cw = __brev(h.first[myl] + rank) >> (32 - myl);
+            const uint32_t cw = canon_codeword(h.first[myl] + rank, myl);
             cwtab[s] = (uint16_t)cw;
             if (myl <= root) {
                 const uint32_t e = seg_entry<KIND>(s, myl);
@@ -368,21 +336,19 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
         }
         // ---- code lengths
         if (btype == 1) {
-            for (uint32_t i = lane; i < 320; i += 64)
-                h.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5);
+            for (uint32_t i = lane; i < 320; i += 64) h.lens[i] = (uint8_t)fixed_code_len(i);
             wave_sync();
         } else {
-            const uint32_t nlit = ((hb >> 3) & 31u) + 257, ndist = ((hb >> 8) & 31u) + 1;
-            const uint32_t nclen = ((hb >> 13) & 15u) + 4;
+            const DynHeader dh = dyn_header(hb >> 3);
+            const uint32_t nlit = dh.nlit, ndist = dh.ndist, nclen = dh.nclen;
             bp += 14;
-            if (nlit > 286 + 2 || ndist > 32) {
+            if (!dh.ok) {
                 bad = true;
                 break;
             }
             {
-                const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
                 const uint32_t v = hbits(bp + 3u * (lane < 19 ? lane : 0)) & 7u;
-                if (lane < 19) h.lens[order[lane]] = (uint8_t)(lane < nclen ? v : 0u);
+                if (lane < 19) h.lens[precode_order(lane)] = (uint8_t)(lane < nclen ? v : 0u);
             }
             bp += 3u * nclen;
             wave_sync();
@@ -406,21 +372,9 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
                 const uint32_t bb = hbits(bp + lane);
                 const uint32_t e = h.ofast[bb & 127u];
                 const uint32_t cl = e & 15u, sym = e >> 16;
-                uint32_t rep = 1, val = sym, used = cl;
-                if (sym == 16) {
-                    rep = 3 + ((bb >> cl) & 3u);
-                    used += 2;
-                } else if (sym == 17) {
-                    rep = 3 + ((bb >> cl) & 7u);
-                    used += 3;
-                    val = 0;
-                } else if (sym == 18) {
-                    rep = 11 + ((bb >> cl) & 127u);
-                    used += 7;
-                    val = 0;
-                }
-                // used (<= 14) | rep (<= 138) << 8 | val (<= 16: 16 = the length before) << 16; 0 = an unused codeword
-                const uint32_t pack = cl ? used | (rep << 8) | (val << 16) : 0u;
+                const PrecodeRun run = precode_run(sym, bb, cl);
+                // used (<= 14) | rep (<= 138) << 8 | val (<= 16: kPrecodePrev = the length before) << 16; 0 = an unused codeword
+                const uint32_t pack = cl ? run.used | (run.rep << 8) | (run.val << 16) : 0u;
                 uint32_t cur = 0;
                 while (cur < 64u && i < total) {
                     const uint32_t pk = rdlane(pack, cur);
@@ -430,7 +384,7 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
                     }
                     const uint32_t r = (pk >> 8) & 255u;
                     uint32_t v = pk >> 16;
-                    if (v == 16) {
+                    if (v == kPrecodePrev) {
                         if (i == 0) {
                             bad = true;
                             break;
@@ -448,18 +402,7 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
                 bp += cur;
             }
             if (bad) break;
-            wave_sync();
-            uint8_t mine[5];
-            for (uint32_t k = 0; k < 5; k++) {
-                const uint32_t s = lane + 64 * k;
-                uint32_t v = 0;
-                if (s < 288) v = s < nlit ? tmp[s] : 0;
-                else if (s < 320) v = (s - 288) < ndist ? tmp[nlit + (s - 288)] : 0;
-                mine[k] = (uint8_t)v;
-            }
-            wave_sync();
-            for (uint32_t k = 0; k < 5; k++) h.lens[lane + 64 * k] = mine[k];
-            wave_sync();
+            code_lengths_split(tmp, h.lens, nlit, ndist, lane);
             if (h.lens[256] == 0) {  // (no end-of-block code: k_inflate's to run to its end)
                 bad = true;
                 break;

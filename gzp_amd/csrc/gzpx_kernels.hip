@@ -172,69 +172,19 @@ __device__ __forceinline__ uint64_t block_exclusive_scan256(uint64_t v, uint64_t
     return base + inc - v;
 }
 
-// DEFLATE length slot of (len - 3), offset slot of (off - 1): closed forms of the RFC 1951 tables
-__device__ __forceinline__ void length_slot(uint32_t len, uint32_t &slot, uint32_t &ebits,
-                                            uint32_t &eval) {
-    const uint32_t x = len - 3;
-    if (x < 8) {
-        slot = x;
-        ebits = 0;
-        eval = 0;
-    } else if (x == 255) {
-        slot = 28;
-        ebits = 0;
-        eval = 0;
-    } else {
-        const uint32_t k = 31 - __clz((int)x);  // 3..7
-        ebits = k - 2;
-        slot = 4 * k - 4 + ((x >> ebits) & 3);
-        eval = x & ((1u << ebits) - 1);
-    }
-}
+// RFC 1951's alphabets, the precode order, the fixed code, the dynamic header's fields and the canonical-code steps
+#define GZPX_DEFLATE_WAVE
+#include "gzpx_deflate.h"
 
-__device__ __forceinline__ void offset_slot(uint32_t off, uint32_t &slot, uint32_t &ebits,
-                                            uint32_t &eval) {
-    const uint32_t d = off - 1;
-    if (d < 4) {
-        slot = d;
-        ebits = 0;
-        eval = 0;
-    } else {
-        const uint32_t k = 31 - __clz((int)d);  // 2..14
-        ebits = k - 1;
-        slot = 2 * k + ((d >> ebits) & 1);
-        eval = d & ((1u << ebits) - 1);
-    }
-}
-
-// The two token consumers (k_hist, k_emit) look slots up without a branch: a text wave always holds
-// literals and matches, so every side of a branch would run for every token.
-//   length: a 256-entry LDS table of length - 3.  k_hist keeps slot | extra-bit count << 5 (length_entry);
-//           k_emit builds, from the same entries, the codeword and extra bits of every length for each sub-block
-//   offset: d = offset - 1.  With k = floor(log2(d | 1)) the extra-bit count is max(k - 1, 0) and the slot
-//           2k + the bit below d's top bit, which for d < 4 is d itself
+// The two token consumers (k_hist, k_emit) look lengths up in a 256-entry LDS table of length - 3.  k_hist keeps
+// slot | extra-bit count << 5 (length_entry); k_emit builds, from the same entries, the codeword and extra bits of
+// every length for each sub-block.
 __device__ __forceinline__ uint32_t length_entry(uint32_t x) {
-    uint32_t ls, le, lv;
-    length_slot(x + 3, ls, le, lv);
-    return ls | (le << 5);
+    const DeflateSlot s = length_slot(x + 3);
+    return s.slot | (s.xbits << 5);
 }
 __device__ __forceinline__ void build_length_table(uint8_t *lslot, uint32_t tid) {
     if (tid < 256) lslot[tid] = (uint8_t)length_entry(tid);
-}
-
-__device__ __forceinline__ void offset_slot_flat(uint32_t d, uint32_t &slot, uint32_t &ebits) {
-    const uint32_t k = 31u - (uint32_t)__clz((int)(d | 1u));
-    ebits = (uint32_t)max((int)k - 1, 0);
-    slot = 2u * k + ((d >> ebits) & 1u);
-}
-
-
-// RFC 1951's order of the code length code lengths (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13,
-// 2, 14, 1, 15), five bits each in two constants: a table indexed by a lane or a loop counter would be an
-// array in scratch memory.  i < 19.
-__device__ __forceinline__ uint32_t precode_order(uint32_t i) {
-    const uint64_t lo = 0x22caa324e804a30ull, hi = 0x3c2e1346cull;
-    return i < 12u ? (uint32_t)(lo >> (5u * i)) & 31u : (uint32_t)(hi >> (5u * (i - 12u))) & 31u;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -865,9 +815,11 @@ __device__ __forceinline__ void clear_marks(uint32_t seg_begin, uint32_t seg_end
 }
 
 // choose_max_block_end (FAST_SOFT_MAX_BLOCK_LENGTH, MIN_BLOCK_LENGTH): where a sub-block that
-// starts at `start` must end at the latest
+// starts at `start` must end at the latest.  SOFT_MAX: FAST_SOFT_MAX_BLOCK_LENGTH at level 1, SOFT_MAX_BLOCK_LENGTH
+// (kHcSoftMaxSub) at levels 2-9.
+template <uint32_t SOFT_MAX = kSoftMaxSub>
 __device__ __forceinline__ uint32_t sub_limit_of(uint32_t start, uint32_t n) {
-    return (n - start < kSoftMaxSub + kMinBlockLen) ? n : start + kSoftMaxSub;
+    return (n - start < SOFT_MAX + kMinBlockLen) ? n : start + SOFT_MAX;
 }
 
 constexpr uint32_t kPSeg = 64;  // positions per walk segment = one 64-bit word of the token bitmap
@@ -1671,10 +1623,6 @@ constexpr uint32_t kHcInWords = (32768 + kHcTile + 264) / 4 + 8;
 constexpr uint32_t kHcSoftMaxSub = 300000;  // SOFT_MAX_BLOCK_LENGTH
 constexpr uint32_t kHcSeqPerSub = 50000;    // SEQ_STORE_LENGTH
 
-__device__ __forceinline__ uint32_t hc_sub_limit_of(uint32_t start, uint32_t n) {
-    return (n - start < kHcSoftMaxSub + kMinBlockLen) ? n : start + kHcSoftMaxSub;
-}
-
 // choose_min_match_len
 __device__ __forceinline__ uint32_t hc_choose_min_len(uint32_t num_used, uint32_t depth) {
     uint32_t m = num_used < 6 ? 9 : num_used < 8 ? 8 : num_used < 10 ? 7 : num_used < 16 ? 6
@@ -1690,7 +1638,7 @@ __device__ __forceinline__ uint32_t hc_choose_min_len(uint32_t num_used, uint32_
 // call it (two barriers), `used` is 8 words of LDS.
 __device__ uint32_t hc_calc_min_len(const Config &cfg, const uint8_t *in, uint32_t start, uint32_t n,
                                     uint32_t *used, uint32_t tid, uint32_t nthreads) {
-    uint32_t data_len = hc_sub_limit_of(start, n) - start;
+    uint32_t data_len = sub_limit_of<kHcSoftMaxSub>(start, n) - start;
     __syncthreads();
     if (tid < 8) used[tid] = 0;
     __syncthreads();
@@ -2715,7 +2663,7 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
     uint32_t cur_sub = ld(&st->cur_sub);
     const uint32_t orphan_at = ld(&st->pad);  // position + 1 of the block's orphan match (k_match_hc), 0 = none
     uint32_t sub_start = entry_carry, sub_start_tok = tok_carry, sub_start_mat = mat_carry;
-    uint32_t sub_limit = hc_sub_limit_of(sub_start, n);
+    uint32_t sub_limit = sub_limit_of<kHcSoftMaxSub>(sub_start, n);
     uint32_t min_len = ld(&st->min_len);
     if (LOOP) __syncthreads();  // the previous round is done with the LDS state
     if (min_len == 0) {  // first round: the sub-block that starts the block (calculate_min_match_len)
@@ -3099,7 +3047,7 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
             sub_start = bp;
             sub_start_tok = bti;
             sub_start_mat = bm;
-            sub_limit = hc_sub_limit_of(bp, n);
+            sub_limit = sub_limit_of<kHcSoftMaxSub>(bp, n);
             stat_from = bti;
             const uint32_t new_min_len = hc_calc_min_len(cfg, in, bp, n, used, tid, kMpThreads);
             __syncthreads();
@@ -3268,7 +3216,7 @@ __global__ __launch_bounds__(64) void k_parse_lazy(Config cfg, const uint8_t *__
 #endif
     for (;;) {                            // DEFLATE sub-blocks
         const uint32_t sub_start = pos, sub_start_tok = ti;
-        const uint32_t max_block_end = hc_sub_limit_of(sub_start, n);
+        const uint32_t max_block_end = sub_limit_of<kHcSoftMaxSub>(sub_start, n);
         uint32_t min_len = hc_calc_min_len(cfg, in, sub_start, n, L.used, lane, 64);
         uint32_t next_recalc = sub_start + (n - sub_start < 10000u ? n - sub_start : 10000u);
         uint32_t nseq = 0, num_new = 0, num_obs = 0;
@@ -3557,11 +3505,7 @@ __global__ __launch_bounds__(256) void k_hist(Config cfg, const BlockMeta *__res
                 const bool m = (int32_t)t < 0;
                 const uint32_t lt = lslot[(t - 3u) & 0xFFu];
                 atomicAdd(&mine[m ? 257u + (lt & 31u) : t], 1u);
-                if (m) {
-                    uint32_t os, oe;
-                    offset_slot_flat(((t >> 9) & 0xFFFFu) - 1u, os, oe);
-                    atomicAdd(&mine[kNumLitlen + os], 1u);
-                }
+                if (m) atomicAdd(&mine[kNumLitlen + offset_slot(((t >> 9) & 0xFFFFu) - 1u).slot], 1u);
             }
         }
         __syncthreads();
@@ -3834,14 +3778,8 @@ __device__ void make_code(HuffLds &h, uint32_t num_syms, uint32_t compat, uint8_
     for (uint32_t base = 0; base < num_syms; base += 64) {
         const uint32_t s = base + lane;
         const uint32_t myl = s < num_syms ? lens[s] : 0;
-        uint32_t code = 0;
-#pragma unroll
-        for (uint32_t l = 1; l <= MAXL; l++) {
-            const uint64_t m = __ballot(myl == l);
-            if (myl == l) code = next_code[l] + (uint32_t)__popcll(m & lane_below);
-            next_code[l] += (uint32_t)__popcll(m);
-        }
-        if (myl) cw[s] = __brev(code) >> (32 - myl);
+        const uint32_t code = code_rank_step<MAXL>(myl, next_code, lane_below);
+        if (myl) cw[s] = canon_codeword(code, myl);
     }
     wave_sync();
 }
@@ -4065,21 +4003,20 @@ __global__ __launch_bounds__(64, GZPX_HUFF_WAVES) void k_huffman(Config cfg, Blo
             const uint32_t dl = h.lens[i];
             if (i < 256) {
                 dyn += f * dl;
-                sta += f * (i < 144 ? 8u : 9u);
+                sta += f * fixed_code_len(i);
             } else if (i == 256) {
                 dyn += dl;  // one EOB
-                sta += 7;
+                sta += fixed_code_len(256);
             } else if (i < 257 + 29) {
-                const uint32_t sl = i - 257;
-                const uint32_t xb = sl < 8 ? 0u : sl == 28 ? 0u : (sl - 4) >> 2;
+                const uint32_t xb = length_sym(i - 257).xbits;
                 dyn += f * (xb + dl);
-                sta += f * (xb + (i < 280 ? 7u : 8u));
+                sta += f * (xb + fixed_code_len(i));
             }
         }
         if (lane < 30) {
-            const uint32_t xb = lane < 4 ? 0u : (lane - 2) >> 1;
+            const uint32_t xb = offset_sym(lane).xbits;
             dyn += ofreq * (xb + h.olens[lane]);
-            sta += ofreq * (xb + 5u);
+            sta += ofreq * (xb + fixed_code_len(288 + lane));
         }
         dyn = wave_reduce_add(dyn) + 5 + 5 + 4 + 3 * num_explicit;
         sta = wave_reduce_add(sta);
@@ -4143,7 +4080,7 @@ __global__ __launch_bounds__(64, GZPX_HUFF_WAVES) void k_huffman(Config cfg, Blo
             wave_sync();
             hdr_bits = 3;
             sub_bits = 3 + sta;
-            // fixed codes of RFC 1951 3.2.6 (canonical, bit-reversed)
+            // fixed codes of RFC 1951 3.2.6 (canonical, bit-reversed; the lengths are fixed_code_len's)
             for (uint32_t i = lane; i < kNumLitlen; i += 64) {
                 uint32_t len, code;
                 if (i < 144) {
@@ -4656,13 +4593,12 @@ __device__ __forceinline__ void emit_block(const Config &cfg, const uint8_t *__r
                     const bool m = (int32_t)tk < 0;
                     const uint32_t lc = codes[m ? kEmitLenTab + ((tk - 3u) & 0xFFu) : tk];
                     const uint32_t d = m ? ((tk >> 9) & 0xFFFFu) - 1u : 0u;
-                    uint32_t os, oe;
-                    offset_slot_flat(d, os, oe);  // (a literal: slot 0, no extra bits)
+                    const DeflateSlot os = offset_slot(d);  // (a literal: slot 0, no extra bits)
                     // (read by every lane and masked: a branch here would keep the tokens' LDS reads apart)
-                    const uint32_t oc = codes[kNumLitlen + os] & (uint32_t)((int32_t)tk >> 31);
+                    const uint32_t oc = codes[kNumLitlen + os.slot] & (uint32_t)((int32_t)tk >> 31);
                     pa[j] = lc & 0xFFFFFFu;
-                    pb[j] = (oc & 0xFFFFu) | ((d & ((1u << oe) - 1u)) << (oc >> 16));
-                    nn[j] = (lc >> 24) | (((oc >> 16) + oe) << 8);
+                    pb[j] = (oc & 0xFFFFu) | (os.xval << (oc >> 16));
+                    nn[j] = (lc >> 24) | (((oc >> 16) + os.xbits) << 8);
                     sumnn += nn[j];  // (8 tokens: <= 160 and <= 224, the bytes do not carry)
                 }
                 // (fetched here, not before the lookups: the scan and the bit writer cover the latency, and this step's
@@ -4795,6 +4731,12 @@ constexpr uint32_t kInfR = GZPX_INF_R;  // groups of 64 bit positions decoded pe
 //   precode: bits 8-12 the symbol.
 enum InfKind { kInfLitlen = 0, kInfOffset = 1, kInfPrecode = 2 };
 
+// k_inflate states RFC 1951 in its own text -- the alphabets here, code counts, verdict and ranks in inflate_build,
+// the dynamic header in the kernel -- and every statement has to agree with gzpx_deflate.h (length_sym, offset_sym,
+// code_shape, code_rank_step, precode_order, fixed_code_len, dyn_header, precode_run, code_lengths_split), which
+// k_inflate_seg and the encoders call.  Measured, not preferred: with the shared routines in any of three mixes the
+// k_inflate route of the bench stream was 0.4 to 0.9 % slower than with this text, over eight alternations each
+// (docs/LAB_NOTES.md, "gzpx_deflate.h"); tests/inflate_cases.py and tests/alphabet_cases.py hold both routes to the same answers.
 template <int KIND>
 __device__ __forceinline__ uint32_t inflate_entry(uint32_t sym, uint32_t cl) {
     if (KIND == kInfPrecode) return cl | (sym << 8);
@@ -5667,44 +5609,22 @@ void launch_candidates(const Config &cfg, const uint8_t *slab, uint64_t slab_len
 bool level1_fused(const Config &cfg) { return cfg.block_size <= kTile && !(cfg.debug & 2u); }
 
 #ifdef GZPX_EXPERIMENT
-extern "C" int gzpx_exp_huff(unsigned long long out[8], int reset) {
+// the column sums of one of the 1024 x 8 counter tables, which is cleared afterwards if `reset`
+static int exp_read(const void *symbol, unsigned long long out[8], int reset) {
     static unsigned long long rows[1024 * 8];
-    if (hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_exp_huff), sizeof(rows)) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(rows, symbol, sizeof(rows)) != hipSuccess) return -1;
     for (int k = 0; k < 8; k++) out[k] = 0;
     for (int r = 0; r < 1024; r++)
         for (int k = 0; k < 8; k++) out[k] += rows[r * 8 + k];
     if (reset) {
         memset(rows, 0, sizeof(rows));
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_exp_huff), rows, sizeof(rows)) != hipSuccess) return -1;
+        if (hipMemcpyToSymbol(symbol, rows, sizeof(rows)) != hipSuccess) return -1;
     }
     return 0;
 }
-
-extern "C" int gzpx_exp_cycles(unsigned long long out[8], int reset) {
-    static unsigned long long rows[1024 * 8];
-    if (hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_exp_cycles), sizeof(rows)) != hipSuccess) return -1;
-    for (int k = 0; k < 8; k++) out[k] = 0;
-    for (int r = 0; r < 1024; r++)
-        for (int k = 0; k < 8; k++) out[k] += rows[r * 8 + k];
-    if (reset) {
-        memset(rows, 0, sizeof(rows));
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_exp_cycles), rows, sizeof(rows)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-
-extern "C" int gzpx_exp_sparse(unsigned long long out[8], int reset) {
-    static unsigned long long rows[1024 * 8];
-    if (hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_exp_sparse), sizeof(rows)) != hipSuccess) return -1;
-    for (int k = 0; k < 8; k++) out[k] = 0;
-    for (int r = 0; r < 1024; r++)
-        for (int k = 0; k < 8; k++) out[k] += rows[r * 8 + k];
-    if (reset) {
-        memset(rows, 0, sizeof(rows));
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_exp_sparse), rows, sizeof(rows)) != hipSuccess) return -1;
-    }
-    return 0;
-}
+extern "C" int gzpx_exp_huff(unsigned long long out[8], int reset) { return exp_read(HIP_SYMBOL(g_exp_huff), out, reset); }
+extern "C" int gzpx_exp_cycles(unsigned long long out[8], int reset) { return exp_read(HIP_SYMBOL(g_exp_cycles), out, reset); }
+extern "C" int gzpx_exp_sparse(unsigned long long out[8], int reset) { return exp_read(HIP_SYMBOL(g_exp_sparse), out, reset); }
 #endif
 
 void launch_match(const Config &cfg, const uint8_t *slab, uint64_t slab_len, uint32_t nb, const Scratch &s,
@@ -5817,6 +5737,18 @@ void launch_emit(const Config &cfg, const uint8_t *slab, uint64_t, uint32_t nb, 
                        (const uint32_t *)s.hdr, (const uint64_t *)s.out_off, out, out_cap, nb);
 }
 
+// How k_inflate_seg goes over nb members, in both of its forms: the waves per member, the grid, the hint word
+struct SegLaunch {
+    bool big;        // Mgzip-sized members: kSegBigW waves each
+    uint32_t grid;   // nb, or the resident workgroups if that is fewer
+    uint32_t *hint;
+};
+static SegLaunch seg_launch_of(const InflateScratch &sc, uint32_t nb) {
+    const bool big = nb && sc.in_bytes / nb >= kSegBigBytes;
+    const uint32_t wgs = (uint32_t)(sc.n_cu > 0 ? sc.n_cu : 256) * 4u * GZPX_SEG_WAVES / (big ? (uint32_t)kSegBigW : (uint32_t)kSegSmallW);
+    return {big, nb < wgs ? nb : wgs, sc.summary ? sc.summary + kDsSegHint : nullptr};
+}
+
 // The decode of nb members whose records and output offsets are in place (k_dinit + k_dscan, or k_dinit_wrap +
 // k_dscan_slots): k_inflate_seg + k_lzcopy + k_inflate over the redo list, or k_inflate for every member.  The
 // template arguments say which of the three kernels carries its clocks.
@@ -5831,16 +5763,13 @@ static void launch_inflate_members_as(const uint8_t *d_in, uint32_t nb, DBlock *
     }
     // decode (literals + match records), LZ copy, then k_inflate over whatever the two left on the redo list
     LzMatch *ml = (LzMatch *)sc.mlist;
-    const bool big = nb && sc.in_bytes / nb >= kSegBigBytes;  // Mgzip-sized members: kSegBigW waves each
-    const uint32_t seg_wgs = (uint32_t)(sc.n_cu > 0 ? sc.n_cu : 256) * 4u * GZPX_SEG_WAVES / (big ? (uint32_t)kSegBigW : (uint32_t)kSegSmallW);  // resident workgroups
-    const uint32_t seg_grid = nb < seg_wgs ? nb : seg_wgs;
-    uint32_t *seg_hint = sc.summary ? sc.summary + kDsSegHint : nullptr;
-    if (big)
-        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegBigW>), dim3(seg_grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
-                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint);
+    const SegLaunch sl = seg_launch_of(sc, nb);
+    if (sl.big)
+        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegBigW>), dim3(sl.grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
+                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, sl.hint);
     else
-        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegSmallW>), dim3(seg_grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
-                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, seg_hint);
+        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegSmallW>), dim3(sl.grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
+                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, sl.hint);
     if (ev_mid) (void)hipEventRecord(ev_mid, stream);
     hipLaunchKernelGGL((k_lzcopy<LC_DBG>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off, d_out,
                        (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
@@ -5921,18 +5850,15 @@ static void launch_inflate_sizes_as(const uint8_t *d_in, uint32_t nb, DBlock *bl
                            (uint8_t *)nullptr, 0ull, (const uint32_t *)nullptr);
         return;
     }
-    const bool big = nb && sc.in_bytes / nb >= kSegBigBytes;
-    const uint32_t seg_wgs = (uint32_t)(sc.n_cu > 0 ? sc.n_cu : 256) * 4u * GZPX_SEG_WAVES / (big ? (uint32_t)kSegBigW : (uint32_t)kSegSmallW);
-    const uint32_t seg_grid = nb < seg_wgs ? nb : seg_wgs;
-    uint32_t *seg_hint = sc.summary ? sc.summary + kDsSegHint : nullptr;
-    if (big)
-        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegBigW, true>), dim3(seg_grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
+    const SegLaunch sl = seg_launch_of(sc, nb);
+    if (sl.big)
+        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegBigW, true>), dim3(sl.grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
                            (const uint64_t *)nullptr, (uint8_t *)nullptr, 0ull, (LzMatch *)nullptr, (uint32_t *)nullptr, sc.redo,
-                           nb, seg_hint);
+                           nb, sl.hint);
     else
-        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegSmallW, true>), dim3(seg_grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
+        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegSmallW, true>), dim3(sl.grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
                            (const uint64_t *)nullptr, (uint8_t *)nullptr, 0ull, (LzMatch *)nullptr, (uint32_t *)nullptr, sc.redo,
-                           nb, seg_hint);
+                           nb, sl.hint);
     if (ev_mid) (void)hipEventRecord(ev_mid, stream);
     hipLaunchKernelGGL((k_inflate<DBG, true>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)nullptr,
                        (uint8_t *)nullptr, 0ull, (const uint32_t *)sc.redo);

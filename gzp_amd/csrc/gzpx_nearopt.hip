@@ -30,6 +30,8 @@
 
 namespace gzpx {
 
+#include "gzpx_deflate.h"  // length_slot, offset_slot, offset_sym: the slots and extra bits the costs and tallies go by
+
 namespace {
 
 constexpr uint32_t kNoWindow = 32768;
@@ -44,10 +46,6 @@ constexpr uint32_t kNoNumObs = 10, kNoNumLitObs = 8, kNoObsPerCheck = 512;
 constexpr uint32_t kNoNumLitlen = 288, kNoNumOffset = 32, kNoEob = 256, kNoFirstLen = 257;
 constexpr int32_t kNoDead = -32768;  // MATCHFINDER_INITVAL: never within the window of any position
 
-__device__ const uint16_t kNoLenBase[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,  13,  15,  17,  19,  23, 27,
-                                            31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-__device__ const uint8_t kNoLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-__device__ const uint8_t kNoOffExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
 // choose_min_match_len (deflate_compress.c): by the number of distinct literals in use
 __device__ const uint8_t kNoMinLens[80] = {9, 9, 9, 9, 9, 9, 8, 8, 7, 7, 6, 6, 6, 6, 6, 6, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5,
                                            5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 4, 4, 4, 4, 4, 4, 4, 4, 4,
@@ -100,18 +98,6 @@ __device__ __forceinline__ uint32_t no_le24(const uint8_t *p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
 }
 __device__ __forceinline__ uint32_t no_hash(uint32_t v, uint32_t bits) { return (v * 0x1E35A7BDu) >> (32 - bits); }
-__device__ __forceinline__ uint32_t no_length_slot(uint32_t len) {
-    uint32_t s = 0;
-    for (uint32_t i = 1; i < 29; i++)
-        if (len >= kNoLenBase[i]) s = i;
-    return s;
-}
-__device__ __forceinline__ uint32_t no_offset_slot(uint32_t off) {
-    // DEFLATE offset slots: 0..3 for 1..4, then two slots per power of two
-    if (off <= 4) return off - 1;
-    const uint32_t m = off - 1, hb = 31u - (uint32_t)__clz((int)m);
-    return 2 * hb + ((m >> (hb - 1)) & 1u);
-}
 // lz_extend, four bytes per step (unaligned dword loads are fine in global memory; both pointers stay inside the block:
 // len + 4 <= max_len <= bytes left)
 __device__ uint32_t no_lz_extend(const uint8_t *a, const uint8_t *b, uint32_t len, uint32_t max_len) {
@@ -342,10 +328,10 @@ __device__ void no_merge_stats(NoLane &L, NoStats &st) {
 }
 
 __device__ __forceinline__ uint32_t no_default_length_cost(uint32_t len, uint32_t len_sym_cost) {
-    return len_sym_cost + kNoLenExtra[no_length_slot(len)] * kNoBitCost;
+    return len_sym_cost + length_slot(len).xbits * kNoBitCost;
 }
 __device__ __forceinline__ uint32_t no_default_offset_cost(uint32_t slot) {
-    return 4 * kNoBitCost + (907 * kNoBitCost) / 1000 + kNoOffExtra[slot] * kNoBitCost;
+    return 4 * kNoBitCost + (907 * kNoBitCost) / 1000 + offset_sym(slot).xbits * kNoBitCost;
 }
 __device__ __forceinline__ uint32_t no_blend(uint32_t cost, uint32_t def, int change) {
     return change == 0 ? (def + 3 * cost) / 4 : change == 1 ? (def + cost) / 2 : change == 2 ? (5 * def + 3 * cost) / 8
@@ -415,7 +401,7 @@ __device__ void no_optimize_block(NoLane &L, NoStats &st, NoNode *nodes, const u
                 uint32_t len = kNoMinMatch;
                 do {
                     const uint32_t offset = match->offset, mlen = match->length;
-                    const uint32_t offset_cost = L.cost_off[no_offset_slot(offset)];
+                    const uint32_t offset_cost = L.cost_off[offset_slot(offset - 1).slot];
                     do {
                         const uint32_t c = offset_cost + L.cost_len[len] + (cur + len)->cost_to_end;
                         if (c < best) {
@@ -438,8 +424,8 @@ __device__ void no_optimize_block(NoLane &L, NoStats &st, NoNode *nodes, const u
             if (length == 1) {
                 L.fr_litlen[offset]++;
             } else {
-                L.fr_litlen[kNoFirstLen + no_length_slot(length)]++;
-                L.fr_offset[no_offset_slot(offset)]++;
+                L.fr_litlen[kNoFirstLen + length_slot(length).slot]++;
+                L.fr_offset[offset_slot(offset - 1).slot]++;
             }
             pos += length;
         }
@@ -448,11 +434,12 @@ __device__ void no_optimize_block(NoLane &L, NoStats &st, NoNode *nodes, const u
         no_make_code_lens(L, kNoNumOffset, 15, compat_1_10, L.fr_offset, L.lens_offset);
         for (uint32_t i = 0; i < 256; i++) L.cost_lit[i] = (L.lens_litlen[i] ? L.lens_litlen[i] : kNoLitNostat) * kNoBitCost;
         for (uint32_t i = kNoMinMatch; i <= kNoMaxMatch; i++) {
-            const uint32_t slot = no_length_slot(i), l = L.lens_litlen[kNoFirstLen + slot];
-            L.cost_len[i] = ((l ? l : kNoLenNostat) + kNoLenExtra[slot]) * kNoBitCost;
+            const DeflateSlot s = length_slot(i);
+            const uint32_t l = L.lens_litlen[kNoFirstLen + s.slot];
+            L.cost_len[i] = ((l ? l : kNoLenNostat) + s.xbits) * kNoBitCost;
         }
         for (uint32_t i = 0; i < 30; i++)
-            L.cost_off[i] = ((L.lens_offset[i] ? L.lens_offset[i] : kNoOffNostat) + kNoOffExtra[i]) * kNoBitCost;
+            L.cost_off[i] = ((L.lens_offset[i] ? L.lens_offset[i] : kNoOffNostat) + offset_sym(i).xbits) * kNoBitCost;
     }
     for (uint32_t pos = 0; pos < block_length;) {
         const uint32_t it = nodes[pos].item, length = it & 511u, offset = it >> 9;

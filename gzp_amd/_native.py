@@ -48,6 +48,8 @@ LINES_TILE = 16384  # GZPX_LINES_TILE: the tile of the line table, in bytes of t
 FIND_MAX_PATTERN = 256  # GZPX_FIND_MAX_PATTERN
 FIND_NO_LINES = -1      # GZPX_FIND_NO_LINES
 SELECT_INVERT = 1       # GZPX_SELECT_INVERT
+FINDSET_MAX_PATTERNS = 256  # GZPX_FINDSET_MAX_PATTERNS
+FINDSET_MAX_BYTES = 16384   # GZPX_FINDSET_MAX_BYTES: the sum of a set's pattern lengths
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -79,6 +81,7 @@ EXPORTS = [
     "gzpx_dctx_last_lines_build_ms",
     "gzpx_find_device", "gzpx_dctx_last_find_ms",
     "gzpx_select_lines_device", "gzpx_dctx_last_select_ms", "gzpx_read_lines_table_device",
+    "gzpx_find_set_device", "gzpx_dctx_last_find_set_ms", "gzpx_select_lines_set_device",
 ]
 
 
@@ -291,6 +294,14 @@ class GzpxLib:
                                                ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_dctx_last_select_ms.restype = i32
         L.gzpx_dctx_last_select_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_find_set_device.restype = i32
+        L.gzpx_find_set_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, sz, vp, pu64,
+                                           ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_find_set_ms.restype = i32
+        L.gzpx_dctx_last_find_set_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gzpx_select_lines_set_device.restype = i32
+        L.gzpx_select_lines_set_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, ctypes.c_uint64, ctypes.c_uint, vp, sz, pu64, pu64,
+                                                   pu64, ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_read_lines_table_device.restype = i32
         L.gzpx_read_lines_table_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, sz, psz, vp, vp, psz,
                                                    ctypes.POINTER(GzpxCheckInfo), vp]
@@ -1063,6 +1074,62 @@ class DContext:
         ms = (ctypes.c_float * 3)()
         self.lib.check(self.lib.L.gzpx_dctx_last_select_ms(self.h, ms))
         return ms[0], ms[1], ms[2]
+
+    # ---- search for a set of patterns (gzpx_findset.h)
+    @staticmethod
+    def _pattern_set(patterns):
+        """A sequence of bytes-likes as the C ABI takes a set: (the bytes joined, uint32 offsets[K + 1], K)."""
+        pats = [bytes(p) for p in patterns]
+        offsets = (ctypes.c_uint32 * (len(pats) + 1))()
+        for k, p in enumerate(pats):
+            offsets[k + 1] = offsets[k] + len(p)
+        return b"".join(pats), offsets, len(pats)
+
+    def find_set_device(self, index, d_in_ptr, in_len, patterns, delim=None, d_positions_ptr=None, d_ids_ptr=None, d_lines_ptr=None,
+                        hits_cap=0, d_counts_ptr=None, stream=None):
+        """Every (position, k) at which pattern k of the sequence `patterns` starts, ascending by position and at one
+        position by k: the positions into the device array d_positions_ptr (uint64[hits_cap]), the ids into d_ids_ptr
+        (uint32[hits_cap]) and, for the delimiter byte `delim`, the lines into d_lines_ptr (uint64[hits_cap]); each may be
+        None, all None counts only.  d_counts_ptr (uint64[len(patterns)], optional) receives the hits of every pattern.
+        Returns n_hits.  More hits than hits_cap: the first hits_cap are written and GzpxError is raised with
+        .needed = n_hits."""
+        blob, offsets, k = self._pattern_set(patterns)
+        n = ctypes.c_uint64(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_find_set_device(self.h, index.h, d_in_ptr, in_len, blob, offsets, k,
+                                             FIND_NO_LINES if delim is None else int(delim), d_positions_ptr, d_ids_ptr, d_lines_ptr,
+                                             hits_cap, d_counts_ptr, ctypes.byref(n), ctypes.byref(info), stream)
+        if rc == OK:
+            return n.value
+        if rc == ERR_INSUFFICIENT_SPACE and n.value:
+            raise GzpxError(rc, "the stream holds %d hits" % n.value, needed=n.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def last_find_set_ms(self):
+        """HIP-event durations of the last find_set_device, summed over its batches: (inflate, count, write)."""
+        ms = (ctypes.c_float * 3)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_find_set_ms(self.h, ms))
+        return ms[0], ms[1], ms[2]
+
+    def select_lines_set_device(self, index, lines, d_in_ptr, in_len, patterns, group=1, invert=False, d_runs_ptr=None,
+                                runs_cap=0, stream=None):
+        """select_lines_device with a hit of any pattern of the sequence `patterns` as "a hit".  Returns
+        (n_runs, n_records, n_hits); timings through last_select_ms."""
+        blob, offsets, k = self._pattern_set(patterns)
+        runs, records, hits = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        info = GzpxCheckInfo()
+        rc = self.lib.L.gzpx_select_lines_set_device(self.h, index.h, lines.h, d_in_ptr, in_len, blob, offsets, k, int(group),
+                                                     SELECT_INVERT if invert else 0, d_runs_ptr, runs_cap, ctypes.byref(runs),
+                                                     ctypes.byref(records), ctypes.byref(hits), ctypes.byref(info), stream)
+        if rc == OK:
+            return runs.value, records.value, hits.value
+        if rc == ERR_INSUFFICIENT_SPACE and runs.value:
+            raise GzpxError(rc, "the selection has %d runs" % runs.value, needed=runs.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
 
     def read_lines_table_device(self, index, lines, d_in_ptr, in_len, d_line_ranges_ptr, n_ranges, d_out_ptr, out_cap,
                                 d_out_offsets_ptr=None, d_byte_ranges_ptr=None, stream=None):

@@ -7,8 +7,10 @@
 // a HIP device every entry point fails with GZPX_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <cstddef>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1582,6 +1584,28 @@ struct SelectState : NoCopy {
     }
 };
 
+// search for a set (gzpx_find_set_device, gzpx_select_lines_set_device): the compiled set and the counts per pattern.
+// The pieces' counts and bases, the record and its pinned copy are the search's (c->find), as the selection uses them.
+struct FindSetState : NoCopy {
+    Event ev[4];                       // per batch: inflate [0..1], count + scan [1..2], write + carry [2..3]
+    float ms[3] = {0.0f, 0.0f, 0.0f};  // the last call's, summed over its batches
+    FsSet *d_set = nullptr;
+    FsSet *h_set = nullptr;        // pinned: the compiled set on its way in
+    uint64_t *d_counts = nullptr;  // [kFsMaxPatterns] the hits of every pattern
+    Allocs once;                   // the three above
+    bool ready = false;
+    int reserve() {
+        if (ready) return GZPX_OK;
+        once.release();  // (an earlier attempt that failed half way)
+        GZPX_TRY(once.dev(d_set, sizeof(FsSet)));
+        GZPX_TRY(once.dev(d_counts, kFsMaxPatterns * 8));
+        GZPX_TRY(once.pinned(h_set, sizeof(FsSet)));
+        for (Event &e : ev) GZPX_TRY(e.create(true));
+        ready = true;
+        return GZPX_OK;
+    }
+};
+
 }  // namespace
 
 // (members are destroyed last to first: memory and events of the slots and of each kind of call, then the streams)
@@ -1604,6 +1628,7 @@ struct gzpx_dctx : NoCopy {
     LinesState lines;
     FindState find;
     SelectState select;
+    FindSetState find_set;
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -2901,6 +2926,246 @@ int gzpx_dctx_last_select_ms(gzpx_dctx *ctx, float ms[3]) {
     std::lock_guard<std::mutex> g(ctx->mu);
     for (int j = 0; j < 3; j++) ms[j] = ctx->select.ms[j];
     return GZPX_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- search for a set of patterns (gzpx_findset.h)
+namespace {
+
+// what the entry points check of a set before anything else happens
+struct SetShape {
+    uint32_t K = 0, longest = 0, shortest = 0;
+};
+
+bool findset_shape(const void *patterns, const uint32_t *off, size_t n_patterns, SetShape &sh) {
+    static_assert(kFsMaxPatterns == GZPX_FINDSET_MAX_PATTERNS && kFsMaxBytes == GZPX_FINDSET_MAX_BYTES,
+                  "the public constants state the kernels' limits");
+    if (!patterns || !off || n_patterns == 0 || n_patterns > kFsMaxPatterns) return false;
+    sh.K = (uint32_t)n_patterns;
+    sh.shortest = kFdMaxPattern;
+    for (size_t k = 0; k < n_patterns; k++) {
+        if (off[k + 1] <= off[k] || off[k + 1] - off[k] > kFdMaxPattern) return false;  // (empty, too long, or decreasing)
+        const uint32_t m = off[k + 1] - off[k];
+        if (m > sh.longest) sh.longest = m;
+        if (m < sh.shortest) sh.shortest = m;
+    }
+    return off[n_patterns] - off[0] <= kFsMaxBytes;
+}
+
+// The set in the form the kernels stage into LDS; returns the bytes of it that are in use (bytes is the last table).
+size_t findset_compile(const uint8_t *patterns, const uint32_t *off, const SetShape &sh, FsSet *h) {
+    const uint32_t K = sh.K, q = sh.shortest < 4u ? sh.shortest : 4u;
+    uint32_t window[kFsMaxPatterns], order[kFsMaxPatterns];
+    memset(h->hdr, 0, sizeof(h->hdr));
+    const uint32_t bitmap_words = q == 1u ? 8u : kFsBitmapWords;
+    memset(h->bitmap, 0, bitmap_words * 4u);
+    uint32_t words = 0;
+    for (uint32_t k = 0; k < K; k++) {
+        const uint8_t *p = patterns + off[k];
+        const uint32_t m = off[k + 1] - off[k];
+        window[k] = 0;
+        for (uint32_t j = 0; j < q; j++) window[k] |= (uint32_t)p[j] << (8u * j);
+        const uint32_t bit = fs_gram_index(window[k], q);
+        h->bitmap[bit >> 5] |= 1u << (bit & 31u);
+        h->meta[k] = (words << 16) | m;
+        h->bytes[words + (m - 1u) / 4u] = 0;  // (the tail of the last dword)
+        memcpy(&h->bytes[words], p, m);
+        words += (m + 3u) / 4u;
+        order[k] = k;
+    }
+    // buckets: the ids sorted by window, ascending inside one window
+    std::stable_sort(order, order + K, [&](uint32_t x, uint32_t y) { return window[x] < window[y]; });
+    uint32_t grams = 0;
+    for (uint32_t j = 0; j < K; j++) {
+        if (j == 0 || window[order[j]] != window[order[j - 1]]) {
+            h->keys[grams] = window[order[j]];
+            h->bstart[grams++] = j;
+        }
+        h->ids[j] = order[j];
+    }
+    h->bstart[grams] = K;
+    while (words % 4u) h->bytes[words++] = 0;  // (staged as 16-byte words)
+    h->hdr[kFsHdrK] = K;
+    h->hdr[kFsHdrQ] = q;
+    h->hdr[kFsHdrM] = sh.longest;
+    h->hdr[kFsHdrGrams] = grams;
+    h->hdr[kFsHdrBitmapWords] = bitmap_words;
+    h->hdr[kFsHdrByteWords] = words;
+    return offsetof(FsSet, bytes) + (size_t)words * 4u;
+}
+
+// What a batch of the set's pass does.  Hits are owned by their START: a batch that is not the last owns the starts p
+// of its region with p + M <= the region's end (M the longest pattern), the last min(M - 1, bytes seen) bytes wait in
+// the carry, and the last batch owns every start that is left -- also when it holds no byte itself.
+struct SetBatch {
+    FindBatch fb;
+    bool search;     // the region is not empty and is either new or the last word on its starts
+    uint32_t carry;  // bytes to keep for the next batch (0: none, or the carry stays as it is)
+};
+
+SetBatch findset_batch(uint8_t *stage, uint64_t base, uint64_t bytes, bool is_last, uint32_t M, int delim) {
+    const uint32_t waiting = (uint32_t)(base < M - 1u ? base : M - 1u);
+    const uint64_t seen = base + bytes;
+    SetBatch s;
+    s.fb = FindBatch{stage, base, bytes, waiting, is_last ? 1u : M, delim};
+    s.search = bytes || (is_last && waiting);
+    s.carry = bytes && !is_last ? (uint32_t)(seen < M - 1u ? seen : M - 1u) : 0u;
+    return s;
+}
+
+// the compiled set and cleared records on their way to the device, in front of the first batch
+int findset_begin(gzpx_dctx *c, const void *patterns, const uint32_t *off, const SetShape &sh) {
+    FindSetState &fs = c->find_set;
+    const size_t used = findset_compile((const uint8_t *)patterns, off, sh, fs.h_set);
+    HIP_TRY(hipMemcpyAsync(fs.d_set, fs.h_set, used, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(fs.d_counts, 0, kFsMaxPatterns * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(c->find.fd.rec, 0, kFdRecWords * 8, c->stream));
+    return GZPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gzpx_find_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *patterns,
+                         const uint32_t *pattern_offsets, size_t n_patterns, int delim, uint64_t *d_positions, uint32_t *d_ids,
+                         uint64_t *d_lines, size_t hits_cap, uint64_t *d_counts, uint64_t *n_hits, gzpx_check_info *info,
+                         void *hip_stream) {
+    if (!c || !ix || !n_hits || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_hits = 0;
+    SetShape sh;
+    if (!findset_shape(patterns, pattern_offsets, n_patterns, sh)) return GZPX_ERR_INVALID_ARG;
+    if (delim < GZPX_FIND_NO_LINES || delim > 255 || (d_lines && delim == GZPX_FIND_NO_LINES)) return GZPX_ERR_INVALID_ARG;
+    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
+    const uint64_t total = ix->inflated_len;
+    const bool writes = d_positions || d_ids || d_lines;
+    const uint64_t cap = writes ? hits_cap : 0;
+    std::unique_lock<std::mutex> lk(c->mu);
+    FindSetState &fs = c->find_set;
+    FindState &f = c->find;
+    fs.ms[0] = fs.ms[1] = fs.ms[2] = 0.0f;
+    hipStream_t stream = c->stream;
+    if (!ix->n || sh.shortest > total) {  // no position can hold a pattern: nothing is inflated, every count is zero
+        if (!d_counts) return GZPX_OK;
+        if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+        GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+        Drain drain{{stream}, 1};
+        HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)sh.K * 8, stream));
+        return GZPX_OK;  // (the drain synchronises)
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    Drain drain{{stream}, 1};
+    Batches b;
+    GZPX_TRY(batches_of(c, ix, b));
+    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
+    GZPX_TRY(fs.reserve());
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    GZPX_TRY(findset_begin(c, patterns, pattern_offsets, sh));
+    GZPX_TRY(batched_pass(
+        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, fs.ev, 3, fs.ms, info, drain,
+        [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
+            const SetBatch sb = findset_batch(c->stage.d, base, bytes, is_last, sh.longest, d_lines ? delim : GZPX_FIND_NO_LINES);
+            HIP_TRY(hipEventRecord(fs.ev[1], stream));
+            if (sb.search) launch_findset_count(sb.fb, f.fd, fs.d_set, fs.d_counts, stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(fs.ev[2], stream));
+            if (sb.search && cap) launch_findset_write(sb.fb, f.fd, fs.d_set, d_positions, d_ids, d_lines, cap, stream);
+            if (sb.carry) launch_find_carry(sb.fb, f.fd, sb.carry, stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(fs.ev[3], stream));
+            return GZPX_OK;
+        }));
+    HIP_TRY(hipMemcpyAsync(f.h_rec, f.fd.rec, kFdRecWords * 8, hipMemcpyDeviceToHost, stream));
+    if (d_counts) HIP_TRY(hipMemcpyAsync(d_counts, fs.d_counts, (size_t)sh.K * 8, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    *n_hits = f.h_rec[kFdRecHits];
+    return writes && *n_hits > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
+}
+
+int gzpx_dctx_last_find_set_ms(gzpx_dctx *ctx, float ms[3]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    for (int j = 0; j < 3; j++) ms[j] = ctx->find_set.ms[j];
+    return GZPX_OK;
+}
+
+int gzpx_select_lines_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                                 const void *patterns, const uint32_t *pattern_offsets, size_t n_patterns, uint64_t group,
+                                 unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_records,
+                                 uint64_t *n_hits, gzpx_check_info *info, void *hip_stream) {
+    if (!c || !ix || !lt || !n_runs || !n_records || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_runs = *n_records = 0;
+    if (n_hits) *n_hits = 0;
+    SetShape sh;
+    if (group == 0 || (flags & ~GZPX_SELECT_INVERT) || !findset_shape(patterns, pattern_offsets, n_patterns, sh))
+        return GZPX_ERR_INVALID_ARG;
+    if (!lines_match(c, ix, lt, in_len)) return GZPX_ERR_INVALID_ARG;
+    const uint64_t L = lt->n_lines, total = ix->inflated_len;
+    const uint64_t R = L / group + (L % group ? 1u : 0u);
+    if (R > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    const int invert = (flags & GZPX_SELECT_INVERT) ? 1 : 0;
+    const uint64_t cap = d_runs ? runs_cap : 0;
+    std::unique_lock<std::mutex> lk(c->mu);
+    SelectState &s = c->select;
+    FindState &f = c->find;
+    FindSetState &fs = c->find_set;
+    s.ms[0] = s.ms[1] = s.ms[2] = 0.0f;
+    if (L == 0) return GZPX_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    hipStream_t stream = c->stream;
+    if (sh.shortest > total) {  // no position can hold a pattern: nothing is inflated, and every record is one run under INVERT
+        if (!invert) return GZPX_OK;
+        *n_runs = 1;
+        *n_records = R;
+        if (!d_runs) return GZPX_OK;
+        if (!cap) return GZPX_ERR_INSUFFICIENT_SPACE;
+        GZPX_TRY(s.reserve(1));
+        GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+        Drain drain{{stream}, 1};
+        s.h_run[0] = 0;
+        s.h_run[1] = L;
+        HIP_TRY(hipMemcpyAsync(d_runs, s.h_run, 16, hipMemcpyHostToDevice, stream));
+        return GZPX_OK;  // (the drain synchronises)
+    }
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    Drain drain{{stream}, 1};
+    Batches b;
+    GZPX_TRY(batches_of(c, ix, b));
+    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
+    GZPX_TRY(fs.reserve());
+    GZPX_TRY(s.reserve(R));
+    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+    GZPX_TRY(findset_begin(c, patterns, pattern_offsets, sh));
+    HIP_TRY(hipMemsetAsync(s.sl.bitmap, 0, (size_t)((R + 31) / 32 * 4), stream));
+    GZPX_TRY(batched_pass(
+        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, s.ev, 2, s.ms, info, drain,
+        [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
+            const SetBatch sb = findset_batch(c->stage.d, base, bytes, is_last, sh.longest, (int)lt->delim);
+            HIP_TRY(hipEventRecord(s.ev[1], stream));
+            if (sb.search) {
+                launch_findset_count(sb.fb, f.fd, fs.d_set, fs.d_counts, stream);
+                launch_findset_mark(sb.fb, f.fd, fs.d_set, s.sl, group, R, stream);
+            }
+            if (sb.carry) launch_find_carry(sb.fb, f.fd, sb.carry, stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(s.ev[2], stream));
+            return GZPX_OK;
+        }));
+    HIP_TRY(hipEventRecord(s.ev[3], stream));
+    launch_select_runs(s.sl, f.fd, R, group, L, invert, (uint64_t *)d_runs, cap, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s.ev[4], stream));
+    HIP_TRY(hipMemcpyAsync(s.h_rec, s.sl.rec, kSlRecWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    if (hipEventElapsedTime(&s.ms[2], s.ev[3], s.ev[4]) != hipSuccess) s.ms[2] = 0.0f;
+    *n_runs = s.h_rec[kSlRecRuns];
+    *n_records = s.h_rec[kSlRecRecords];
+    if (n_hits) *n_hits = s.h_rec[kSlRecHits];
+    return d_runs && *n_runs > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
 }
 
 int gzpx_dctx_set_lines_batch(gzpx_dctx *ctx, size_t inflated_bytes) {

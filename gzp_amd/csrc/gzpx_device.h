@@ -383,6 +383,36 @@ void launch_select_mark(const FindBatch &b, const FindScratch &f, const SelectSc
 void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n_records, uint64_t group, uint64_t n_lines,
                         int invert, uint64_t *d_runs, uint64_t cap, hipStream_t stream);
 
+// Search for a set of patterns (gzpx_findset.h).  The host compiles the set into an FsSet, the form the kernels stage
+// into LDS: q = min(shortest pattern, 4); the WINDOW of a pattern is its first q bytes as a little-endian number.
+constexpr uint32_t kFsMaxPatterns = 256;  // GZPX_FINDSET_MAX_PATTERNS
+constexpr uint32_t kFsMaxBytes = 16384;   // GZPX_FINDSET_MAX_BYTES
+constexpr uint32_t kFsBitmapWords = 2048;  // 2^16 bits
+constexpr uint32_t kFsByteWords = (kFsMaxBytes + 3u * kFsMaxPatterns) / 4u;  // every pattern starts on a dword
+enum { kFsHdrK = 0, kFsHdrQ = 1, kFsHdrM = 2, kFsHdrGrams = 3, kFsHdrBitmapWords = 4, kFsHdrByteWords = 5, kFsHdrWords = 8 };
+struct alignas(16) FsSet {
+    uint32_t hdr[kFsHdrWords];        // patterns, q, the longest pattern, distinct windows, words in use of bitmap and bytes
+    uint32_t bitmap[kFsBitmapWords];  // bit fs_gram_index(window): some pattern starts with it (q = 1: 8 words in use)
+    uint32_t keys[kFsMaxPatterns];    // the distinct windows, ascending
+    uint32_t bstart[kFsMaxPatterns + 4u];  // bucket g = ids[bstart[g] .. bstart[g + 1]): the patterns of window keys[g]
+    uint32_t ids[kFsMaxPatterns];     // ... ids ascending inside a bucket
+    uint32_t meta[kFsMaxPatterns];    // of pattern k: (its first word in bytes) << 16 | its length
+    uint32_t bytes[kFsByteWords];     // the patterns, each padded with zeros to a whole dword
+};
+static_assert(sizeof(FsSet) % 16u == 0, "staged as 16-byte words");
+// where the filter keeps the bit of a window of q bytes
+constexpr uint32_t fs_gram_index(uint32_t window, uint32_t q) { return q <= 2u ? window : (window * 0x9E3779B1u) >> 16; }
+// The set's passes over one batch, behind its inflate.  b.m says which starts the batch owns: the longest pattern for
+// a batch that is not the last, 1 for the last (gzpx_findset.h).  f.cnt / f.bases / f.rec are the search's.
+// count + scan (k_fd_scan): d_counts[k] += the hits of pattern k
+void launch_findset_count(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_counts, hipStream_t stream);
+// behind it: the batch's hits below rank `cap` into d_positions / d_ids / d_lines (each may be null)
+void launch_findset_write(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_positions, uint32_t *d_ids,
+                          uint64_t *d_lines, uint64_t cap, hipStream_t stream);
+// behind launch_findset_count of a batch with a delimiter: the records of the batch's hits into s.bitmap
+void launch_findset_mark(const FindBatch &b, const FindScratch &f, const FsSet *d_set, const SelectScratch &s, uint64_t group,
+                         uint64_t n_records, hipStream_t stream);
+
 // gzpx_wrap.h (k_adler32_tiles): (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);
 

@@ -5521,6 +5521,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_lines.h"
 #include "gzpx_find.h"
 #include "gzpx_select.h"
+#include "gzpx_findset.h"
 #include "gzpx_wrap.h"
 #include "gzpx_cksum.h"
 
@@ -6060,6 +6061,30 @@ void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n
     if (d_runs && cap)
         hipLaunchKernelGGL(k_sl_runs_write, dim3(groups), dim3(kSlRunThreads), 0, stream, bits, n_records, inv,
                            (const uint32_t *)s.cnt, (const uint32_t *)s.bases, group, n_lines, d_runs, cap);
+}
+
+// The search for a set (gzpx_findset.h): the single-pattern search's region, pieces, scan and scratch.
+void launch_findset_count(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_counts, hipStream_t stream) {
+    uint32_t x0, grid;
+    const FdArgs a = find_args(b, x0, grid);
+    hipLaunchKernelGGL(k_fs_count, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, d_set, f.cnt, (unsigned long long *)d_counts);
+    hipLaunchKernelGGL(k_fd_scan, dim3(1), dim3(kFdThreads), 0, stream, (const uint32_t *)f.cnt, grid, f.bases, f.rec);
+}
+
+void launch_findset_write(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_positions, uint32_t *d_ids,
+                          uint64_t *d_lines, uint64_t cap, hipStream_t stream) {
+    uint32_t x0, grid;
+    const FdArgs a = find_args(b, x0, grid);
+    hipLaunchKernelGGL(k_fs_write, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, d_set, (const uint32_t *)f.cnt,
+                       (const uint64_t *)f.bases, d_positions, d_ids, d_lines, cap);
+}
+
+void launch_findset_mark(const FindBatch &b, const FindScratch &f, const FsSet *d_set, const SelectScratch &s, uint64_t group,
+                         uint64_t n_records, hipStream_t stream) {
+    uint32_t x0, grid;
+    const FdArgs a = find_args(b, x0, grid);
+    hipLaunchKernelGGL(k_fs_mark, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, d_set, (const uint32_t *)f.cnt,
+                       (const uint64_t *)f.bases, s.bitmap, group, n_records);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

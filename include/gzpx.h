@@ -517,6 +517,59 @@ int gzpx_read_lines_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gz
                                  size_t in_len, const gzpx_range *d_line_ranges, size_t n_ranges, void *d_out, size_t out_cap,
                                  size_t *out_len, uint64_t *d_out_offsets, gzpx_range *d_byte_ranges, size_t *bad_range,
                                  gzpx_check_info *info, void *hip_stream);
+/* ---- search for a SET of byte strings (gzpx_findset.h): grep -F -e A -e B -f list on a device-resident BGZF / Mgzip
+ * stream -- the VCF rows of a handful of contigs, the FASTQ records that carry any of 96 barcodes, the log lines with
+ * any of a list of error codes -- in ONE inflate and one pass over it, the hits of all patterns already merged by
+ * position.  gzpx_find_device and gzpx_select_lines_device are untouched by it.
+ * Definitions.  `plain`, n, `delim` and the LINE of a hit are exactly as for gzpx_find_device.  The set is a HOST
+ *   array: pattern k is patterns[pattern_offsets[k] .. pattern_offsets[k + 1]), m_k bytes; there are n_patterns + 1
+ *   offsets, non-decreasing; pattern_offsets[0] may be non-zero.  1 <= n_patterns <= GZPX_FINDSET_MAX_PATTERNS;
+ *   1 <= m_k <= GZPX_FIND_MAX_PATTERN for every k; the sum of the lengths, pattern_offsets[n_patterns] -
+ *   pattern_offsets[0], is at most GZPX_FINDSET_MAX_BYTES.  Bytes may have any value; patterns may be equal to,
+ *   prefixes of, or contained in one another.  A violation of any of these rules (a NULL array, an empty or too long
+ *   pattern, offsets that decrease, too many patterns or bytes) is GZPX_ERR_INVALID_ARG with nothing inflated and
+ *   nothing written.
+ *   A HIT is a pair (p, k) with plain[p .. p + m_k) == pattern k, 0 <= p <= n - m_k: gzpx_find_device's rule for every
+ *   pattern.  Equal patterns each hit under their own id.  Hits are reported in ascending p and, at equal p, in
+ *   ascending k -- the order a stable merge by position of the results of n_patterns calls of gzpx_find_device gives,
+ *   so the result is reproducible bit for bit and d_ids can be cut by position.
+ * gzpx_find_set_device.  d_positions (uint64), d_ids (uint32) and d_lines (uint64) are DEVICE arrays of hits_cap
+ *   entries, each optional: entry r describes hit r.  All three NULL: count only, hits_cap is ignored, GZPX_OK.
+ *   *n_hits is always the number of hits of all patterns in the whole stream.  When it exceeds hits_cap and an output
+ *   array was given, the first hits_cap hits are written, nothing behind hits_cap entries is touched and the call
+ *   returns GZPX_ERR_INSUFFICIENT_SPACE.  delim outside -1..255, or GZPX_FIND_NO_LINES with d_lines given:
+ *   GZPX_ERR_INVALID_ARG.
+ *   d_counts is an optional DEVICE array of n_patterns uint64: entry k is the number of hits of pattern k in the whole
+ *   stream, whatever hits_cap is, in count-only calls too.  Whenever the call returns GZPX_OK or
+ *   GZPX_ERR_INSUFFICIENT_SPACE the entries sum to *n_hits -- also when nothing is inflated, where all are zero.
+ *   An index of 0 members, or every m_k > n: GZPX_OK, 0 hits, nothing inflated.  A set in which only some patterns are
+ *   longer than the stream is searched for the others.
+ *   Every member is inflated once per call, in the batches of gzpx_dctx_set_lines_batch.  Hits are owned by the batch
+ *   in which they START: a batch that is not the last reports the starts p with p + M <= the end of what it holds,
+ *   M = the longest pattern, and keeps its last M - 1 bytes in front of the next batch; the last batch -- also an empty
+ *   one, such as the BGZF EOF member at a batch size of 1 -- reports every start that is left.  That keeps the order
+ *   above across batches for patterns of different lengths.
+ *   Index and context checks, the context's lock, the slot, hip_stream, "returns synchronised" and the report of a
+ *   failing member are gzpx_find_device's: the inflate's error, info->block = the member's index in the stream,
+ *   *n_hits = 0, and the output arrays, d_counts included, hold nothing of use.
+ * gzpx_dctx_last_find_set_ms: HIP-event durations of the last gzpx_find_set_device, summed over its batches:
+ *   [0] inflate, [1] counting pass + scan, [2] writing pass + carry.
+ * gzpx_select_lines_set_device is gzpx_select_lines_device with "a hit" meaning a hit of any pattern of the set:
+ *   definitions, `group`, GZPX_SELECT_INVERT, runs, runs_cap, errors and the report of a failing member are unchanged;
+ *   *n_hits (optional) is the set's total as above; the rules of the set are those above, a violation is
+ *   GZPX_ERR_INVALID_ARG.  Every m_k > n: nothing is inflated; 0 runs, with INVERT the one run {0, L}.  The table feeds
+ *   gzpx_read_lines_table_device as it is; the timings are read with gzpx_dctx_last_select_ms. */
+#define GZPX_FINDSET_MAX_PATTERNS 256
+#define GZPX_FINDSET_MAX_BYTES 16384 /* sum of the patterns' lengths */
+int gzpx_find_set_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *patterns,
+                         const uint32_t *pattern_offsets, size_t n_patterns, int delim, uint64_t *d_positions, uint32_t *d_ids,
+                         uint64_t *d_lines, size_t hits_cap, uint64_t *d_counts, uint64_t *n_hits, gzpx_check_info *info,
+                         void *hip_stream);
+int gzpx_dctx_last_find_set_ms(gzpx_dctx *ctx, float ms[3]);
+int gzpx_select_lines_set_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in,
+                                 size_t in_len, const void *patterns, const uint32_t *pattern_offsets, size_t n_patterns,
+                                 uint64_t group, unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs,
+                                 uint64_t *n_records, uint64_t *n_hits, gzpx_check_info *info, void *hip_stream);
 /* ---- batches of independent DEFLATE members that this library did not write (gzpx_wrap.h): GZIP pages of Parquet,
  * zlib chunks of HDF5 / Zarr / ORC, PNG IDAT streams, members of a multi-member gzip file whose extents are known.
  * The counterpart of libdeflate_deflate_decompress / libdeflate_zlib_decompress / libdeflate_gzip_decompress for a

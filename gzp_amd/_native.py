@@ -40,6 +40,9 @@ COMPAT_1_10 = 1
 STREAM_NONE = ctypes.c_void_p(-1).value  # GZPX_STREAM_NONE: the caller has synchronized, no stream dependency
 N_STAGES = 9
 INFLATE_SEG, INFLATE_WAVE = 0, 1
+# GZPX_HANDBACK_*: why the decode / copy pair handed a member to k_inflate (DContext.debug_handback)
+(HANDBACK_NONE, HANDBACK_HEADER, HANDBACK_STORED, HANDBACK_NO_EOB, HANDBACK_RESYNC, HANDBACK_SPAN_SYMBOL, HANDBACK_SPAN_OVERRUN,
+ HANDBACK_DISTANCE, HANDBACK_OFFSET_SYMBOL, HANDBACK_CODEWORD, HANDBACK_COUNT_MISMATCH, HANDBACK_FINAL, HANDBACK_LZCOPY) = range(13)
 RANGE_UNCOMPRESSED, RANGE_VIRTUAL = 0, 1
 WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # inflate_batch_device: RFC 1951 / 1950 / 1952
 BATCH_SHORT_OK = 1
@@ -68,7 +71,7 @@ EXPORTS = [
     "gzpx_decompress_blocks_wait", "gzpx_alloc_decompressor", "gzpx_deflate_decompress",
     "gzpx_free_decompressor", "gzpx_pard_create", "gzpx_pard_read", "gzpx_pard_fill_buf", "gzpx_pard_consume", "gzpx_pard_destroy",
     "gzpx_pard_last_error", "gzpx_host_alloc", "gzpx_host_free", "gzpx_dctx_last_inflate_ms",
-    "gzpx_debug_inflate", "gzpx_dctx_last_inflate_stage_ms", "gzpx_dctx_set_route", "gzpx_dctx_last_redo_count", "gzpx_synth_fastq_device", "gzpx_synth_ascii_device",
+    "gzpx_debug_inflate", "gzpx_debug_inflate_handback", "gzpx_dctx_last_inflate_stage_ms", "gzpx_dctx_set_route", "gzpx_dctx_last_redo_count", "gzpx_synth_fastq_device", "gzpx_synth_ascii_device",
     "gzpx_ctx_active_compat", "gzpx_build_id", "gzpx_multi_create", "gzpx_multi_destroy", "gzpx_multi_devices", "gzpx_multi_compress_slab",
     "gzpx_multi_shard", "gzpx_multi_compress_slab_device", "gzpx_debug_snap",
     "gzpx_scan_blocks_device", "gzpx_decompress_stream_device", "gzpx_index_device", "gzpx_dctx_last_scan_ms",
@@ -332,6 +335,8 @@ class GzpxLib:
         L.gzpx_dctx_last_inflate_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_debug_inflate.restype = i32
         L.gzpx_debug_inflate.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint64)]
+        L.gzpx_debug_inflate_handback.restype = i32
+        L.gzpx_debug_inflate_handback.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
         L.gzpx_debug_snap.restype = i32
         L.gzpx_debug_snap.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint64)]
         L.gzpx_crc32_combine.restype = ctypes.c_uint32
@@ -847,6 +852,13 @@ class DContext:
         c = (ctypes.c_uint64 * 8)()
         self.lib.check(self.lib.L.gzpx_debug_inflate(self.h, int(enable), c))
         return list(c)
+
+    def debug_handback(self, n):
+        """HANDBACK_* of members 0 .. n - 1 of the last launch, made under debug_inflate(1): why the decode / copy pair
+        handed each to k_inflate, HANDBACK_NONE for a member it decoded."""
+        r = (ctypes.c_uint32 * max(n, 1))()
+        self.lib.check(self.lib.L.gzpx_debug_inflate_handback(self.h, r, n))
+        return list(r)[:n]
 
     def decompress_device(self, d_in_ptr, in_len, offsets, sizes, d_out_ptr, out_cap, stream=None):
         out_len = ctypes.c_size_t(0)

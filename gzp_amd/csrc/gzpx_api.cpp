@@ -1365,6 +1365,7 @@ struct DSlot : NoCopy {
     Allocs mlist_mem, tfirst_mem;  // sc.mlist, sc.tfirst
     size_t nb = 0;
     int route = kInflateRouteSeg;  // the route of the slot's last launch (the context's may have changed since)
+    int debug = 0;                 // ... and what gzpx_debug_inflate had selected for it
 };
 
 int dslot_reserve(DSlot &c, size_t nb) {
@@ -1385,7 +1386,7 @@ int dslot_reserve(DSlot &c, size_t nb) {
         GZPX_TRY(t.dev(c.d_sizes, cap * 4));
         GZPX_TRY(t.dev(c.d_crc, cap * 4));
         GZPX_TRY(t.dev(c.d_blk, cap * sizeof(DBlockHost)));
-        GZPX_TRY(t.dev(c.sc.redo, (cap + 2) * 4));
+        GZPX_TRY(t.dev(c.sc.redo, (2 * cap + 2) * 4));  // (list, ticket counter, and a debug launch's reasons)
         GZPX_TRY(t.pinned(c.h_blk, cap * sizeof(DBlockHost)));
         GZPX_TRY(t.pinned(c.h_crc, cap * 4));
         GZPX_TRY(t.pinned(c.h_offsets, cap * 8));
@@ -1664,6 +1665,7 @@ int dslot_seg_scratch(DSlot &sl, size_t out_cap, size_t nb) {
 int dslot_prepare(gzpx_dctx *c, DSlot &sl, size_t nb, int route, size_t cap, uint64_t in_bytes, bool writes = true) {
     sl.nb = nb;
     sl.route = route;
+    sl.debug = c->debug;
     sl.have_blk = sl.have_check = false;
     sl.sc.n_cu = c->n_cu;
     sl.sc.in_bytes = in_bytes;
@@ -3457,6 +3459,35 @@ int gzpx_debug_inflate(gzpx_dctx *ctx, int enable, uint64_t sums[8]) {
             for (size_t b = 0; b < ctx->last_nb; b++)
                 for (int k = 0; k < 8; k++) sums[k] += ctx->slots[ctx->last_slot].h_blk[b].cyc[k];
     }
+    return GZPX_OK;
+}
+
+static_assert(kHbNone == GZPX_HANDBACK_NONE && kHbHeader == GZPX_HANDBACK_HEADER && kHbStored == GZPX_HANDBACK_STORED &&
+                  kHbNoEob == GZPX_HANDBACK_NO_EOB && kHbResync == GZPX_HANDBACK_RESYNC && kHbSpanSymbol == GZPX_HANDBACK_SPAN_SYMBOL &&
+                  kHbSpanOverrun == GZPX_HANDBACK_SPAN_OVERRUN && kHbDistance == GZPX_HANDBACK_DISTANCE &&
+                  kHbOffsetSymbol == GZPX_HANDBACK_OFFSET_SYMBOL && kHbCodeword == GZPX_HANDBACK_CODEWORD &&
+                  kHbCountMismatch == GZPX_HANDBACK_COUNT_MISMATCH && kHbFinal == GZPX_HANDBACK_FINAL &&
+                  kHbLzcopy == GZPX_HANDBACK_LZCOPY, "the kernels' reasons are the header's");
+int gzpx_debug_inflate_handback(gzpx_dctx *ctx, uint32_t *reasons, size_t n) {
+    if (!ctx || (n && !reasons)) return GZPX_ERR_INVALID_ARG;
+    for (size_t b = 0; b < n; b++) reasons[b] = GZPX_HANDBACK_NONE;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (ctx->last_slot < 0 || !ctx->last_nb) return GZPX_OK;
+    const DSlot &sl = ctx->slots[ctx->last_slot];
+    if (!sl.debug || !sl.sc.redo || sl.route != kInflateRouteSeg) return GZPX_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const size_t nb = sl.nb;  // (the launch's own count: it says where the reasons lie)
+    if (!nb || nb > sl.cap_blocks) return GZPX_OK;
+    std::vector<uint32_t> h(2 + 2 * nb);
+    if (hipMemcpy(h.data(), sl.sc.redo, h.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return GZPX_ERR_DEVICE;
+    const uint32_t *why = h.data() + 2 + nb;
+    for (size_t b = 0; b < n && b < nb; b++) reasons[b] = why[b];
+    // k_lzcopy carries no instrumentation under enable 1: a member on the list that k_inflate_seg did not put there is its
+    if (sl.debug == 1)
+        for (size_t i = 0; i < h[0] && i < nb; i++) {
+            const uint32_t b = h[1 + i];
+            if (b < n && b < nb && why[b] == kHbNone) reasons[b] = kHbLzcopy;
+        }
     return GZPX_OK;
 }
 

@@ -190,12 +190,31 @@ struct DBlockHost {
 };
 // DBlockHost.status of a member that was inflated (kInfShortOutput: fewer bytes than its ISIZE)
 enum InflateStatus : uint32_t { kInfOk = 0, kInfBadData = 1, kInfInsufficientSpace = 2, kInfShortOutput = 3 };
+// Why the decode / copy pair handed a member to k_inflate (gzpx_inflate_seg.h): recorded per member by the debug
+// instances of k_inflate_seg and k_lzcopy only, read back by gzpx_debug_inflate_handback (GZPX_HANDBACK_*).
+enum InflateHandback : uint32_t {
+    kHbNone = 0,           // the pair decoded the member (or never looked at it: ISIZE 0, no room in the output)
+    kHbHeader = 1,         // seg_header refused the block header: block type 3, the shape of a code, the header's runs,
+                           // no end-of-block code, stored LEN / NLEN, or the payload ends inside the header
+    kHbStored = 2,         // a stored block reaches past the payload or past ISIZE
+    kHbNoEob = 3,          // the payload ends and the block has not
+    kHbResync = 4,         // pass 2 took more than kSegMaxFix iterations
+    kHbSpanSymbol = 5,     // the span's true path stops at something that is no end-of-block code
+    kHbSpanOverrun = 6,    // the span's output overruns ISIZE, or its exit lies behind the payload
+    kHbDistance = 7,       // pass 3: a distance reaches in front of the output's start
+    kHbOffsetSymbol = 8,   // pass 3: an invalid offset codeword behind a length
+    kHbCodeword = 9,       // pass 3: an invalid litlen codeword (litlen 286 and 287 are among them)
+    kHbCountMismatch = 10, // pass 3, count-only: the walk from the true entry disagrees with pass 2
+    kHbFinal = 11,         // behind the final block: fewer bytes than ISIZE, or the stream ends behind the payload
+    kHbLzcopy = 12,        // k_lzcopy gave up (its polling loop ran out of spins)
+};
 // Scratch of the two-kernel inflate (gzpx_inflate_seg.h): the members' match records, the first record of every
 // 32 KiB output tile, and the list of members handed back to k_inflate ([0] = how many).
 struct InflateScratch {
     void *mlist = nullptr;       // inflate_mlist_bytes(out_cap, nb)
     uint32_t *tfirst = nullptr;  // inflate_tfirst_bytes(out_cap, nb)
-    uint32_t *redo = nullptr;    // [1 + nb] the list, [1 + nb] behind it k_inflate_seg's ticket counter
+    uint32_t *redo = nullptr;    // [1 + nb] the list, [1 + nb] behind it k_inflate_seg's ticket counter, [2 + nb + b]
+                                 // member b's InflateHandback (debug launches; room for 2 + 2 nb words)
     uint32_t *summary = nullptr; // [kDsWords] the launch record below
     int n_cu = 0;                // compute units of the device (the size of the persistent launch)
     uint64_t in_bytes = 0;       // compressed bytes that stand for the members' total: launch_inflate_members takes their

@@ -423,6 +423,15 @@ __device__ __attribute__((noinline)) void seg_header(InfSegLds &h, uint16_t *cwt
     wave_sync();
 }
 
+// An InflateHandback in the debug instances, nothing at all in the others (not even a dead variable: the production
+// instances are held to the machine code they had before reasons were recorded)
+template <bool DBG>
+struct SegWhy {
+    uint32_t v = kHbNone;
+};
+template <>
+struct SegWhy<false> {};
+
 // DBlock.cyc of a debug launch (wave 0's clocks): [0] whole member, [1] headers + tables, [2] pass 1, [3] pass 2,
 // [4] pass 3, counts [5] spans, [6] pass-2 iterations, [7] symbol steps of passes 1 and 3 (wave iterations)
 //
@@ -484,7 +493,10 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
 
     uint32_t bp = bit0, o = 0, mtot = 0, prev_blk_bits = 0;  // (prev_blk_bits: the symbols of the block before, in bits)
     bool final_block = false, bad = false;
-#define SEG_BAD() do { bad = true; } while (0)  // (the member goes to k_inflate)
+    // debug launches: which of the checks below handed the member back; the first thing this lane's pass 3 tripped over
+    // (declared here and not beside bad_dist: even an empty object there changed the production instances' registers)
+    SegWhy<DBG> why, why3;
+#define SEG_BAD(reason) do { bad = true; if constexpr (DBG) why.v = (reason); } while (0)  // (the member goes to k_inflate)
     while (!final_block && !bad) {
         bp = uniform(bp);
         o = uniform(o);
@@ -497,13 +509,14 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
         final_block = uniform(hh.hres[1]) != 0;
         const uint32_t btype = uniform(hh.hres[2]);
         bp = uniform(hh.hres[3]);
+        if constexpr (DBG) if (bad) why.v = kHbHeader;
         if (bad) break;
         if (btype == 0) {
             // stored: raw bytes straight from the payload to their place (final bytes, like literals)
             const uint32_t len = uniform(hh.hres[4]);
             const uint32_t src = (bp - bit0) >> 3;
             if (src + len > pay_len || over(o, len)) {
-                SEG_BAD();
+                SEG_BAD(kHbStored);
                 break;
             }
             if constexpr (COUNT) {
@@ -565,7 +578,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
             o = uniform(o);
             mtot = uniform(mtot);
             if (bp >= bit_end) {  // no end-of-block code before the payload's end
-                SEG_BAD();
+                SEG_BAD(kHbNoEob);
                 break;
             }
             if (DBG) dbg[5]++;
@@ -648,7 +661,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
                 const bool need = has_data && new_entry != entry && new_entry >= my_start;
                 if (W > 1 ? __syncthreads_or(need ? 1 : 0) == 0 : __ballot(need) == 0) break;
                 if (++iters > kSegMaxFix) {
-                    SEG_BAD();
+                    SEG_BAD(kHbResync);
                     break;
                 }
                 // both replays run in the lane's relative coordinates, window by window like pass 1
@@ -771,7 +784,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
             const bool live = wave < stop_wave || (wave == stop_wave && lane <= first_stop);
             if (stop_wave < (uint32_t)W) {
                 if (stop_fl != 1u) {  // an invalid symbol on the true path
-                    SEG_BAD();
+                    SEG_BAD(kHbSpanSymbol);
                     break;
                 }
                 eob = true;
@@ -800,12 +813,13 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
             }
             const uint32_t new_bp = stop_ex;
             if (over(o, tot_n) || new_bp > bit_end + (eob ? 0u : 64u)) {
-                SEG_BAD();
+                SEG_BAD(kHbSpanOverrun);
                 break;
             }
             // ---- pass 3: the segment again from its true entry, now writing
             const long long t_p3 = DBG ? clock64() : 0;
             bool bad_dist = false;
+            if constexpr (DBG) why3.v = kHbNone;
             {
                 uint32_t pos = o + in_n - my_n, mi = mtot + in_m - my_m;
                 uint32_t f3 = live ? 0u : 2u;
@@ -833,6 +847,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
                                 }
                             } else if (y.e & kSegLen) {
                                 if (y.dist > pos || y.obad) bad_dist = true;
+                                if constexpr (DBG) if (why3.v == kHbNone) why3.v = y.obad ? kHbOffsetSymbol : y.dist > pos ? kHbDistance : kHbNone;
                                 if constexpr (!COUNT) {
                                     LzMatch rec;
                                     rec.pos = pos;
@@ -842,6 +857,7 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
                                 }
                             } else if (!(y.e & kSegEob)) {
                                 bad_dist = true;  // an invalid codeword on the true path
+                                if constexpr (DBG) if (why3.v == kHbNone) why3.v = kHbCodeword;
                             }
                             const uint32_t np = pos + y.outlen;
                             if (multi && ((pos ^ np) >> kLzTileShift)) tf[np >> kLzTileShift] = mi;  // the next record is the tile's first
@@ -861,11 +877,25 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
                 // where it ended is held against what pass 2 said of the lane -- entries chain from exit to exit, so a
                 // span that passes has been decoded symbol by symbol from its first bit to its last)
                 if constexpr (COUNT)
-                    if (live && (pos != o + in_n || rel0 + rp != ex)) bad_dist = true;
+                    if (live && (pos != o + in_n || rel0 + rp != ex)) {
+                        bad_dist = true;
+                        if constexpr (DBG) if (why3.v == kHbNone) why3.v = kHbCountMismatch;
+                    }
             }
             if (DBG) dbg[4] += (uint32_t)(clock64() - t_p3);
             if (W > 1 ? __syncthreads_or(bad_dist ? 1 : 0) != 0 : __ballot(bad_dist) != 0) {
-                SEG_BAD();
+                SEG_BAD(kHbNone);
+                if constexpr (DBG) {  // the reason of the first lane of the span that has one: the earliest on the true path
+                    const uint64_t tripped = __ballot(why3.v != kHbNone);
+                    why.v = tripped ? rdlane(why3.v, (uint32_t)__ffsll((long long)tripped) - 1u) : (uint32_t)kHbNone;
+                    if (W > 1) {  // (x_fl is free: the span's stop was read in front of the prefix sum's barrier)
+                        if (lane == 0) hh.x_fl[wave] = why.v;
+                        __syncthreads();
+                        why.v = kHbNone;
+                        for (uint32_t w2 = 0; w2 < (uint32_t)W; w2++)
+                            if (why.v == kHbNone) why.v = hh.x_fl[w2];
+                    }
+                }
                 break;
             }
             o += tot_n;
@@ -879,9 +909,12 @@ __device__ __attribute__((noinline)) void seg_member(const uint32_t b, const uin
             __hip_atomic_store(hint_p, pm < 1u ? 1u : pm > 1000u ? 1000u : pm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (!bad && ((!COUNT && o != isize) || bp > bit_end)) SEG_BAD();
+    if (!bad && ((!COUNT && o != isize) || bp > bit_end)) SEG_BAD(kHbFinal);
     if (bad) {
         seg_redo(blk, redo, b, tid);
+        // (debug launches: a member that waits for k_inflate has produced nothing, and k_inflate sets the field -- until
+        // then it holds the reason, for k_seg_reasons)
+        if constexpr (DBG) if (tid == 0) blk->produced = why.v;
     } else if (tid == 0) {
         blk->status = kInfOk;
         blk->produced = o;
@@ -916,7 +949,18 @@ __global__ __launch_bounds__(64 * W, GZPX_SEG_WAVES) void k_inflate_seg(const ui
         if (b >= nb) break;
         wave_sync();
         seg_member<DBG, W, COUNT>(b, tid, in_all, blk_all, out_off, out_all, out_cap, mlist_all, tfirst_all, redo, hint_p);
+        // (nothing divergent may follow the call inside this loop, in no instance: a branch of thread 0's alone here
+        // let the compiler send the other 63 lanes round the loop again without it -- k_seg_reasons is a kernel for that)
     }
+}
+
+// Debug launches, between k_inflate_seg and k_lzcopy: the reasons get an array of their own behind the redo list and the
+// ticket counter (redo[2 + nb + b]), because the debug instances of k_lzcopy and k_inflate write DBlock.cyc[] and k_inflate
+// the rest of the record.  from_seg: k_inflate_seg was the instrumented one and left its reason in DBlock.produced of
+// every member it handed back; otherwise nobody has a reason yet (k_lzcopy's instrumented instance may add its own).
+__global__ __launch_bounds__(256) void k_seg_reasons(const DBlock *__restrict__ blk, uint32_t *__restrict__ redo, uint32_t nb, uint32_t from_seg) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nb) redo[2 + nb + b] = from_seg && blk[b].status == kInfRedo ? blk[b].produced : (uint32_t)kHbNone;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1350,6 +1394,7 @@ __global__ __launch_bounds__(kLcThreads, GZPX_LC_WAVES) void k_lzcopy(DBlock *__
     }
     if (give_up) {
         seg_redo(blk, redo, b, tid);
+        if (DBG && tid == 0) redo[2 + gridDim.x + b] = kHbLzcopy;  // (one workgroup per member: the grid is nb)
     } else if (tid == 0) {  // (thread 0 wrote crc_total last: its own program order)
         crc_found[b] = l.crc_total;
         blk->nmatch = nmatch | kLcCrcDone;

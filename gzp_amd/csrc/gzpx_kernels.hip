@@ -5772,6 +5772,8 @@ static void launch_inflate_members_as(const uint8_t *d_in, uint32_t nb, DBlock *
         hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegSmallW>), dim3(sl.grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
                            (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, sl.hint);
     if (ev_mid) (void)hipEventRecord(ev_mid, stream);
+    if (SEG_DBG || LC_DBG)  // (a debug launch: why each member was handed back, InflateHandback)
+        hipLaunchKernelGGL(k_seg_reasons, dim3((nb + 255) / 256), dim3(256), 0, stream, (const DBlock *)blk, sc.redo, nb, SEG_DBG ? 1u : 0u);
     hipLaunchKernelGGL((k_lzcopy<LC_DBG>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off, d_out,
                        (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
     hipLaunchKernelGGL((k_inflate<INF_DBG>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)d_out_off, d_out,
@@ -5861,6 +5863,7 @@ static void launch_inflate_sizes_as(const uint8_t *d_in, uint32_t nb, DBlock *bl
                            (const uint64_t *)nullptr, (uint8_t *)nullptr, 0ull, (LzMatch *)nullptr, (uint32_t *)nullptr, sc.redo,
                            nb, sl.hint);
     if (ev_mid) (void)hipEventRecord(ev_mid, stream);
+    if (DBG) hipLaunchKernelGGL(k_seg_reasons, dim3((nb + 255) / 256), dim3(256), 0, stream, (const DBlock *)blk, sc.redo, nb, 1u);
     hipLaunchKernelGGL((k_inflate<DBG, true>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)nullptr,
                        (uint8_t *)nullptr, 0ull, (const uint32_t *)sc.redo);
 }

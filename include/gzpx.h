@@ -812,6 +812,26 @@ int gzpx_dctx_last_redo_count(gzpx_dctx *ctx, uint32_t *count);
  * progress, [7] matches.  GZPX_INFLATE_WAVE: [0] cycles, [1] headers + tables, [2] round set-up, [3] stores + copies,
  * [4] rounds, [5] literals, [6] matches, [7] flushes */
 int gzpx_debug_inflate(gzpx_dctx *ctx, int enable, uint64_t sums[8]);
+/* Why the decode / copy pair handed members of the last launch to k_inflate: reasons[b] for members b < n of it,
+ * GZPX_HANDBACK_NONE for a member the pair decoded (or never looked at: ISIZE 0) and for every member when the last
+ * launch was not an instrumented one on the GZPX_INFLATE_SEG route.  Only the instrumented kernels record a reason
+ * (gzpx_debug_inflate's enable 1: k_inflate_seg's, and GZPX_HANDBACK_LZCOPY for a member on the list that k_inflate_seg
+ * did not put there; enable 2: k_lzcopy's alone); the production kernels carry none of this.  Where several lanes of a
+ * span trip in pass 3, the reason is the first such lane's: the earliest on the true path. */
+#define GZPX_HANDBACK_NONE 0
+#define GZPX_HANDBACK_HEADER 1          /* block header refused: type 3, a code's shape, the header's runs, no end-of-block code, stored LEN / NLEN, payload ends inside it */
+#define GZPX_HANDBACK_STORED 2          /* a stored block reaches past the payload or past ISIZE */
+#define GZPX_HANDBACK_NO_EOB 3          /* the payload ends before the block does */
+#define GZPX_HANDBACK_RESYNC 4          /* the lanes did not re-synchronise within the iteration limit of pass 2 */
+#define GZPX_HANDBACK_SPAN_SYMBOL 5     /* the span's true path stops at something that is no end-of-block code */
+#define GZPX_HANDBACK_SPAN_OVERRUN 6    /* the span's output overruns ISIZE, or its exit lies behind the payload */
+#define GZPX_HANDBACK_DISTANCE 7        /* pass 3: a distance reaches in front of the output's start */
+#define GZPX_HANDBACK_OFFSET_SYMBOL 8   /* pass 3: an invalid offset codeword */
+#define GZPX_HANDBACK_CODEWORD 9        /* pass 3: an invalid litlen codeword (litlen symbols 286 and 287 among them) */
+#define GZPX_HANDBACK_COUNT_MISMATCH 10 /* pass 3 of the count-only form disagrees with pass 2 */
+#define GZPX_HANDBACK_FINAL 11          /* behind the final block: fewer bytes than ISIZE, or the stream ends behind the payload */
+#define GZPX_HANDBACK_LZCOPY 12         /* k_lzcopy gave up */
+int gzpx_debug_inflate_handback(gzpx_dctx *ctx, uint32_t *reasons, size_t n);
 
 const char *gzpx_strerror(int code);
 const char *gzpx_device_name(const gzpx_ctx *ctx);

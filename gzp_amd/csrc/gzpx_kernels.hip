@@ -84,6 +84,14 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 #define GZPX_PIN_VGPR(x) ((void)0)
 #endif
 
+// last statement of one arm of a branch whose arms end alike: keeps the compiler from sinking the like
+// tails into one copy behind the branch (which would turn this arm's immediate offsets into selected addresses)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GZPX_KEEP_ARM_APART() asm volatile("")
+#else
+#define GZPX_KEEP_ARM_APART() ((void)0)
+#endif
+
 __device__ __forceinline__ uint32_t lz_hash15(uint32_t v) { return (v * 0x1E35A7BDu) >> 17; }
 
 // little-endian u32 at an arbitrary byte address of global memory via two aligned loads
@@ -246,7 +254,14 @@ __global__ void k_init_meta(Config cfg, uint64_t slab_len, uint32_t nb, uint32_t
 // Output: cand[p] = d0 (u16, 0 = no live predecessor).
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kBuckets = 1u << 15;
-constexpr uint32_t kCandSteps = 16;  // steps per iteration; also the depth of the input prefetch
+// (measurement builds set another pair: python tools/build_variant.py w16s8 -DGZPX_CAND_STEPS=8)
+#ifndef GZPX_CAND_STEPS
+#define GZPX_CAND_STEPS 16
+#endif
+#ifndef GZPX_CAND_WAVES
+#define GZPX_CAND_WAVES 16
+#endif
+constexpr uint32_t kCandSteps = GZPX_CAND_STEPS;  // steps per iteration; also the depth of the input prefetch
 
 // aligned dword pair covering in[p .. p+3] (in32 = the block's bytes rounded down to a dword
 // boundary, mis = bytes skipped by that rounding).  Unconditional (index clamped to the block's
@@ -263,12 +278,18 @@ __device__ __forceinline__ uint2 cand_fetch(const uint32_t *__restrict__ in32, u
     return v;
 }
 
-// Waves per workgroup x steps per turn, measured on the 550 MiB slab (ms per launch, level 1):
-// 4 x 32: 1.00, 8 x 32: 0.74, 12 x 32: 0.84 (32 turns do not divide by 12), 16 x 8: 0.73, 16 x 16: 0.64.
-// The work AROUND the turn (loads, hashing, distance, stores) is what a block waits for, and it
-// spreads over the waves; 16 x 16 is what the 512 VGPRs of a SIMD lane allow (ring + address /
-// value / result of every step stay in registers).
-constexpr uint32_t kCandWaves = 16;  // four per SIMD; they take turns at the table
+// Waves per workgroup x steps per turn, measured on the 550 MiB slab (ms per launch, level 1, average
+// (min-max) of 12 launches under a kernel trace, with the scalar cursor and the interior body):
+//   16 x 8: 0.562 (0.556-0.569),  8 x 32: 0.532 (0.524-0.543),  16 x 16: 0.495 (0.490-0.504)  <- kept.
+// 16 x 20 needs 125 VGPRs in modes 0 and 1 and spills three dwords in modes 2 and 3; 16 x 24 spills in
+// every mode: neither was run.  (Before the scalar cursor, when the work around the turn was three
+// times as many VALU instructions: 4 x 32: 1.00, 8 x 32: 0.74, 12 x 32: 0.84, 16 x 8: 0.73, 16 x 16: 0.64,
+// and with the persistent workgroups 16 x 16: 0.54.)  The work AROUND the turn (loads, hashing,
+// distance, stores) spreads over the waves; the turn itself -- sixteen atomics and the hand-off of
+// the ticket -- is what a block waits for now, so a shorter turn (16 x 8) pays the hand-off twice as
+// often and fewer waves (8 x 32) leave the table idle while a wave hashes.  16 x 16 is what the 512
+// VGPRs of a SIMD lane allow (ring + address / value / result of every step stay in registers: 95).
+constexpr uint32_t kCandWaves = GZPX_CAND_WAVES;  // sixteen: four per SIMD; they take turns at the table
 
 // Which chain a candidate pass builds (MODE):
 //   0  level 1, ht_matchfinder: 15-bit hash of 4 bytes
@@ -363,7 +384,10 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_candidates(Config cfg,
     __shared__ uint32_t tab[kBuckets + 64];  // 128 KiB + one spare word per lane for lanes without a bucket
     __shared__ uint32_t turn;               // index of the iteration (counted through the blocks) whose atomics may go next
     __shared__ uint32_t bad_any;            // some wave saw the order check fail
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    // (read from lane 0, so that the compiler knows it as wave-uniform: the cursor below, settle, the block
+    // geometry and the loop branches are then scalar registers, scalar arithmetic and scalar branches)
+    const uint32_t wave = uniform(tid >> 6);
     constexpr uint32_t kIterPos = 64 * kCandSteps;
     auto block_len = [&](uint32_t blk) -> uint32_t {  // k_init_meta's cut
         const uint64_t begin = (uint64_t)blk * cfg.block_size;
@@ -410,53 +434,104 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_candidates(Config cfg,
         }
     };
     const bool force_safe = (cfg.debug & 1u) != 0;  // diagnostics: the fallback on every block, instead of the fast form
+    const bool clamp_all = (cfg.debug & 128u) != 0;  // diagnostics: every iteration through the clamped body (A/B timing)
+    // An iteration has two bodies.  The INTERIOR one has no clamps and no per-position tests; it is taken
+    // (wave-uniformly) when
+    //   * the iteration is not the block's first (position 0 is filed under bucket 0), and
+    //   * base0 + kIterPos + 16 <= n  (base0 = it * kIterPos, the iteration's first position).
+    // Then every position p <= base0 + kIterPos - 1 of the iteration is hashed (p + 5 <= n), and the reads stay
+    // inside the block's own bytes: the last dword touched is w + 1 with w = (base0 + kIterPos - 1 + mis) >> 2,
+    // counted from in - mis, so its last byte lies at 4 * (w + 1) + 3 - mis <= base0 + kIterPos + 6 from the
+    // block's first byte (the worst case is mis = 1), which is below n.  The first dword read starts at
+    // in - mis + base0 with base0 >= kIterPos: behind the block's first byte.  Every other iteration -- a block's
+    // first, its last one or two, everything under debug bit 7 -- takes the clamped body.  Both take the same one turn.
+    auto interior = [&](const Cursor &c) -> bool {
+        return !clamp_all && c.it != 0 && c.it * kIterPos + kIterPos + 16u <= c.n;
+    };
+    uint2 ring[kCandSteps];
+    // the input of iteration c, one step per ring slot
+    auto prefetch = [&](const Cursor &c) {
+        const uint8_t *in = slab + (uint64_t)c.b * cfg.block_size;
+        const uint32_t mis = (uint32_t)((uintptr_t)in & 3u);
+        const uint32_t *in32 = (const uint32_t *)(in - mis);
+        if (interior(c)) {
+            // p + mis = (base0 + 64 k) + (lane + mis) and base0 + 64 k is a multiple of four: the lane's dword of
+            // step k is its dword of step 0 plus 16 k, so one address per lane and an immediate offset per load.
+            // The upper dword goes through an offset of its own that the compiler cannot see through: left
+            // alone it merges the pair into one 4-byte-aligned dwordx2 load, the slower way (see cand_fetch).
+            const uint8_t *row = (const uint8_t *)(in32 + c.it * (kIterPos / 4));  // (uniform)
+            const uint32_t lo = (lane + mis) & ~3u;
+            uint32_t hi = lo + 4;
+            GZPX_PIN_VGPR(hi);
+#pragma unroll
+            for (uint32_t k = 0; k < kCandSteps; k++) {
+                ring[k].x = *(const uint32_t *)(row + lo + 64 * k);
+                ring[k].y = *(const uint32_t *)(row + hi + 64 * k);
+            }
+            GZPX_KEEP_ARM_APART();
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < kCandSteps; k++)
+                ring[k] = cand_fetch(in32, mis, c.it * kIterPos + k * 64 + lane, (mis + c.n - 1) >> 2);
+        }
+    };
     Cursor cur{blockIdx.x, wave, 0, 0, 32768u, 0};  // (vbase starts a window's length up: an empty bucket, 0, reads as dead too)
     bool live = !force_safe && settle(cur);
     bool bad = false;
-    uint2 ring[kCandSteps];
-    if (live) {
-        const uint8_t *in = slab + (uint64_t)cur.b * cfg.block_size;
-        const uint32_t mis = (uint32_t)((uintptr_t)in & 3u);
-#pragma unroll
-        for (uint32_t k = 0; k < kCandSteps; k++)
-            ring[k] = cand_fetch((const uint32_t *)(in - mis), mis, cur.it * kIterPos + k * 64 + lane, (mis + cur.n - 1) >> 2);
-    }
+    if (live) prefetch(cur);
     while (live) {  // (wave-uniform)
         const uint32_t n = cur.n, base0 = cur.it * kIterPos, vbase = cur.vbase, my_turn = cur.ibase + cur.it;
         const uint32_t mis = (uint32_t)((uintptr_t)(slab + (uint64_t)cur.b * cfg.block_size) & 3u);
         uint16_t *cand = cand_all + (uint64_t)cur.b * cfg.stride;
+        const bool inner = interior(cur);
         // The serial phase must be nothing but the atomics: a lone wave issues about one dependent
         // instruction per ten cycles, so every instruction inside the turn costs every wave.
         // LDS byte address and value of every step are therefore finished (and pinned in registers)
         // before the wave asks for its turn; lanes without a bucket aim a zero at a spare word.
         uint32_t addr[kCandSteps], val[kCandSteps], old[kCandSteps];
         bool mine[kCandSteps];  // this pass owns the position's bucket
+        if (inner) {
+            const uint32_t sh = (lane + mis) & 3u;  // (p + mis) & 3 of every step: 64 k + base0 is a multiple of four
+            const uint32_t v0 = vbase + base0 + lane + 1;
 #pragma unroll
-        for (uint32_t k = 0; k < kCandSteps; k++) {
-            const uint32_t p = base0 + k * 64 + lane;
-            const uint32_t v = __builtin_amdgcn_alignbyte(ring[k].y, ring[k].x, (p + mis) & 3u);
-            uint32_t hk;
-            mine[k] = cand_bucket<MODE>(v, p, hk) && p + 5 <= n;
-            // byte offset into the table; a lane without a bucket (the other hash4 pass owns it) aims its
-            // zero at a spare word of its own -- one shared spare word made half the lanes of every
-            // atomic hit the same address, which the LDS serialises (hash4 passes 1.43 / 1.25 ms against
-            // 1.00 ms for the hash3 pass)
-            addr[k] = 4u * (mine[k] ? hk : kBuckets + lane);
-            val[k] = mine[k] ? vbase + p + 1 : 0u;
-            GZPX_PIN_VGPR(addr[k]);
-            GZPX_PIN_VGPR(val[k]);
+            for (uint32_t k = 0; k < kCandSteps; k++) {
+                const uint32_t v = __builtin_amdgcn_alignbyte(ring[k].y, ring[k].x, sh);
+                if (MODE <= 1) {  // p != 0, p + 5 <= n: every position has its bucket
+                    mine[k] = true;
+                    addr[k] = 4u * lz_hash15(MODE == 0 ? v : v & 0xFFFFFFu);
+                    val[k] = v0 + 64 * k;
+                } else {
+                    const uint32_t h16 = (v * 0x1E35A7BDu) >> 16;
+                    mine[k] = MODE == 2 ? h16 < 32768u : h16 >= 32768u;
+                    addr[k] = 4u * (mine[k] ? h16 & 32767u : kBuckets + lane);
+                    val[k] = mine[k] ? v0 + 64 * k : 0u;
+                }
+                GZPX_PIN_VGPR(addr[k]);
+                GZPX_PIN_VGPR(val[k]);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < kCandSteps; k++) {
+                const uint32_t p = base0 + k * 64 + lane;
+                const uint32_t v = __builtin_amdgcn_alignbyte(ring[k].y, ring[k].x, (p + mis) & 3u);
+                uint32_t hk;
+                mine[k] = cand_bucket<MODE>(v, p, hk) && p + 5 <= n;
+                // byte offset into the table; a lane without a bucket (the other hash4 pass owns it) aims its
+                // zero at a spare word of its own -- one shared spare word made half the lanes of every
+                // atomic hit the same address, which the LDS serialises (hash4 passes 1.43 / 1.25 ms against
+                // 1.00 ms for the hash3 pass)
+                addr[k] = 4u * (mine[k] ? hk : kBuckets + lane);
+                val[k] = mine[k] ? vbase + p + 1 : 0u;
+                GZPX_PIN_VGPR(addr[k]);
+                GZPX_PIN_VGPR(val[k]);
+            }
         }
         // this wave's next iteration: of this block, or the first it owns in a later one
         Cursor nxt = cur;
         nxt.it += kCandWaves;
         const bool more = settle(nxt);
-        if (more) {
-            const uint8_t *in = slab + (uint64_t)nxt.b * cfg.block_size;
-            const uint32_t nmis = (uint32_t)((uintptr_t)in & 3u);
-#pragma unroll
-            for (uint32_t k = 0; k < kCandSteps; k++)
-                ring[k] = cand_fetch((const uint32_t *)(in - nmis), nmis, nxt.it * kIterPos + k * 64 + lane, (nmis + nxt.n - 1) >> 2);
-        }
+        if (more) prefetch(nxt);
+        // (the turn: one place for both bodies, so that every iteration takes exactly one, with the same number)
         wave_sync();
         while (__hip_atomic_load(&turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != my_turn)
             __builtin_amdgcn_s_sleep(1);
@@ -471,15 +546,28 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_candidates(Config cfg,
         bad |= seen > 0x7FFFFFFFu;  // (never) -- orders the ticket store after the atomics' return
         wave_sync();
         if (lane == 0) __hip_atomic_store(&turn, my_turn + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (inner) {
+            uint16_t *out = cand + base0 + lane;  // step k's slot: out[64 k], an immediate offset
 #pragma unroll
-        for (uint32_t k = 0; k < kCandSteps; k++) {
-            const uint32_t p = base0 + k * 64 + lane;
-            bad |= old[k] > vbase + p;  // handed a predecessor that is not earlier: LDS order assumption broken
-            uint32_t d0 = vbase + p + 1 - old[k];  // (an empty bucket, or an earlier block's entry: > 32767)
-            if (d0 > 32767u) d0 = 0;  // farther than the window: dead
-            // p < cfg.stride (padded by >= one iteration).  The two hash4 passes own disjoint
-            // positions; positions that are never hashed are zeroed by the first of them.
-            if (MODE < 2 || mine[k] || (MODE == 2 && p + 5 > n)) cand[p] = (uint16_t)d0;
+            for (uint32_t k = 0; k < kCandSteps; k++) {
+                // val[k] = vbase + p + 1 is still in its register: one subtraction gives the distance, and the
+                // order check (old >= val <=> a difference that is not positive; values stay below 2^31, see
+                // `seen`) and the window test read it.  A lane without a bucket has 0 - 0 here and is left out.
+                const uint32_t d0 = val[k] - old[k];
+                bad |= (MODE < 2 || mine[k]) && (int32_t)d0 <= 0;
+                if (MODE < 2 || mine[k]) out[64 * k] = (uint16_t)(d0 > 32767u ? 0u : d0);  // (every position is hashed)
+            }
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < kCandSteps; k++) {
+                const uint32_t p = base0 + k * 64 + lane;
+                bad |= old[k] > vbase + p;  // handed a predecessor that is not earlier: LDS order assumption broken
+                uint32_t d0 = vbase + p + 1 - old[k];  // (an empty bucket, or an earlier block's entry: > 32767)
+                if (d0 > 32767u) d0 = 0;  // farther than the window: dead
+                // p < cfg.stride (padded by >= one iteration).  The two hash4 passes own disjoint
+                // positions; positions that are never hashed are zeroed by the first of them.
+                if (MODE < 2 || mine[k] || (MODE == 2 && p + 5 > n)) cand[p] = (uint16_t)d0;
+            }
         }
         cur = nxt;
         live = more;

@@ -779,7 +779,9 @@ int gzpx_debug_tokens(gzpx_ctx *ctx, size_t block, uint32_t *tokens, size_t max_
  * fallback (cand_block_safe) on every block instead of the atomic-chain form; bit 1 = level 1 through the
  * dense k_match / k_parse pair instead of the match-on-demand kernel k_mparse; bit 2 = k_mparse
  * hands every block back to the dense pair (exercises the redo list); bit 3 = k_mparse's walks search at
- * every position instead of stepping over the runs that have no hash candidate (same stream; A/B timing). */
+ * every position instead of stepping over the runs that have no hash candidate (same stream; A/B timing);
+ * bit 7 = k_candidates takes every iteration through its clamped body instead of the interior one (same
+ * stream; A/B timing). */
 int gzpx_debug_set_flags(gzpx_ctx *ctx, uint32_t flags);
 /* Level 1: how many blocks of the last batch k_mparse handed back to the dense kernels. */
 int gzpx_debug_redo_count(gzpx_ctx *ctx, uint32_t *count);

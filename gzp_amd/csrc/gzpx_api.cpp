@@ -1533,10 +1533,11 @@ struct LinesState : NoCopy {
     }
 };
 
-// search (gzpx_find_device): the batches, the staging buffer and one slot as a line-table build uses them
+// search (gzpx_find_device; the scratch and the events for a set's too): the batches, the staging buffer and one slot as a
+// line-table build uses them
 struct FindState : NoCopy {
     Event ev[4];                       // per batch: inflate [0..1], count + scan [1..2], write + carry [2..3]
-    float ms[3] = {0.0f, 0.0f, 0.0f};  // the last call's, summed over its batches
+    float ms[3] = {0.0f, 0.0f, 0.0f};  // the last gzpx_find_device's, summed over its batches
     FindScratch fd;
     uint32_t *h_pat = nullptr;  // pinned: the pattern on its way in
     uint64_t *h_rec = nullptr;  // pinned: the record on its way out
@@ -1588,8 +1589,7 @@ struct SelectState : NoCopy {
 // search for a set (gzpx_find_set_device, gzpx_select_lines_set_device): the compiled set and the counts per pattern.
 // The pieces' counts and bases, the record and its pinned copy are the search's (c->find), as the selection uses them.
 struct FindSetState : NoCopy {
-    Event ev[4];                       // per batch: inflate [0..1], count + scan [1..2], write + carry [2..3]
-    float ms[3] = {0.0f, 0.0f, 0.0f};  // the last call's, summed over its batches
+    float ms[3] = {0.0f, 0.0f, 0.0f};  // the last gzpx_find_set_device's, summed over its batches (timed with c->find.ev)
     FsSet *d_set = nullptr;
     FsSet *h_set = nullptr;        // pinned: the compiled set on its way in
     uint64_t *d_counts = nullptr;  // [kFsMaxPatterns] the hits of every pattern
@@ -1601,7 +1601,6 @@ struct FindSetState : NoCopy {
         GZPX_TRY(once.dev(d_set, sizeof(FsSet)));
         GZPX_TRY(once.dev(d_counts, kFsMaxPatterns * 8));
         GZPX_TRY(once.pinned(h_set, sizeof(FsSet)));
-        for (Event &e : ev) GZPX_TRY(e.create(true));
         ready = true;
         return GZPX_OK;
     }
@@ -2683,65 +2682,6 @@ int gzpx_dlines_build_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_
     return GZPX_OK;
 }
 
-int gzpx_find_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *pattern,
-                     size_t pattern_len, int delim, uint64_t *d_positions, uint64_t *d_lines, size_t hits_cap, uint64_t *n_hits,
-                     gzpx_check_info *info, void *hip_stream) {
-    static_assert(kFdMaxPattern == GZPX_FIND_MAX_PATTERN, "the public constant states the kernels' limit");
-    if (!c || !ix || !n_hits || !pattern || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
-    *n_hits = 0;
-    if (pattern_len == 0 || pattern_len > kFdMaxPattern || delim < GZPX_FIND_NO_LINES || delim > 255) return GZPX_ERR_INVALID_ARG;
-    if (d_lines && delim == GZPX_FIND_NO_LINES) return GZPX_ERR_INVALID_ARG;
-    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
-    const uint64_t total = ix->inflated_len;
-    const uint32_t m = (uint32_t)pattern_len;
-    const bool writes = d_positions || d_lines;
-    const uint64_t cap = writes ? hits_cap : 0;
-    std::unique_lock<std::mutex> lk(c->mu);
-    FindState &f = c->find;
-    f.ms[0] = f.ms[1] = f.ms[2] = 0.0f;
-    if (!ix->n || m > total) return GZPX_OK;  // (no position can hold the pattern: nothing is inflated)
-    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
-    hipStream_t stream = c->stream;
-    Drain drain{{stream}, 1};
-    Batches b;
-    GZPX_TRY(batches_of(c, ix, b));
-    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
-    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
-    memset(f.h_pat, 0, kFdMaxPattern);
-    memcpy(f.h_pat, pattern, m);
-    HIP_TRY(hipMemcpyAsync(f.fd.pat, f.h_pat, kFdMaxPattern, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(f.fd.rec, 0, kFdRecWords * 8, stream));
-    GZPX_TRY(batched_pass(
-        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, f.ev, 3, f.ms, info, drain,
-        [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
-            const FindBatch fb{c->stage.d, base, bytes, (uint32_t)(base < m - 1u ? base : m - 1u), m, d_lines ? delim : GZPX_FIND_NO_LINES};
-            HIP_TRY(hipEventRecord(f.ev[1], stream));
-            if (bytes) launch_find_count(fb, f.fd, stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(f.ev[2], stream));
-            if (bytes && cap) launch_find_write(fb, f.fd, d_positions, d_lines, cap, stream);
-            const uint64_t seen = base + bytes;
-            const uint32_t carry = (uint32_t)(seen < m - 1u ? seen : m - 1u);  // (a batch shorter than that appends to the carry)
-            if (bytes && carry && !is_last) launch_find_carry(fb, f.fd, carry, stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(f.ev[3], stream));
-            return GZPX_OK;
-        }));
-    HIP_TRY(hipMemcpyAsync(f.h_rec, f.fd.rec, kFdRecWords * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    drain.armed = false;
-    *n_hits = f.h_rec[kFdRecHits];
-    return writes && *n_hits > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
-}
-
-int gzpx_dctx_last_find_ms(gzpx_dctx *ctx, float ms[3]) {
-    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    for (int j = 0; j < 3; j++) ms[j] = ctx->find.ms[j];
-    return GZPX_OK;
-}
-
 int gzpx_dlines_prefix(const gzpx_dlines *lt, uint64_t *prefix, size_t max_entries, size_t *n_entries) {
     if (!lt || !n_entries) return GZPX_ERR_INVALID_ARG;
     *n_entries = (size_t)lt->tiles + 1;
@@ -2845,94 +2785,10 @@ int gzpx_read_lines_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx
                       d_byte_ranges, bad_range, info, hip_stream);
 }
 
-int gzpx_select_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
-                             const void *pattern, size_t pattern_len, uint64_t group, unsigned flags, gzpx_range *d_runs,
-                             size_t runs_cap, uint64_t *n_runs, uint64_t *n_records, uint64_t *n_hits, gzpx_check_info *info,
-                             void *hip_stream) {
-    if (!c || !ix || !lt || !n_runs || !n_records || !pattern || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
-    *n_runs = *n_records = 0;
-    if (n_hits) *n_hits = 0;
-    if (group == 0 || (flags & ~GZPX_SELECT_INVERT) || pattern_len == 0 || pattern_len > kFdMaxPattern) return GZPX_ERR_INVALID_ARG;
-    if (!lines_match(c, ix, lt, in_len)) return GZPX_ERR_INVALID_ARG;
-    const uint64_t L = lt->n_lines, total = ix->inflated_len;
-    const uint64_t R = L / group + (L % group ? 1u : 0u);
-    if (R > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
-    const uint32_t m = (uint32_t)pattern_len;
-    const int invert = (flags & GZPX_SELECT_INVERT) ? 1 : 0;
-    const uint64_t cap = d_runs ? runs_cap : 0;
-    std::unique_lock<std::mutex> lk(c->mu);
-    SelectState &s = c->select;
-    FindState &f = c->find;
-    s.ms[0] = s.ms[1] = s.ms[2] = 0.0f;
-    if (L == 0) return GZPX_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
-    hipStream_t stream = c->stream;
-    if (m > total) {  // no position can hold the pattern: nothing is inflated, and every record is one run under INVERT
-        if (!invert) return GZPX_OK;
-        *n_runs = 1;
-        *n_records = R;
-        if (!d_runs) return GZPX_OK;
-        if (!cap) return GZPX_ERR_INSUFFICIENT_SPACE;
-        GZPX_TRY(s.reserve(1));
-        GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
-        Drain drain{{stream}, 1};
-        s.h_run[0] = 0;
-        s.h_run[1] = L;
-        HIP_TRY(hipMemcpyAsync(d_runs, s.h_run, 16, hipMemcpyHostToDevice, stream));
-        return GZPX_OK;  // (the drain synchronises)
-    }
-    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
-    Drain drain{{stream}, 1};
-    Batches b;
-    GZPX_TRY(batches_of(c, ix, b));
-    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
-    GZPX_TRY(s.reserve(R));
-    GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
-    memset(f.h_pat, 0, kFdMaxPattern);
-    memcpy(f.h_pat, pattern, m);
-    HIP_TRY(hipMemcpyAsync(f.fd.pat, f.h_pat, kFdMaxPattern, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(f.fd.rec, 0, kFdRecWords * 8, stream));
-    HIP_TRY(hipMemsetAsync(s.sl.bitmap, 0, (size_t)((R + 31) / 32 * 4), stream));
-    GZPX_TRY(batched_pass(
-        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, s.ev, 2, s.ms, info, drain,
-        [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
-            const FindBatch fb{c->stage.d, base, bytes, (uint32_t)(base < m - 1u ? base : m - 1u), m, (int)lt->delim};
-            HIP_TRY(hipEventRecord(s.ev[1], stream));
-            if (bytes) {
-                launch_find_count(fb, f.fd, stream);
-                launch_select_mark(fb, f.fd, s.sl, group, R, stream);
-            }
-            const uint64_t seen = base + bytes;
-            const uint32_t carry = (uint32_t)(seen < m - 1u ? seen : m - 1u);  // (a batch shorter than that appends to the carry)
-            if (bytes && carry && !is_last) launch_find_carry(fb, f.fd, carry, stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(s.ev[2], stream));
-            return GZPX_OK;
-        }));
-    HIP_TRY(hipEventRecord(s.ev[3], stream));
-    launch_select_runs(s.sl, f.fd, R, group, L, invert, (uint64_t *)d_runs, cap, stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s.ev[4], stream));
-    HIP_TRY(hipMemcpyAsync(s.h_rec, s.sl.rec, kSlRecWords * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    drain.armed = false;
-    if (hipEventElapsedTime(&s.ms[2], s.ev[3], s.ev[4]) != hipSuccess) s.ms[2] = 0.0f;
-    *n_runs = s.h_rec[kSlRecRuns];
-    *n_records = s.h_rec[kSlRecRecords];
-    if (n_hits) *n_hits = s.h_rec[kSlRecHits];
-    return d_runs && *n_runs > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
-}
-
-int gzpx_dctx_last_select_ms(gzpx_dctx *ctx, float ms[3]) {
-    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    for (int j = 0; j < 3; j++) ms[j] = ctx->select.ms[j];
-    return GZPX_OK;
-}
-
 }  // extern "C"
 
-// ---------------------------------------------------------------- search for a set of patterns (gzpx_findset.h)
+// ---------------------------------------------------------------- search and selection, for one pattern or a set of them
+// (gzpx_find.h, gzpx_select.h, gzpx_findset.h)
 namespace {
 
 // what the entry points check of a set before anything else happens
@@ -2997,63 +2853,92 @@ size_t findset_compile(const uint8_t *patterns, const uint32_t *off, const SetSh
     return offsetof(FsSet, bytes) + (size_t)words * 4u;
 }
 
-// What a batch of the set's pass does.  Hits are owned by their START: a batch that is not the last owns the starts p
-// of its region with p + M <= the region's end (M the longest pattern), the last min(M - 1, bytes seen) bytes wait in
-// the carry, and the last batch owns every start that is left -- also when it holds no byte itself.
-struct SetBatch {
+// What a call searches for: one pattern (off null; sh.K = 1, sh.longest = sh.shortest = its length) or a set.
+struct Wanted {
+    const void *bytes;    // the pattern, or the set's patterns back to back
+    const uint32_t *off;  // the set's offsets into them
+    SetShape sh;
+};
+
+// What a batch of a search does.
+struct SearchBatch {
     FindBatch fb;
     bool search;     // the region is not empty and is either new or the last word on its starts
     uint32_t carry;  // bytes to keep for the next batch (0: none, or the carry stays as it is)
 };
 
-SetBatch findset_batch(uint8_t *stage, uint64_t base, uint64_t bytes, bool is_last, uint32_t M, int delim) {
+// One pattern of m bytes.  Hits are owned by their LAST byte: a batch searches its bytes with the last min(m - 1, bytes
+// in front of it) bytes of the earlier batches in front of them, and keeps the last min(m - 1, bytes seen) bytes for the
+// next batch (a batch shorter than that appends to the carry).
+SearchBatch batch_by_last_byte(uint8_t *stage, uint64_t base, uint64_t bytes, bool is_last, uint32_t m, int delim) {
+    const uint64_t seen = base + bytes;
+    SearchBatch s;
+    s.fb = FindBatch{stage, base, bytes, (uint32_t)(base < m - 1u ? base : m - 1u), m, delim};
+    s.search = bytes != 0;
+    s.carry = bytes && !is_last ? (uint32_t)(seen < m - 1u ? seen : m - 1u) : 0u;
+    return s;
+}
+
+// A set whose longest pattern has M bytes.  Hits are owned by their START: a batch that is not the last owns the starts
+// p of its region with p + M <= the region's end, the last min(M - 1, bytes seen) bytes wait in the carry, and the last
+// batch owns every start that is left -- also when it holds no byte itself.
+SearchBatch batch_by_start(uint8_t *stage, uint64_t base, uint64_t bytes, bool is_last, uint32_t M, int delim) {
     const uint32_t waiting = (uint32_t)(base < M - 1u ? base : M - 1u);
     const uint64_t seen = base + bytes;
-    SetBatch s;
+    SearchBatch s;
     s.fb = FindBatch{stage, base, bytes, waiting, is_last ? 1u : M, delim};
     s.search = bytes || (is_last && waiting);
     s.carry = bytes && !is_last ? (uint32_t)(seen < M - 1u ? seen : M - 1u) : 0u;
     return s;
 }
 
-// the compiled set and cleared records on their way to the device, in front of the first batch
-int findset_begin(gzpx_dctx *c, const void *patterns, const uint32_t *off, const SetShape &sh) {
+SearchBatch search_batch(const Wanted &w, uint8_t *stage, uint64_t base, uint64_t bytes, bool is_last, int delim) {
+    return w.off ? batch_by_start(stage, base, bytes, is_last, w.sh.longest, delim)
+                 : batch_by_last_byte(stage, base, bytes, is_last, w.sh.longest, delim);
+}
+
+// the search's scratch for the batches of b (and the events both kinds of search time with)
+int search_reserve(gzpx_dctx *c, const Wanted &w, const Batches &b) {
+    GZPX_TRY(c->find.reserve((size_t)find_pieces(b.max_bytes)));
+    return w.off ? c->find_set.reserve() : GZPX_OK;
+}
+
+// In front of the first batch: the pattern or the compiled set, and cleared records, on their way to the device.
+// `mt`: what the launchers take for it.
+int search_begin(gzpx_dctx *c, const Wanted &w, FindMatcher &mt) {
+    FindState &f = c->find;
     FindSetState &fs = c->find_set;
-    const size_t used = findset_compile((const uint8_t *)patterns, off, sh, fs.h_set);
+    mt = FindMatcher{};
+    HIP_TRY(hipMemsetAsync(f.fd.rec, 0, kFdRecWords * 8, c->stream));
+    if (!w.off) {
+        memset(f.h_pat, 0, kFdMaxPattern);
+        memcpy(f.h_pat, w.bytes, w.sh.longest);
+        HIP_TRY(hipMemcpyAsync(f.fd.pat, f.h_pat, kFdMaxPattern, hipMemcpyHostToDevice, c->stream));
+        return GZPX_OK;
+    }
+    const size_t used = findset_compile((const uint8_t *)w.bytes, w.off, w.sh, fs.h_set);
     HIP_TRY(hipMemcpyAsync(fs.d_set, fs.h_set, used, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(fs.d_counts, 0, kFsMaxPatterns * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(c->find.fd.rec, 0, kFdRecWords * 8, c->stream));
+    mt = FindMatcher{fs.d_set, fs.d_counts};
     return GZPX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gzpx_find_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *patterns,
-                         const uint32_t *pattern_offsets, size_t n_patterns, int delim, uint64_t *d_positions, uint32_t *d_ids,
-                         uint64_t *d_lines, size_t hits_cap, uint64_t *d_counts, uint64_t *n_hits, gzpx_check_info *info,
-                         void *hip_stream) {
-    if (!c || !ix || !n_hits || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
-    *n_hits = 0;
-    SetShape sh;
-    if (!findset_shape(patterns, pattern_offsets, n_patterns, sh)) return GZPX_ERR_INVALID_ARG;
-    if (delim < GZPX_FIND_NO_LINES || delim > 255 || (d_lines && delim == GZPX_FIND_NO_LINES)) return GZPX_ERR_INVALID_ARG;
-    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
-    const uint64_t total = ix->inflated_len;
+// gzpx_find_device and gzpx_find_set_device behind their argument checks.  `ms`: the kind's own three sums.
+int search_hits(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, const Wanted &w, int delim, uint64_t *d_positions,
+                uint32_t *d_ids, uint64_t *d_lines, size_t hits_cap, uint64_t *d_counts, float *ms, uint64_t *n_hits,
+                gzpx_check_info *info, void *hip_stream) {
     const bool writes = d_positions || d_ids || d_lines;
     const uint64_t cap = writes ? hits_cap : 0;
     std::unique_lock<std::mutex> lk(c->mu);
-    FindSetState &fs = c->find_set;
     FindState &f = c->find;
-    fs.ms[0] = fs.ms[1] = fs.ms[2] = 0.0f;
+    ms[0] = ms[1] = ms[2] = 0.0f;
     hipStream_t stream = c->stream;
-    if (!ix->n || sh.shortest > total) {  // no position can hold a pattern: nothing is inflated, every count is zero
+    if (!ix->n || w.sh.shortest > ix->inflated_len) {  // no position can hold a pattern: nothing is inflated, every count is zero
         if (!d_counts) return GZPX_OK;
         if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
         GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
         Drain drain{{stream}, 1};
-        HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)sh.K * 8, stream));
+        HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)w.sh.K * 8, stream));
         return GZPX_OK;  // (the drain synchronises)
     }
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
@@ -3061,51 +2946,37 @@ int gzpx_find_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, 
     Drain drain{{stream}, 1};
     Batches b;
     GZPX_TRY(batches_of(c, ix, b));
-    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
-    GZPX_TRY(fs.reserve());
+    GZPX_TRY(search_reserve(c, w, b));
     GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
-    GZPX_TRY(findset_begin(c, patterns, pattern_offsets, sh));
+    FindMatcher mt;
+    GZPX_TRY(search_begin(c, w, mt));
     GZPX_TRY(batched_pass(
-        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, fs.ev, 3, fs.ms, info, drain,
+        c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, f.ev, 3, ms, info, drain,
         [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
-            const SetBatch sb = findset_batch(c->stage.d, base, bytes, is_last, sh.longest, d_lines ? delim : GZPX_FIND_NO_LINES);
-            HIP_TRY(hipEventRecord(fs.ev[1], stream));
-            if (sb.search) launch_findset_count(sb.fb, f.fd, fs.d_set, fs.d_counts, stream);
+            const SearchBatch sb = search_batch(w, c->stage.d, base, bytes, is_last, d_lines ? delim : GZPX_FIND_NO_LINES);
+            HIP_TRY(hipEventRecord(f.ev[1], stream));
+            if (sb.search) launch_find_count(sb.fb, f.fd, mt, stream);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(fs.ev[2], stream));
-            if (sb.search && cap) launch_findset_write(sb.fb, f.fd, fs.d_set, d_positions, d_ids, d_lines, cap, stream);
+            HIP_TRY(hipEventRecord(f.ev[2], stream));
+            if (sb.search && cap) launch_find_write(sb.fb, f.fd, mt, d_positions, d_ids, d_lines, cap, stream);
             if (sb.carry) launch_find_carry(sb.fb, f.fd, sb.carry, stream);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(fs.ev[3], stream));
+            HIP_TRY(hipEventRecord(f.ev[3], stream));
             return GZPX_OK;
         }));
     HIP_TRY(hipMemcpyAsync(f.h_rec, f.fd.rec, kFdRecWords * 8, hipMemcpyDeviceToHost, stream));
-    if (d_counts) HIP_TRY(hipMemcpyAsync(d_counts, fs.d_counts, (size_t)sh.K * 8, hipMemcpyDeviceToDevice, stream));
+    if (d_counts) HIP_TRY(hipMemcpyAsync(d_counts, mt.d_counts, (size_t)w.sh.K * 8, hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;
     *n_hits = f.h_rec[kFdRecHits];
     return writes && *n_hits > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
 }
 
-int gzpx_dctx_last_find_set_ms(gzpx_dctx *ctx, float ms[3]) {
-    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    for (int j = 0; j < 3; j++) ms[j] = ctx->find_set.ms[j];
-    return GZPX_OK;
-}
-
-int gzpx_select_lines_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
-                                 const void *patterns, const uint32_t *pattern_offsets, size_t n_patterns, uint64_t group,
-                                 unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_records,
-                                 uint64_t *n_hits, gzpx_check_info *info, void *hip_stream) {
-    if (!c || !ix || !lt || !n_runs || !n_records || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
-    *n_runs = *n_records = 0;
-    if (n_hits) *n_hits = 0;
-    SetShape sh;
-    if (group == 0 || (flags & ~GZPX_SELECT_INVERT) || !findset_shape(patterns, pattern_offsets, n_patterns, sh))
-        return GZPX_ERR_INVALID_ARG;
-    if (!lines_match(c, ix, lt, in_len)) return GZPX_ERR_INVALID_ARG;
-    const uint64_t L = lt->n_lines, total = ix->inflated_len;
+// gzpx_select_lines_device and gzpx_select_lines_set_device behind their argument checks.
+int select_lines(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, const Wanted &w, uint64_t group,
+                 unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_records, uint64_t *n_hits,
+                 gzpx_check_info *info, void *hip_stream) {
+    const uint64_t L = lt->n_lines;
     const uint64_t R = L / group + (L % group ? 1u : 0u);
     if (R > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
     const int invert = (flags & GZPX_SELECT_INVERT) ? 1 : 0;
@@ -3113,12 +2984,11 @@ int gzpx_select_lines_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx
     std::unique_lock<std::mutex> lk(c->mu);
     SelectState &s = c->select;
     FindState &f = c->find;
-    FindSetState &fs = c->find_set;
     s.ms[0] = s.ms[1] = s.ms[2] = 0.0f;
     if (L == 0) return GZPX_OK;
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
     hipStream_t stream = c->stream;
-    if (sh.shortest > total) {  // no position can hold a pattern: nothing is inflated, and every record is one run under INVERT
+    if (w.sh.shortest > ix->inflated_len) {  // no position can hold a pattern: nothing is inflated, and every record is one run under INVERT
         if (!invert) return GZPX_OK;
         *n_runs = 1;
         *n_records = R;
@@ -3136,20 +3006,20 @@ int gzpx_select_lines_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx
     Drain drain{{stream}, 1};
     Batches b;
     GZPX_TRY(batches_of(c, ix, b));
-    GZPX_TRY(f.reserve((size_t)find_pieces(b.max_bytes)));
-    GZPX_TRY(fs.reserve());
+    GZPX_TRY(search_reserve(c, w, b));
     GZPX_TRY(s.reserve(R));
     GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
-    GZPX_TRY(findset_begin(c, patterns, pattern_offsets, sh));
+    FindMatcher mt;
+    GZPX_TRY(search_begin(c, w, mt));
     HIP_TRY(hipMemsetAsync(s.sl.bitmap, 0, (size_t)((R + 31) / 32 * 4), stream));
     GZPX_TRY(batched_pass(
         c, si, ix, b, (const uint8_t *)d_in, kFdPad /* the inflate writes behind the pad */, s.ev, 2, s.ms, info, drain,
         [&](uint64_t base, uint64_t bytes, bool is_last) -> int {
-            const SetBatch sb = findset_batch(c->stage.d, base, bytes, is_last, sh.longest, (int)lt->delim);
+            const SearchBatch sb = search_batch(w, c->stage.d, base, bytes, is_last, (int)lt->delim);
             HIP_TRY(hipEventRecord(s.ev[1], stream));
             if (sb.search) {
-                launch_findset_count(sb.fb, f.fd, fs.d_set, fs.d_counts, stream);
-                launch_findset_mark(sb.fb, f.fd, fs.d_set, s.sl, group, R, stream);
+                launch_find_count(sb.fb, f.fd, mt, stream);
+                launch_select_mark(sb.fb, f.fd, mt, s.sl, group, R, stream);
             }
             if (sb.carry) launch_find_carry(sb.fb, f.fd, sb.carry, stream);
             HIP_TRY(hipGetLastError());
@@ -3169,6 +3039,80 @@ int gzpx_select_lines_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx
     if (n_hits) *n_hits = s.h_rec[kSlRecHits];
     return d_runs && *n_runs > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
 }
+
+// the three sums of the last call of one kind
+template <class State>
+int last_ms(gzpx_dctx *ctx, State gzpx_dctx::*kind, float ms[3]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    for (int j = 0; j < 3; j++) ms[j] = (ctx->*kind).ms[j];
+    return GZPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gzpx_find_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *pattern,
+                     size_t pattern_len, int delim, uint64_t *d_positions, uint64_t *d_lines, size_t hits_cap, uint64_t *n_hits,
+                     gzpx_check_info *info, void *hip_stream) {
+    static_assert(kFdMaxPattern == GZPX_FIND_MAX_PATTERN, "the public constant states the kernels' limit");
+    if (!c || !ix || !n_hits || !pattern || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_hits = 0;
+    if (pattern_len == 0 || pattern_len > kFdMaxPattern || delim < GZPX_FIND_NO_LINES || delim > 255) return GZPX_ERR_INVALID_ARG;
+    if (d_lines && delim == GZPX_FIND_NO_LINES) return GZPX_ERR_INVALID_ARG;
+    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
+    const uint32_t m = (uint32_t)pattern_len;
+    return search_hits(c, ix, d_in, Wanted{pattern, nullptr, SetShape{1u, m, m}}, delim, d_positions, nullptr, d_lines, hits_cap, nullptr,
+                       c->find.ms, n_hits, info, hip_stream);
+}
+
+int gzpx_find_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const void *d_in, size_t in_len, const void *patterns,
+                         const uint32_t *pattern_offsets, size_t n_patterns, int delim, uint64_t *d_positions, uint32_t *d_ids,
+                         uint64_t *d_lines, size_t hits_cap, uint64_t *d_counts, uint64_t *n_hits, gzpx_check_info *info,
+                         void *hip_stream) {
+    if (!c || !ix || !n_hits || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_hits = 0;
+    SetShape sh;
+    if (!findset_shape(patterns, pattern_offsets, n_patterns, sh)) return GZPX_ERR_INVALID_ARG;
+    if (delim < GZPX_FIND_NO_LINES || delim > 255 || (d_lines && delim == GZPX_FIND_NO_LINES)) return GZPX_ERR_INVALID_ARG;
+    if (!index_matches(c, ix, in_len)) return GZPX_ERR_INVALID_ARG;
+    return search_hits(c, ix, d_in, Wanted{patterns, pattern_offsets, sh}, delim, d_positions, d_ids, d_lines, hits_cap, d_counts,
+                       c->find_set.ms, n_hits, info, hip_stream);
+}
+
+int gzpx_select_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                             const void *pattern, size_t pattern_len, uint64_t group, unsigned flags, gzpx_range *d_runs,
+                             size_t runs_cap, uint64_t *n_runs, uint64_t *n_records, uint64_t *n_hits, gzpx_check_info *info,
+                             void *hip_stream) {
+    if (!c || !ix || !lt || !n_runs || !n_records || !pattern || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_runs = *n_records = 0;
+    if (n_hits) *n_hits = 0;
+    if (group == 0 || (flags & ~GZPX_SELECT_INVERT) || pattern_len == 0 || pattern_len > kFdMaxPattern) return GZPX_ERR_INVALID_ARG;
+    if (!lines_match(c, ix, lt, in_len)) return GZPX_ERR_INVALID_ARG;
+    const uint32_t m = (uint32_t)pattern_len;
+    return select_lines(c, ix, lt, d_in, Wanted{pattern, nullptr, SetShape{1u, m, m}}, group, flags, d_runs, runs_cap, n_runs,
+                        n_records, n_hits, info, hip_stream);
+}
+
+int gzpx_select_lines_set_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                                 const void *patterns, const uint32_t *pattern_offsets, size_t n_patterns, uint64_t group,
+                                 unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_records,
+                                 uint64_t *n_hits, gzpx_check_info *info, void *hip_stream) {
+    if (!c || !ix || !lt || !n_runs || !n_records || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_runs = *n_records = 0;
+    if (n_hits) *n_hits = 0;
+    SetShape sh;
+    if (group == 0 || (flags & ~GZPX_SELECT_INVERT) || !findset_shape(patterns, pattern_offsets, n_patterns, sh))
+        return GZPX_ERR_INVALID_ARG;
+    if (!lines_match(c, ix, lt, in_len)) return GZPX_ERR_INVALID_ARG;
+    return select_lines(c, ix, lt, d_in, Wanted{patterns, pattern_offsets, sh}, group, flags, d_runs, runs_cap, n_runs, n_records,
+                        n_hits, info, hip_stream);
+}
+
+int gzpx_dctx_last_find_ms(gzpx_dctx *ctx, float ms[3]) { return last_ms(ctx, &gzpx_dctx::find, ms); }
+int gzpx_dctx_last_find_set_ms(gzpx_dctx *ctx, float ms[3]) { return last_ms(ctx, &gzpx_dctx::find_set, ms); }
+int gzpx_dctx_last_select_ms(gzpx_dctx *ctx, float ms[3]) { return last_ms(ctx, &gzpx_dctx::select, ms); }
 
 int gzpx_dctx_set_lines_batch(gzpx_dctx *ctx, size_t inflated_bytes) {
     if (!ctx) return GZPX_ERR_INVALID_ARG;

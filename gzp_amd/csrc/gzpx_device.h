@@ -373,11 +373,18 @@ struct FindBatch {
     int delim;  // -1: no line numbers
 };
 inline uint64_t find_pieces(uint64_t len) { return (kFdPad + len + kFdPiece - 1u) / kFdPiece; }  // of a batch, at most
-// count + scan of one batch (len > 0): f.cnt, f.bases and the record
-void launch_find_count(const FindBatch &b, const FindScratch &f, hipStream_t stream);
-// behind launch_find_count: the batch's hits below rank `cap` into d_positions / d_lines (either may be null)
-void launch_find_write(const FindBatch &b, const FindScratch &f, uint64_t *d_positions, uint64_t *d_lines, uint64_t cap,
-                       hipStream_t stream);
+// which matcher a pass runs: the pattern in f.pat (d_set null), or a compiled set (gzpx_findset.h) and its counters
+struct FsSet;
+struct FindMatcher {
+    const FsSet *d_set = nullptr;
+    uint64_t *d_counts = nullptr;  // [kFsMaxPatterns] the counting pass adds the hits of pattern k to d_counts[k]
+};
+// count + scan of one batch (region not empty): f.cnt, f.bases and the record
+void launch_find_count(const FindBatch &b, const FindScratch &f, const FindMatcher &mt, hipStream_t stream);
+// behind launch_find_count: the batch's hits below rank `cap` into d_positions / d_ids / d_lines (each may be null; one
+// pattern: no ids)
+void launch_find_write(const FindBatch &b, const FindScratch &f, const FindMatcher &mt, uint64_t *d_positions, uint32_t *d_ids,
+                       uint64_t *d_lines, uint64_t cap, hipStream_t stream);
 // behind both: the last `n` <= m - 1 bytes of the region become the next batch's carry
 void launch_find_carry(const FindBatch &b, const FindScratch &f, uint32_t n, hipStream_t stream);
 
@@ -396,8 +403,8 @@ struct SelectScratch {
 };
 inline uint64_t select_groups(uint64_t n_records) { return (n_records + kSlRunRecords - 1u) / kSlRunRecords; }
 // behind launch_find_count of a batch with a delimiter: the records of the batch's hits into s.bitmap
-void launch_select_mark(const FindBatch &b, const FindScratch &f, const SelectScratch &s, uint64_t group, uint64_t n_records,
-                        hipStream_t stream);
+void launch_select_mark(const FindBatch &b, const FindScratch &f, const FindMatcher &mt, const SelectScratch &s, uint64_t group,
+                        uint64_t n_records, hipStream_t stream);
 // behind the last batch (n_records > 0): s.rec, and the runs below rank `cap` into d_runs (null: counts only) as
 // (begin, end) pairs of line numbers
 void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n_records, uint64_t group, uint64_t n_lines,
@@ -422,16 +429,9 @@ struct alignas(16) FsSet {
 static_assert(sizeof(FsSet) % 16u == 0, "staged as 16-byte words");
 // where the filter keeps the bit of a window of q bytes
 constexpr uint32_t fs_gram_index(uint32_t window, uint32_t q) { return q <= 2u ? window : (window * 0x9E3779B1u) >> 16; }
-// The set's passes over one batch, behind its inflate.  b.m says which starts the batch owns: the longest pattern for
-// a batch that is not the last, 1 for the last (gzpx_findset.h).  f.cnt / f.bases / f.rec are the search's.
-// count + scan (k_fd_scan): d_counts[k] += the hits of pattern k
-void launch_findset_count(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_counts, hipStream_t stream);
-// behind it: the batch's hits below rank `cap` into d_positions / d_ids / d_lines (each may be null)
-void launch_findset_write(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_positions, uint32_t *d_ids,
-                          uint64_t *d_lines, uint64_t cap, hipStream_t stream);
-// behind launch_findset_count of a batch with a delimiter: the records of the batch's hits into s.bitmap
-void launch_findset_mark(const FindBatch &b, const FindScratch &f, const FsSet *d_set, const SelectScratch &s, uint64_t group,
-                         uint64_t n_records, hipStream_t stream);
+// The set's passes over one batch are the search's (launch_find_count, launch_find_write, launch_select_mark) with
+// FindMatcher::d_set given.  b.m says which starts the batch owns: the longest pattern for a batch that is not the last,
+// 1 for the last (gzpx_findset.h).
 
 // gzpx_wrap.h (k_adler32_tiles): (s1, s2, n) of every 64 KiB tile of d_in[0..n) -> d_out3[3 * tile + ..]
 void launch_adler32(const uint8_t *d_in, uint64_t n, uint32_t *d_out3, hipStream_t stream);

@@ -8,15 +8,29 @@
 // [kFdPad - carry, kFdPad + len) of staging; a start is allowed where the pattern ends inside the region, so a batch
 // finds the hits whose LAST byte lies in it.  The region is cut on the 16 KiB grid of staging into PIECES.
 //
-//   k_fd_count  one workgroup per piece: its bytes once as aligned 16-byte words, four loads in flight per lane; the
-//               first three bytes of the pattern are tested on the marks (the dword behind a word comes from the
-//               neighbour lane), the rest is compared byte by byte with the pattern in LDS (up to m - 1 bytes behind
-//               the piece); delimiters counted
-//               with the same marks.  One hit count and one delimiter count per piece.
+// The writing pass of one pattern and the marking passes of the selection (gzpx_select.h: one pattern, a set) walk a
+// piece on one frame; their __global__ kernels declare the LDS and name the matcher.
+//   fd_walk     the WALK FRAME: 256 lanes x one aligned 16-byte word a step, so that lane order is byte order; the dword
+//               behind a word comes from the neighbour lane (fd_next); hits from the matcher, delimiters with ln_word; a
+//               block prefix of (hits << 32 | delimiters) in one 64-bit value; act(rank, address, line) per hit.  Three
+//               things are decided here, once, for every kernel on the walk:
+//                 - a ranked walk (the writing) ends with the row that reaches `cap`: no later row holds a hit below it;
+//                 - an unranked walk (the marking) carries no hits in the prefix: it reads only the lines;
+//                 - "delimiters wanted" is one argument: the writing pass wants them iff it stores lines, the marking
+//                   always.
+// A MATCHER is what one pattern and a set differ in on the walk: Src (what lies in device memory), Lds (what the kernel
+// declares __shared__; the constructor loads it and ends in a barrier), and
+//   hits(v, next, p, a0, ah)  bit b: a hit starts at byte b of the aligned word v read at p, for the starts in [a0, ah).
+// FdPattern is the matcher of one pattern (fd_hits): its first three bytes are tested on the marks, the rest is compared
+// byte by byte with the pattern in LDS (up to m - 1 bytes behind the piece).  FsAny (gzpx_findset.h) is the set's.
+//
+//   k_fd_count  one workgroup per piece: its bytes once as aligned 16-byte words, kFdItems loads in flight per lane;
+//               hits with fd_hits, delimiters with ln_word when lines are asked for; a wave reduction.  cnt[2 i] hits,
+//               cnt[2 i + 1] delimiters of piece x0 + i.  (k_fs_count, gzpx_findset.h, has this geometry with the
+//               set's test and counters per pattern; a frame shared by the two measured 0.5 % slower for the set.)
 //   k_fd_scan   one workgroup: the counts -> where every piece's hits go and how many delimiters lie in front of it,
 //               the totals of the earlier batches (the record) added; the record moves on.
-//   k_fd_write  the test again, 256 lanes x one word a step so that lane order is byte order; a block prefix of
-//               (hits, delimiters) packed in one 64-bit value; positions and lines stored below hits_cap.
+//   k_fd_write  the writing pass on the walk with FdPattern: positions and lines of the ranks below hits_cap.
 //   k_fd_carry  one workgroup: the region's last min(m - 1, bytes seen) bytes go to the end of the pad (a batch
 //               shorter than m - 1 bytes thereby appends), and their delimiters are counted: the next batch's pieces
 //               count them again, so its scan starts that many lower.
@@ -103,6 +117,65 @@ __device__ __forceinline__ void fd_piece(const FdArgs &a, uint32_t x, uintptr_t 
     a0 = (uintptr_t)a.stage + b;
     a1 = (uintptr_t)a.stage + e;
     ah = (uintptr_t)a.stage + (h < e ? h : e);
+}
+
+// f(b) for every set bit b of a 16-bit mask, ascending
+template <class F>
+__device__ __forceinline__ void fd_each_bit(uint32_t mask, F &&f) {
+    for (uint32_t c = mask; c; c &= c - 1u) f((uint32_t)__ffs((int)c) - 1u);
+}
+
+// the matcher of one pattern
+struct FdPattern {
+    using Src = uint32_t;                      // the pattern in device memory, kFdMaxPattern bytes
+    using Lds = uint32_t[kFdMaxPattern / 4u];
+    const uint8_t *pat;
+    uint32_t s0, s1, s2, m;  // the splats of the first three bytes
+    __device__ __forceinline__ FdPattern(const FdArgs &a, const Src *__restrict__ d_pat, Lds &lds) : pat((const uint8_t *)lds), m(a.m) {
+        fd_load_pattern(d_pat, lds);
+        s0 = pat[0] * 0x01010101u, s1 = pat[1] * 0x01010101u, s2 = pat[2] * 0x01010101u;
+    }
+    __device__ __forceinline__ uint32_t hits(const uint4 &v, uint32_t next, uintptr_t p, uintptr_t a0, uintptr_t ah) const {
+        return fd_hits(v, next, p, a0, ah, s0, s1, s2, m, pat);
+    }
+};
+
+// THE WALK FRAME.  The workgroup walks piece x, which lies behind `line` delimiters of the stream (counted iff
+// `delims`): act(rank, address in staging, line) for every hit, ascending inside the lane and in no order between
+// lanes.  kRanked: the piece's first hit has rank `rank`, the prefix carries the hits, and the walk ends with the row
+// that reaches `cap`; the ranks at and above cap in a word whose first hit lies below it are the action's to drop.
+// Not kRanked: the prefix carries the delimiters alone, rank and cap are not read and act's rank means nothing.
+template <bool kRanked, class M, class Act>
+__device__ __forceinline__ void fd_walk(const FdArgs &a, uint32_t x, const M &mt, bool delims, uint64_t rank, uint64_t line,
+                                        uint64_t cap, uint64_t (&wsum)[4], Act &&act) {
+    uintptr_t a0, a1, ah;
+    fd_piece(a, x, a0, a1, ah);
+    const uint32_t sd = a.delim * 0x01010101u;
+    for (uintptr_t row = a0 & ~(uintptr_t)15; row < a1 && (!kRanked || rank < cap); row += 16u * kFdThreads) {  // (the same in every lane)
+        const uintptr_t p = row + 16u * threadIdx.x;
+        uint32_t h = 0, dm = 0;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (p < a1) v = *(const uint4 *)p;
+        const uint32_t next = fd_next(v, p, a1);
+        if (p < a1) {
+            h = mt.hits(v, next, p, a0, ah);
+            if (delims) {
+                uint32_t d[4];
+                ln_word(v, sd, p, a0, a1, d);
+                dm = fd_mask16(d);
+            }
+        }
+        // (2^20 hits and 4096 delimiters a step at most)
+        const uint64_t mine = (kRanked ? (uint64_t)__popc(h) << 32 : 0u) | (uint32_t)__popc(dm);
+        uint64_t step;
+        const uint64_t ex = block_exclusive_scan256(mine, wsum, &step);
+        uint64_t r = rank + (ex >> 32);
+        const uint64_t l = line + (uint32_t)ex;
+        if (h && (!kRanked || r < cap))
+            fd_each_bit(h, [&](uint32_t b) { act(r++, p + b, l + (uint32_t)__popc(dm & ((1u << b) - 1u))); });
+        if (kRanked) rank += step >> 32;
+        line += (uint32_t)step;
+    }
 }
 
 // Workgroup i counts piece x0 + i: cnt[2 i] hits, cnt[2 i + 1] delimiters.
@@ -195,49 +268,22 @@ __global__ __launch_bounds__(kFdThreads) void k_fd_scan(const uint32_t *__restri
 }
 
 // Workgroup i writes the hits of piece x0 + i: positions[r] and lines[r] for the ranks r < cap (either array may be
-// absent).  A piece without a hit, or whose first rank is not below cap, is left at once.
+// absent).  A piece without a hit, or whose first rank is not below cap, is left at once, the pattern unloaded.
 __global__ __launch_bounds__(kFdThreads) void k_fd_write(FdArgs a, uint32_t x0, const uint32_t *__restrict__ d_pat,
                                                          const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ bases,
                                                          uint64_t *__restrict__ positions, uint64_t *__restrict__ lines,
                                                          uint64_t cap) {
-    __shared__ uint32_t pat[kFdMaxPattern / 4u];
+    __shared__ FdPattern::Lds pat;
     __shared__ uint64_t wsum[4];
-    const uint32_t tid = threadIdx.x;
-    uint64_t rank = bases[2u * (uint64_t)blockIdx.x], line = bases[2u * (uint64_t)blockIdx.x + 1u];
+    const uint64_t rank = bases[2u * (uint64_t)blockIdx.x], line = bases[2u * (uint64_t)blockIdx.x + 1u];
     if (cnt[2u * (uint64_t)blockIdx.x] == 0 || rank >= cap) return;  // (the whole workgroup)
-    fd_load_pattern(d_pat, pat);
-    const uint8_t *pb = (const uint8_t *)pat;
-    uintptr_t a0, a1, ah;
-    fd_piece(a, x0 + blockIdx.x, a0, a1, ah);
-    const uint32_t s0 = pb[0] * 0x01010101u, s1 = pb[1] * 0x01010101u, s2 = pb[2] * 0x01010101u, sd = a.delim * 0x01010101u;
-    for (uintptr_t row = a0 & ~(uintptr_t)15; row < a1; row += 16u * kFdThreads) {  // (the same in every lane)
-        const uintptr_t p = row + 16u * tid;
-        uint32_t hm = 0, dm = 0;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (p < a1) v = *(const uint4 *)p;
-        const uint32_t next = fd_next(v, p, a1);
-        if (p < a1) {
-            hm = fd_hits(v, next, p, a0, ah, s0, s1, s2, a.m, pb);
-            if (lines) {
-                uint32_t d[4];
-                ln_word(v, sd, p, a0, a1, d);
-                dm = fd_mask16(d);
-            }
-        }
-        const uint64_t mine = ((uint64_t)__popc(hm) << 32) | (uint32_t)__popc(dm);  // (4096 of either a step at most)
-        uint64_t step;
-        const uint64_t ex = block_exclusive_scan256(mine, wsum, &step);
-        uint64_t r = rank + (ex >> 32);
-        const uint64_t l = line + (uint32_t)ex;
-        for (uint32_t c = hm; c && r < cap; c &= c - 1u, r++) {
-            const uint32_t b = (uint32_t)__ffs((int)c) - 1u;
-            // (a start in the carry lies in front of staging[kFdPad]: the sum stays >= 0, carry <= base)
-            if (positions) positions[r] = a.base + (uint64_t)(p + b - (uintptr_t)a.stage) - kFdPad;
-            if (lines) lines[r] = l + (uint32_t)__popc(dm & ((1u << b) - 1u));
-        }
-        rank += step >> 32;
-        line += (uint32_t)step;
-    }
+    const FdPattern mt(a, d_pat, pat);
+    fd_walk<true>(a, x0 + blockIdx.x, mt, lines != nullptr, rank, line, cap, wsum, [&](uint64_t r, uintptr_t at, uint64_t l) {
+        if (r >= cap) return;
+        // (a start in the carry lies in front of staging[kFdPad]: the sum stays >= 0, carry <= base)
+        if (positions) positions[r] = a.base + (uint64_t)(at - (uintptr_t)a.stage) - kFdPad;
+        if (lines) lines[r] = l;
+    });
 }
 
 // One workgroup, one byte a thread: staging[src + t] -> staging[kFdPad - n + t] for t < n (the two may overlap: every

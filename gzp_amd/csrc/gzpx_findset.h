@@ -1,8 +1,9 @@
 // gzpx_findset.h -- WHERE any of a SET of byte strings occurs in a BGZF / Mgzip stream in device memory: every pair
 // (position, pattern id) at which a pattern of the set starts, ascending by position and at one position by id, the
 // line of each, and how often every pattern occurs; and WHICH lines hold a hit of any of them.  Included from
-// gzpx_kernels.hip behind gzpx_select.h: staging, the region, its pieces (fd_piece), k_fd_scan, k_fd_carry and the run
-// kernels of the selection are the single-pattern search's, unchanged.  (Definitions: include/gzpx.h.)
+// gzpx_kernels.hip behind gzpx_select.h: staging, the region, its pieces (fd_piece), the walk frame with the marking
+// pass, k_fd_scan, k_fd_carry and the run kernels of the selection are shared with the single-pattern search.
+// (Definitions: include/gzpx.h.)
 //
 // The set arrives compiled by the host (FsSet, gzpx_device.h) and is staged into LDS once per workgroup.  With
 // q = min(shortest pattern, 4), the WINDOW of a position is its first q bytes as a little-endian number.
@@ -27,10 +28,11 @@
 //               bucket, compare.  cnt[2 i] hits (of all patterns), cnt[2 i + 1] delimiters: k_fd_count's layout, so
 //               k_fd_scan runs behind it as it is.  Hits per pattern in LDS counters, flushed with one 64-bit atomicAdd
 //               per non-zero counter: only this pass counts them, so they are totals however the writing is clipped.
-//   k_fs_write  k_fd_write's walk: 256 lanes x one word a step, a block prefix of (hits << 32 | delimiters); a lane
-//               with hits walks its word again and stores positions[r], ids[r], lines[r] for r < cap.
-//   k_fs_mark   k_sl_mark's body with "some pattern of the set starts here" as the hit mask: the compare stops at the
-//               first match of a position.
+//   k_fs_write  k_fd_write's walk, written out: 256 lanes x one word a step, a block prefix of (hits << 32 |
+//               delimiters); a lane with hits walks its word again and stores positions[r], ids[r], lines[r] for
+//               r < cap.  Not on the walk frame: there it measured 1 % slower where millions of hits are written.
+//   k_fs_mark   the marking pass (sl_mark, gzpx_select.h) with FsAny, the matcher whose hit mask is "some pattern of
+//               the set starts here": the compare stops at the first match of a position.
 // No kernel's depth of dependent global loads grows with the stream.
 
 static_assert(kFdThreads == kFsMaxPatterns, "a thread clears and flushes one pattern's counter");
@@ -121,6 +123,24 @@ __device__ __forceinline__ void fs_word(const FsSet &s, const uint4 &v, uint32_t
 }
 
 __device__ __forceinline__ uint32_t fs_qmask(uint32_t q) { return q >= 4u ? 0xFFFFFFFFu : (1u << (8u * q)) - 1u; }
+
+// the matcher (gzpx_find.h) of "some pattern of the set starts here"
+struct FsAny {
+    using Src = FsSet;
+    using Lds = FsSet;
+    const FsSet &set;
+    uintptr_t end;  // of the region
+    uint32_t q, qmask;
+    __device__ __forceinline__ FsAny(const FdArgs &a, const Src *__restrict__ d_set, Lds &lds) : set(lds), end((uintptr_t)a.stage + a.r1) {
+        fs_load_set(d_set, lds);
+        q = set.hdr[kFsHdrQ], qmask = fs_qmask(q);
+    }
+    __device__ __forceinline__ uint32_t hits(const uint4 &v, uint32_t next, uintptr_t p, uintptr_t a0, uintptr_t ah) const {
+        uint32_t h = 0;
+        fs_word<true>(set, v, next, p, a0, ah, end, q, qmask, [&](uint32_t b, uint32_t) { h |= 1u << b; });
+        return h;
+    }
+};
 
 // Workgroup i counts piece x0 + i: cnt[2 i] hits, cnt[2 i + 1] delimiters; counts[k] += the hits of pattern k.
 __global__ __launch_bounds__(kFdThreads) void k_fs_count(FdArgs a, uint32_t x0, const FsSet *__restrict__ d_set,
@@ -228,45 +248,11 @@ __global__ __launch_bounds__(kFdThreads) void k_fs_write(FdArgs a, uint32_t x0, 
     }
 }
 
-// Workgroup i marks the records of the hits of piece x0 + i, as k_sl_mark does for one pattern.  A piece without a hit
-// is left at once.
+// Workgroup i marks the records of the hits of piece x0 + i.
 __global__ __launch_bounds__(kFdThreads) void k_fs_mark(FdArgs a, uint32_t x0, const FsSet *__restrict__ d_set,
                                                         const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ bases,
                                                         uint32_t *bitmap, uint64_t g, uint64_t n_records) {
     __shared__ FsSet set;
     __shared__ uint64_t wsum[4];
-    const uint32_t tid = threadIdx.x;
-    if (cnt[2u * (uint64_t)blockIdx.x] == 0) return;  // (the whole workgroup)
-    uint64_t line = bases[2u * (uint64_t)blockIdx.x + 1u];
-    fs_load_set(d_set, set);
-    const uint32_t q = set.hdr[kFsHdrQ], qmask = fs_qmask(q);
-    uintptr_t a0, a1, ah;
-    fd_piece(a, x0 + blockIdx.x, a0, a1, ah);
-    const uintptr_t end = (uintptr_t)a.stage + a.r1;
-    const uint32_t sd = a.delim * 0x01010101u;
-    uint64_t last = ~(uint64_t)0;  // the record of the lane's previous hit
-    for (uintptr_t row = a0 & ~(uintptr_t)15; row < a1; row += 16u * kFdThreads) {  // (the same in every lane)
-        const uintptr_t p = row + 16u * tid;
-        uint32_t hm = 0, dm = 0;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (p < a1) v = *(const uint4 *)p;
-        const uint32_t next = fd_next(v, p, a1);
-        if (p < a1) {
-            fs_word<true>(set, v, next, p, a0, ah, end, q, qmask, [&](uint32_t b, uint32_t) { hm |= 1u << b; });
-            uint32_t d[4];
-            ln_word(v, sd, p, a0, a1, d);
-            dm = fd_mask16(d);
-        }
-        const uint64_t mine = (uint32_t)__popc(dm);  // (only the delimiters in front of the lane are needed)
-        uint64_t step;
-        const uint64_t ex = block_exclusive_scan256(mine, wsum, &step);
-        const uint64_t l = line + ex;
-        for (uint32_t c = hm; c; c &= c - 1u) {
-            const uint32_t b = (uint32_t)__ffs((int)c) - 1u;
-            const uint64_t r = sl_record(l + (uint32_t)__popc(dm & ((1u << b) - 1u)), g);
-            if (r != last && r < n_records) atomicOr(&bitmap[r >> 5], 1u << (r & 31u));
-            last = r;
-        }
-        line += step;
-    }
+    sl_mark<FsAny>(a, x0, d_set, set, wsum, cnt, bases, bitmap, g, n_records);
 }

@@ -6105,7 +6105,7 @@ void launch_lines_find(const LnTable &tb, uint32_t n, uint32_t per, uint32_t del
                            (const uint64_t *)l.bpos, r.src, r.out_off, l.rec);
 }
 
-// The search (gzpx_find.h), behind the inflate of a batch into staging.
+// The search (gzpx_find.h, for a set gzpx_findset.h), behind the inflate of a batch into staging.
 static FdArgs find_args(const FindBatch &b, uint32_t &x0, uint32_t &grid) {
     const uint64_t r0 = kFdPad - b.carry, r1 = kFdPad + b.len;
     x0 = (uint32_t)(r0 / kFdPiece);
@@ -6113,19 +6113,27 @@ static FdArgs find_args(const FindBatch &b, uint32_t &x0, uint32_t &grid) {
     return FdArgs{b.stage, r0, r1, b.base, b.m, b.delim >= 0 ? 1u : 0u, b.delim >= 0 ? (uint32_t)b.delim : 0u};
 }
 
-void launch_find_count(const FindBatch &b, const FindScratch &f, hipStream_t stream) {
+// (mt says which matcher runs: the pattern in f.pat, or the set of gzpx_findset.h)
+void launch_find_count(const FindBatch &b, const FindScratch &f, const FindMatcher &mt, hipStream_t stream) {
     uint32_t x0, grid;
     const FdArgs a = find_args(b, x0, grid);
-    hipLaunchKernelGGL(k_fd_count, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat, f.cnt);
+    if (mt.d_set)
+        hipLaunchKernelGGL(k_fs_count, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, mt.d_set, f.cnt, (unsigned long long *)mt.d_counts);
+    else
+        hipLaunchKernelGGL(k_fd_count, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat, f.cnt);
     hipLaunchKernelGGL(k_fd_scan, dim3(1), dim3(kFdThreads), 0, stream, (const uint32_t *)f.cnt, grid, f.bases, f.rec);
 }
 
-void launch_find_write(const FindBatch &b, const FindScratch &f, uint64_t *d_positions, uint64_t *d_lines, uint64_t cap,
-                       hipStream_t stream) {
+void launch_find_write(const FindBatch &b, const FindScratch &f, const FindMatcher &mt, uint64_t *d_positions, uint32_t *d_ids,
+                       uint64_t *d_lines, uint64_t cap, hipStream_t stream) {
     uint32_t x0, grid;
     const FdArgs a = find_args(b, x0, grid);
-    hipLaunchKernelGGL(k_fd_write, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat,
-                       (const uint32_t *)f.cnt, (const uint64_t *)f.bases, d_positions, d_lines, cap);
+    if (mt.d_set)
+        hipLaunchKernelGGL(k_fs_write, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, mt.d_set, (const uint32_t *)f.cnt,
+                           (const uint64_t *)f.bases, d_positions, d_ids, d_lines, cap);
+    else
+        hipLaunchKernelGGL(k_fd_write, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat,
+                           (const uint32_t *)f.cnt, (const uint64_t *)f.bases, d_positions, d_lines, cap);
 }
 
 void launch_find_carry(const FindBatch &b, const FindScratch &f, uint32_t n, hipStream_t stream) {
@@ -6134,12 +6142,16 @@ void launch_find_carry(const FindBatch &b, const FindScratch &f, uint32_t n, hip
 }
 
 // The selection (gzpx_select.h): the marking pass behind the count and the scan of a batch, the runs behind the last.
-void launch_select_mark(const FindBatch &b, const FindScratch &f, const SelectScratch &s, uint64_t group, uint64_t n_records,
-                        hipStream_t stream) {
+void launch_select_mark(const FindBatch &b, const FindScratch &f, const FindMatcher &mt, const SelectScratch &s, uint64_t group,
+                        uint64_t n_records, hipStream_t stream) {
     uint32_t x0, grid;
     const FdArgs a = find_args(b, x0, grid);
-    hipLaunchKernelGGL(k_sl_mark, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat,
-                       (const uint32_t *)f.cnt, (const uint64_t *)f.bases, s.bitmap, group, n_records);
+    if (mt.d_set)
+        hipLaunchKernelGGL(k_fs_mark, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, mt.d_set, (const uint32_t *)f.cnt,
+                           (const uint64_t *)f.bases, s.bitmap, group, n_records);
+    else
+        hipLaunchKernelGGL(k_sl_mark, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, (const uint32_t *)f.pat,
+                           (const uint32_t *)f.cnt, (const uint64_t *)f.bases, s.bitmap, group, n_records);
 }
 
 void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n_records, uint64_t group, uint64_t n_lines,
@@ -6152,30 +6164,6 @@ void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n
     if (d_runs && cap)
         hipLaunchKernelGGL(k_sl_runs_write, dim3(groups), dim3(kSlRunThreads), 0, stream, bits, n_records, inv,
                            (const uint32_t *)s.cnt, (const uint32_t *)s.bases, group, n_lines, d_runs, cap);
-}
-
-// The search for a set (gzpx_findset.h): the single-pattern search's region, pieces, scan and scratch.
-void launch_findset_count(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_counts, hipStream_t stream) {
-    uint32_t x0, grid;
-    const FdArgs a = find_args(b, x0, grid);
-    hipLaunchKernelGGL(k_fs_count, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, d_set, f.cnt, (unsigned long long *)d_counts);
-    hipLaunchKernelGGL(k_fd_scan, dim3(1), dim3(kFdThreads), 0, stream, (const uint32_t *)f.cnt, grid, f.bases, f.rec);
-}
-
-void launch_findset_write(const FindBatch &b, const FindScratch &f, const FsSet *d_set, uint64_t *d_positions, uint32_t *d_ids,
-                          uint64_t *d_lines, uint64_t cap, hipStream_t stream) {
-    uint32_t x0, grid;
-    const FdArgs a = find_args(b, x0, grid);
-    hipLaunchKernelGGL(k_fs_write, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, d_set, (const uint32_t *)f.cnt,
-                       (const uint64_t *)f.bases, d_positions, d_ids, d_lines, cap);
-}
-
-void launch_findset_mark(const FindBatch &b, const FindScratch &f, const FsSet *d_set, const SelectScratch &s, uint64_t group,
-                         uint64_t n_records, hipStream_t stream) {
-    uint32_t x0, grid;
-    const FdArgs a = find_args(b, x0, grid);
-    hipLaunchKernelGGL(k_fs_mark, dim3(grid), dim3(kFdThreads), 0, stream, a, x0, d_set, (const uint32_t *)f.cnt,
-                       (const uint64_t *)f.bases, s.bitmap, group, n_records);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

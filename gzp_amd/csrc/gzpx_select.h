@@ -1,14 +1,13 @@
 // gzpx_select.h -- WHICH lines of a BGZF / Mgzip stream in device memory hold a byte string: the records (groups of g
 // lines) in which at least one hit of the search lies, or the records in which none does, as a table of line ranges in
 // device memory that gzpx_read_lines_table_device reads where it lies.  Included from gzpx_kernels.hip behind
-// gzpx_find.h, whose counting pass, scan and carry run unchanged in front of the marking pass.  (Definitions:
-// include/gzpx.h.)
+// gzpx_find.h, whose counting pass, scan and carry run in front of the marking pass.  (Definitions: include/gzpx.h.)
 //
-//   k_sl_mark        behind k_fd_count + k_fd_scan of a batch, one workgroup per piece, walking it as k_fd_write does:
-//                    the same fd_hits and the same block prefix of packed (hits, delimiters), so every hit's line comes
-//                    out by the same arithmetic, carry included.  Instead of storing it, the lane sets bit line / g of
-//                    the record bitmap (R bits, zeroed per call) with atomicOr -- lanes of different workgroups set bits
-//                    of one word -- and only when the record differs from that of its previous hit.
+//   k_sl_mark        behind k_fd_count + k_fd_scan of a batch, one workgroup per piece: sl_mark, the marking pass on
+//                    the walk frame (fd_walk, gzpx_find.h), so every hit's line comes out by the writing pass's
+//                    arithmetic, carry included.  Instead of storing it, the lane sets bit line / g of the record
+//                    bitmap (R bits, zeroed per call) with atomicOr -- lanes of different workgroups set bits of one
+//                    word -- and only when the record differs from that of its previous hit.
 //   k_sl_runs_count  behind the last batch: the bitmap a byte a lane, 64 bytes a workgroup.  A byte is XORed with 0xFF
 //                    under INVERT and loses the bits at and behind R; its rising edges are w & ~(w << 1 | the msb of the
 //                    byte in front).  One count of edges and one of set bits per workgroup.
@@ -30,46 +29,32 @@ __device__ __forceinline__ uint64_t sl_record(uint64_t line, uint64_t g) {
     return line / g;
 }
 
-// Workgroup i marks the records of the hits of piece x0 + i.  A piece without a hit is left at once.  (A line at or
-// behind L -- the stream is not the one the line table was built from -- has no bit.)
+// The marking pass of piece x0 + i by workgroup i, for the matcher M: the records of its hits.  A piece without a hit is
+// left at once, the matcher unloaded.  No rank is needed: the walk is not ranked, and its prefix carries the delimiters
+// alone.  Delimiters are always marked.  (A line at or behind L -- the stream is not the one the line table was built
+// from -- has no bit.)
+template <class M>
+__device__ __forceinline__ void sl_mark(const FdArgs &a, uint32_t x0, const typename M::Src *__restrict__ src, typename M::Lds &lds,
+                                        uint64_t (&wsum)[4], const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ bases,
+                                        uint32_t *bitmap, uint64_t g, uint64_t n_records) {
+    if (cnt[2u * (uint64_t)blockIdx.x] == 0) return;  // (the whole workgroup)
+    const M mt(a, src, lds);
+    uint64_t last = ~(uint64_t)0;  // the record of the lane's previous hit
+    fd_walk<false>(a, x0 + blockIdx.x, mt, true, 0, bases[2u * (uint64_t)blockIdx.x + 1u], 0, wsum,
+            [&](uint64_t, uintptr_t, uint64_t line) {
+                const uint64_t r = sl_record(line, g);
+                if (r != last && r < n_records) atomicOr(&bitmap[r >> 5], 1u << (r & 31u));
+                last = r;
+            });
+}
+
+// Workgroup i marks the records of the hits of piece x0 + i.
 __global__ __launch_bounds__(kFdThreads) void k_sl_mark(FdArgs a, uint32_t x0, const uint32_t *__restrict__ d_pat,
                                                         const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ bases,
                                                         uint32_t *bitmap, uint64_t g, uint64_t n_records) {
-    __shared__ uint32_t pat[kFdMaxPattern / 4u];
+    __shared__ FdPattern::Lds pat;
     __shared__ uint64_t wsum[4];
-    const uint32_t tid = threadIdx.x;
-    if (cnt[2u * (uint64_t)blockIdx.x] == 0) return;  // (the whole workgroup)
-    uint64_t line = bases[2u * (uint64_t)blockIdx.x + 1u];
-    fd_load_pattern(d_pat, pat);
-    const uint8_t *pb = (const uint8_t *)pat;
-    uintptr_t a0, a1, ah;
-    fd_piece(a, x0 + blockIdx.x, a0, a1, ah);
-    const uint32_t s0 = pb[0] * 0x01010101u, s1 = pb[1] * 0x01010101u, s2 = pb[2] * 0x01010101u, sd = a.delim * 0x01010101u;
-    uint64_t last = ~(uint64_t)0;  // the record of the lane's previous hit
-    for (uintptr_t row = a0 & ~(uintptr_t)15; row < a1; row += 16u * kFdThreads) {  // (the same in every lane)
-        const uintptr_t p = row + 16u * tid;
-        uint32_t hm = 0, dm = 0;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (p < a1) v = *(const uint4 *)p;
-        const uint32_t next = fd_next(v, p, a1);
-        if (p < a1) {
-            hm = fd_hits(v, next, p, a0, ah, s0, s1, s2, a.m, pb);
-            uint32_t d[4];
-            ln_word(v, sd, p, a0, a1, d);
-            dm = fd_mask16(d);
-        }
-        const uint64_t mine = ((uint64_t)__popc(hm) << 32) | (uint32_t)__popc(dm);  // (4096 of either a step at most)
-        uint64_t step;
-        const uint64_t ex = block_exclusive_scan256(mine, wsum, &step);
-        const uint64_t l = line + (uint32_t)ex;
-        for (uint32_t c = hm; c; c &= c - 1u) {
-            const uint32_t b = (uint32_t)__ffs((int)c) - 1u;
-            const uint64_t r = sl_record(l + (uint32_t)__popc(dm & ((1u << b) - 1u)), g);
-            if (r != last && r < n_records) atomicOr(&bitmap[r >> 5], 1u << (r & 31u));
-            last = r;
-        }
-        line += (uint32_t)step;
-    }
+    sl_mark<FdPattern>(a, x0, d_pat, pat, wsum, cnt, bases, bitmap, g, n_records);
 }
 
 // byte k of the bitmap as the runs see it: inverted where asked, the bits at and behind R cleared

@@ -340,9 +340,25 @@ def lines_close_the_loop(lib):
 
 
 # ------------------------------------------------------------------------------------------------ 4. capacity
+def capacity_text():
+    """line_text three times over (27 KiB): with the default batch its hits lie in two pieces of staging, on both sides of
+    the first row of the second."""
+    return line_text(NL, True)[0] * 3
+
+
+def piece_caps(starts):
+    """Two values of hits_cap that end the writing inside the stream's second piece, from the host's ascending starts of
+    the hits; they hold for one batch (the default), where byte p of the stream lies at PAD + p of staging.  The hits in
+    front of staging offset T: piece 1's first rank equals the cap, and its workgroup leaves before the walk.  The hits in
+    front of T + 4096: the cap is reached when piece 1's first row of 256 words is done, and the walk leaves its loop."""
+    caps = [int(np.searchsorted(starts, at - PAD, side="left")) for at in (T, T + 4096)]
+    assert 1 < caps[0] < caps[1] < len(starts) - 1, caps
+    return caps
+
+
 def capacity(lib):
     mem = Mem(lib)
-    text, _ = line_text(NL, True)
+    text = capacity_text()
     for fmt in (BGZF, MGZIP):
         s = cut(fmt, text, [40, 5000])
         pl = Plain(fmt, s)
@@ -355,7 +371,9 @@ def capacity(lib):
                     o.d.set_lines_batch(batch)
                     assert o.count(pattern) == n and o.count(pattern, NL) == n
                     assert o.d.find_device(o.ix, o.ptr, o.n, pattern, None, None, None, 3) == n  # (count only: hits_cap is ignored)
-                    for cap in (n, n + 3, n - 1, 1, 0):
+                    # (piece_caps: at batch 0 they end the writing inside the second piece -- the workgroup's early return, the walk's
+                    # early out; at batch 5000 staging is laid out otherwise and they are two more values)
+                    for cap in [n, n + 3, n - 1, 1, 0] + piece_caps(hits):
                         for positions, lines_ in ((True, True), (True, False), (False, True)):
                             got, pos, ln = o.find(pattern, NL, cap, positions, lines_)
                             what = (fmt, pattern, batch, cap, positions, lines_)

@@ -392,7 +392,7 @@ def lines_close_the_loop(lib):
 # ------------------------------------------------------------------------------------------------ 10. capacity
 def capacity(lib):
     mem = Mem(lib)
-    text, _ = find_cases.line_text(NL, True)
+    text = find_cases.capacity_text()
     patterns = [b"HIT", b"qu", b"HIT\n", b"zz"]
     for fmt in (BGZF, MGZIP):
         s = cut(fmt, text, [40, 5000])
@@ -406,7 +406,9 @@ def capacity(lib):
                 assert o.count(patterns, NL)[0] == n
                 # (count only: hits_cap is ignored)
                 assert o.d.find_set_device(o.ix, o.ptr, o.n, patterns, None, None, None, None, 3) == n
-                for cap in (n, n + 3, n - 1, 1, 0):
+                # (piece_caps: at batch 0 they end the writing inside the second piece -- the workgroup's early return, the walk's
+                # early out; at batch 5000 staging is laid out otherwise and they are two more values)
+                for cap in [n, n + 3, n - 1, 1, 0] + find_cases.piece_caps(pos):
                     for subset in itertools.product((True, False), repeat=3):
                         if not any(subset):
                             continue

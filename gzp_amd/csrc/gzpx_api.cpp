@@ -1671,6 +1671,30 @@ int dslot_prepare(gzpx_dctx *c, DSlot &sl, size_t nb, int route, size_t cap, uin
     return route == kInflateRouteSeg && writes ? dslot_seg_scratch(sl, cap, nb) : GZPX_OK;
 }
 
+// What an inflate launch takes from the context and from a slot that dslot_prepare has made ready (InflateLaunch): the
+// caller adds where the compressed bytes lie and where the output goes (the sizes call: nowhere).
+InflateLaunch inflate_launch_of(const gzpx_dctx *c, const DSlot &sl, const uint8_t *d_in, uint64_t *d_out_off, uint8_t *d_out,
+                                size_t out_cap) {
+    InflateLaunch l;
+    l.d_in = d_in;
+    l.nb = (uint32_t)sl.nb;
+    l.d_blk = sl.d_blk;
+    l.d_out_off = d_out_off;
+    l.d_out = d_out;
+    l.out_cap = out_cap;
+    l.d_check = sl.d_crc;
+    l.debug = sl.debug;
+    l.route = sl.route;
+    l.ev_begin = sl.ev_t0;
+    l.ev_mid = sl.ev_tm;
+    l.ev_end = sl.ev_t1;
+    l.ev_check = sl.ev_tc;
+    l.stream = c->stream;
+    l.sc = &sl.sc;
+    l.cc = &c->cc;
+    return l;
+}
+
 // The framed inflate, enqueued on the context's stream: the slot made ready, nb members of d_in, listed by the device
 // tables `offsets` / `sizes`, into dst[0..cap) back to back, and k_dsummary's words (what the host needs of the members'
 // records: summary_verdict) on their way to sl.h_summary.  `ev_before`, if any, is recorded in front of the kernels.
@@ -1678,8 +1702,7 @@ int inflate_enqueue(gzpx_dctx *c, DSlot &sl, const uint8_t *d_in, const uint64_t
                     uint8_t *dst, size_t cap, uint64_t in_bytes, hipEvent_t ev_before = nullptr) {
     GZPX_TRY(dslot_prepare(c, sl, nb, c->route, cap, in_bytes));
     if (ev_before) HIP_TRY(hipEventRecord(ev_before, c->stream));
-    launch_inflate(header_bytes(c->format), d_in, offsets, sizes, (uint32_t)nb, sl.d_blk, sl.d_out_off, dst, cap, sl.d_crc, c->cc,
-                   c->debug, sl.ev_t0, sl.ev_t1, c->stream, sl.sc, sl.route, sl.ev_tm);
+    launch_inflate(inflate_launch_of(c, sl, d_in, sl.d_out_off, dst, cap), header_bytes(c->format), offsets, sizes);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kDsHostWords * 4, hipMemcpyDeviceToHost, c->stream));
     return GZPX_OK;
@@ -2408,10 +2431,8 @@ int gzpx_inflate_batch_device(gzpx_dctx *c, int wrap, unsigned flags, const void
     // (fewer bytes than the slot are k_inflate's to see; the sizes are on the device: the input stands for their sum)
     GZPX_TRY(dslot_prepare(c, sl, n, short_ok ? (int)kInflateRouteWave : c->route, out_cap, in_len));
     // the slot's own size table is free here (the caller's is read where it lies): it holds the members' slots
-    launch_inflate_batch(wrap, short_ok ? 1 : 0, (const uint8_t *)d_in, in_len, d_in_offsets, d_in_sizes, d_out_sizes,
-                         (uint32_t)n, sl.d_blk, sl.d_sizes, sl.d_out_off, (uint8_t *)d_out, out_cap, sl.d_crc, c->cc,
-                         c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, d_out_offsets, d_results, sl.ev_tm,
-                         sl.ev_tc);
+    launch_inflate_batch(inflate_launch_of(c, sl, (const uint8_t *)d_in, sl.d_out_off, (uint8_t *)d_out, out_cap), wrap,
+                         short_ok ? 1 : 0, in_len, d_in_offsets, d_in_sizes, d_out_sizes, sl.d_sizes, d_out_offsets, d_results);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
     GZPX_TRY(debug_records(c, sl, n));
@@ -2447,8 +2468,8 @@ int gzpx_inflate_batch_sizes_device(gzpx_dctx *c, int wrap, const void *d_in, si
     Drain drain{{stream}, 1};
     // (nothing is inflated: a capacity of 0 and no scratch of the decode / copy pair; the input stands for the members' sum)
     GZPX_TRY(dslot_prepare(c, sl, n, c->route, 0, in_len, false));
-    launch_inflate_sizes(wrap, (const uint8_t *)d_in, in_len, d_in_offsets, d_in_sizes, max_out_size, (uint32_t)n, sl.d_blk,
-                         c->debug, sl.ev_t0, sl.ev_t1, stream, sl.sc, sl.route, d_out_sizes, d_in_used, d_results, sl.ev_tm);
+    launch_inflate_sizes(inflate_launch_of(c, sl, (const uint8_t *)d_in, nullptr, nullptr, 0), wrap, in_len, d_in_offsets,
+                         d_in_sizes, max_out_size, d_out_sizes, d_in_used, d_results);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(sl.h_summary, sl.sc.summary, kWrRecHostWords * 4, hipMemcpyDeviceToHost, stream));
     GZPX_TRY(debug_records(c, sl, n));

@@ -1,6 +1,6 @@
 // gzpx_cksum.h -- checksums of a table of device-resident buffers (gzpx_checksum_batch_device): CRC-32, CRC-32C and
 // Adler-32 of n entries of one input, tables in, sums out.  Included from gzpx_kernels.hip, namespace gzpx, behind
-// gzpx_wrap.h (adler_workgroup, the status values of a report) and gzpx_crc.h (the CRC arithmetic).
+// gzpx_wrap.h (adler_workgroup, the status values of a report) and gzpx_wave.h (gzpx_crc.h: the CRC arithmetic; the scans).
 //
 // The work is cut into 64 KiB tiles counted from every entry's first byte, and the tiles of all entries form one flat
 // index space, so that a table of one 2 GiB entry and a table of 30,000 small ones load the device alike:

@@ -1,6 +1,7 @@
 // gzpx_crc.h -- the CRC arithmetic of the library, once: CRC-32 (gzip) and CRC-32C (Snap, the batch checksums), both
-// reflected, the polynomial a template argument.  Included by gzpx_kernels.hip inside namespace gzpx, in front of the
-// first CRC routine and with GZPX_CRC_KERNELS defined, and by gzpx_api.cpp for the host half alone.
+// reflected, the polynomial a template argument.  Two includers.  gzpx_wave.h, inside namespace gzpx, behind dword4 and
+// with GZPX_CRC_KERNELS defined: that puts it in front of every kernel of gzpx_kernels.hip and of every header included
+// there.  gzpx_api.cpp, for the host half alone.
 //
 //   host and device   crc_mulmod<P> (the one GF(2) product), CrcPow / crc_pow_table<P> / crc_xpow8<P> (the one power table
 //                     and x^(8 m) out of it)

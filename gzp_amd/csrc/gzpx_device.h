@@ -236,27 +236,39 @@ enum { kDsSegHint = 15, kDsWords = 16 };
 enum { kInflateRouteSeg = 0, kInflateRouteWave = 1 };  // k_inflate_seg + k_lzcopy (default) | k_inflate for every member
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb);
 size_t inflate_tfirst_bytes(uint64_t out_cap, uint64_t nb);
-void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes,
-                    uint32_t nb, void *d_blk, uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap,
-                    uint32_t *d_crc_found, const CrcConsts &cc, int debug, hipEvent_t ev_begin,
-                    hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc, int route, hipEvent_t ev_mid = nullptr);
+// What the three inflate launches below have in common: each adds the tables that are its own.
+struct InflateLaunch {
+    const uint8_t *d_in = nullptr;  // the compressed bytes the tables point into
+    uint32_t nb = 0;                // members
+    void *d_blk = nullptr;          // [nb] their records (DBlockHost)
+    uint64_t *d_out_off = nullptr;  // [nb + 1] where each member's output starts in d_out, the total
+    uint8_t *d_out = nullptr;       // [out_cap] (the sizes call: no offsets, no output, a capacity of 0)
+    uint64_t out_cap = 0;
+    uint32_t *d_check = nullptr;    // [nb] the checksum found for each member
+    int debug = 0;                  // which kernels carry their clocks (launch_inflate_members, gzpx_kernels.hip)
+    int route = kInflateRouteSeg;
+    // optional; recorded in front of the members' kernels, behind k_inflate_seg (the decode / copy route alone), behind
+    // the members' kernels, and behind the check kernel (launch_inflate_batch alone)
+    hipEvent_t ev_begin = nullptr, ev_mid = nullptr, ev_end = nullptr, ev_check = nullptr;
+    hipStream_t stream = nullptr;
+    const InflateScratch *sc = nullptr;
+    const CrcConsts *cc = nullptr;
+};
+// The framed members of a stream (the header is hdr_len bytes), listed by d_offsets / d_sizes; sc.summary gets
+// k_dsummary's record (kDs*).
+void launch_inflate(const InflateLaunch &l, uint32_t hdr_len, const uint64_t *d_offsets, const uint32_t *d_sizes);
 
 // A batch of independent members in a raw / zlib / gzip wrapper (gzpx_wrap.h): the table and every result in device
 // memory; sc.summary gets k_dresult's record (kWrRec*).
-void launch_inflate_batch(int wrap, int short_ok, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets,
-                          const uint32_t *d_sizes, const uint32_t *d_out_sizes, uint32_t nb, void *d_blk, uint32_t *d_slot,
-                          uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap, uint32_t *d_check, const CrcConsts &cc,
-                          int debug, hipEvent_t ev_begin, hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc,
-                          int route, uint64_t *d_user_off, void *d_results, hipEvent_t ev_mid = nullptr,
-                          hipEvent_t ev_check = nullptr);  // (ev_end .. ev_check: the check kernel)
+void launch_inflate_batch(const InflateLaunch &l, int wrap, int short_ok, uint64_t in_len, const uint64_t *d_offsets,
+                          const uint32_t *d_sizes, const uint32_t *d_out_sizes, uint32_t *d_slot, uint64_t *d_user_off,
+                          void *d_results);
 
 // The sizes of such a batch (gzpx_inflate_batch_sizes_device): the count-only inflate kernels; d_out_sizes [nb] is
 // written, d_in_used [nb] and d_results [nb] if given, sc.summary gets k_dresult_sizes' record (kWrRec*, [6..7] the sum
 // of the good members' sizes).  Of `sc` only redo, summary, n_cu and in_bytes are used.  max_out 0: no cap below 2^32.
-void launch_inflate_sizes(int wrap, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
-                          uint32_t max_out, uint32_t nb, void *d_blk, int debug, hipEvent_t ev_begin, hipEvent_t ev_end,
-                          hipStream_t stream, const InflateScratch &sc, int route, uint32_t *d_out_sizes, uint32_t *d_in_used,
-                          void *d_results, hipEvent_t ev_mid = nullptr);
+void launch_inflate_sizes(const InflateLaunch &l, int wrap, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
+                          uint32_t max_out, uint32_t *d_out_sizes, uint32_t *d_in_used, void *d_results);
 
 // Checksums of a table of buffers (gzpx_cksum.h, gzpx_checksum_batch_device): CRC-32 / Adler-32 / CRC-32C (`kind`:
 // GZPX_CHECK_*) of n entries of d_in -- entry i is [off[i], off[i] + size[i]), or [off[i], off[i + 1]) with d_sizes null.

@@ -1,6 +1,7 @@
 // gzpx_inflate_seg.h -- the two-kernel form of ParDecompress's decode_block (src/par/decompress.rs:162-186,
 // src/bgzf.rs:151-170: libdeflate_deflate_decompress of one member).  Included by gzpx_kernels.hip inside
-// namespace gzpx, behind k_inflate (whose DBlock and status codes it shares).
+// namespace gzpx, behind k_inflate (whose DBlock and status codes it shares) and gzpx_wave.h (dword4,
+// gzpx_deflate.h with its wave routines, gzpx_crc.h, the scans).
 //
 //   k_inflate_seg  Huffman decode only: bitstream -> literal bytes in place + a list of (position, length,
 //                  distance) records; it never reads the window.  One wave per member.  The bits of a DEFLATE

@@ -40,160 +40,18 @@
 // splitting), levels 5-9 for k_match_hc / k_parse_lazy (the lazy and lazy2 parsers); ParDecompress
 // is k_dinit / k_dscan / k_inflate / k_dcrc32.
 // Integer/byte work only: no MFMA; the path is bound by instruction issue, then LDS.
+//
+// What more than one stage or more than one of the headers included below uses -- wave_sync, the scans, dword4, the
+// experiment counters, and through it gzpx_deflate.h and gzpx_crc.h -- is in gzpx_wave.h, in front of them all.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <cstring>
 
 #include "gzpx_device.h"
 
-// Measurement-only switches (tools/exp_bounds.py builds a second library with -DGZPX_EXPERIMENT; the
-// product build compiles them away): parts of a kernel are skipped -- the results are wrong on purpose
-// -- to see which resource bounds it.
-#ifdef GZPX_EXPERIMENT
-#define GZPX_EXP(cfg, bit) (((cfg).debug >> (bit)) & 1u)
-#else
-#define GZPX_EXP(cfg, bit) 0u
-#endif
-
 namespace gzpx {
 
-// ------------------------------------------------------------------------------------------
-// small device helpers
-// ------------------------------------------------------------------------------------------
-
-// Rendezvous + ordering point for the lanes of ONE wave that communicate through LDS.  LDS
-// operations of a wave execute in issue order, so no hardware wait is needed -- only the
-// compiler must not move LDS accesses across it.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-}
-
-// a value that is the same in every lane, moved to a scalar register (wave-uniform state that
-// comes out of LDS would otherwise occupy a VGPR in every lane)
-__device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-// keep a finished value in a VGPR here (stops the compiler from sinking its computation to the use)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define GZPX_PIN_VGPR(x) asm volatile("" : "+v"(x))
-#else
-#define GZPX_PIN_VGPR(x) ((void)0)
-#endif
-
-// last statement of one arm of a branch whose arms end alike: keeps the compiler from sinking the like
-// tails into one copy behind the branch (which would turn this arm's immediate offsets into selected addresses)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define GZPX_KEEP_ARM_APART() asm volatile("")
-#else
-#define GZPX_KEEP_ARM_APART() ((void)0)
-#endif
-
-__device__ __forceinline__ uint32_t lz_hash15(uint32_t v) { return (v * 0x1E35A7BDu) >> 17; }
-
-// little-endian u32 at an arbitrary byte address of global memory via two aligned loads
-__device__ __forceinline__ uint32_t load_le32_global(const uint8_t *p) {
-    const uintptr_t a = (uintptr_t)p;
-    const uint32_t *w = (const uint32_t *)(a & ~(uintptr_t)3);
-    return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(a & 3));
-}
-
-__device__ __forceinline__ uint32_t wave_reduce_add(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, unsigned lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d);
-        if (lane >= (unsigned)d) v += t;
-    }
-    return v;
-}
-
-// wave-wide inclusive scans on the DPP network (row shifts, then the row broadcasts of gfx9)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_zero(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-    v += dpp_zero<0x111, 0xf>(v);
-    v += dpp_zero<0x112, 0xf>(v);
-    v += dpp_zero<0x114, 0xf>(v);
-    v += dpp_zero<0x118, 0xf>(v);
-    v += dpp_zero<0x142, 0xa>(v);
-    v += dpp_zero<0x143, 0xc>(v);
-    return v;
-}
-__device__ __forceinline__ uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
-    v = umax32(v, dpp_zero<0x111, 0xf>(v));
-    v = umax32(v, dpp_zero<0x112, 0xf>(v));
-    v = umax32(v, dpp_zero<0x114, 0xf>(v));
-    v = umax32(v, dpp_zero<0x118, 0xf>(v));
-    v = umax32(v, dpp_zero<0x142, 0xa>(v));
-    v = umax32(v, dpp_zero<0x143, 0xc>(v));
-    return v;
-}
-
-// Exclusive scan of one value per thread over a workgroup of NW waves; `wsum` is NW words of LDS.
-// Returns the exclusive prefix; *total receives the workgroup sum.  Two barriers.
-template <unsigned NW>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *wsum, uint32_t *total) {
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t inc = wave_incl_add(v);
-    __syncthreads();  // protect wsum from the previous use
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    // the wave totals: one LDS read per lane and a second DPP scan (NW <= 64) instead of NW reads and
-    // 2 NW additions in every lane
-    const uint32_t mine = lane < NW ? wsum[lane] : 0u;
-    const uint32_t winc = wave_incl_add(mine);
-    *total = rdlane(winc, NW - 1);
-    const uint32_t base = wave ? rdlane(winc, wave - 1) : 0u;
-    return base + inc - v;
-}
-
-// Exclusive scan of one 64-bit value per thread over a 256-thread workgroup; `wsum` is 4 words of
-// LDS.  Returns the exclusive prefix; *total receives the workgroup sum.  Two barriers.  (64-bit:
-// 256 Mgzip blocks of 16 MiB, or foreign ISIZE fields, sum to 2^32 and more.)
-__device__ __forceinline__ uint64_t block_exclusive_scan256(uint64_t v, uint64_t *wsum, uint64_t *total) {
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint64_t inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(inc, d);
-        if (lane >= (unsigned)d) inc += t;
-    }
-    __syncthreads();  // protect wsum from the previous use
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint64_t base = 0, tot = 0;
-    for (unsigned w = 0; w < 4; w++) {
-        const uint64_t s = wsum[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    *total = tot;
-    return base + inc - v;
-}
-
-// RFC 1951's alphabets, the precode order, the fixed code, the dynamic header's fields and the canonical-code steps
-#define GZPX_DEFLATE_WAVE
-#include "gzpx_deflate.h"
-
-// The two token consumers (k_hist, k_emit) look lengths up in a 256-entry LDS table of length - 3.  k_hist keeps
-// slot | extra-bit count << 5 (length_entry); k_emit builds, from the same entries, the codeword and extra bits of
-// every length for each sub-block.
-__device__ __forceinline__ uint32_t length_entry(uint32_t x) {
-    const DeflateSlot s = length_slot(x + 3);
-    return s.slot | (s.xbits << 5);
-}
-__device__ __forceinline__ void build_length_table(uint8_t *lslot, uint32_t tid) {
-    if (tid < 256) lslot[tid] = (uint8_t)length_entry(tid);
-}
+#include "gzpx_wave.h"
 
 // ------------------------------------------------------------------------------------------
 // k_init_meta: cut the slab into blocks the way ParCompress::write / flush_last do
@@ -222,10 +80,10 @@ __device__ __forceinline__ BlockMeta block_meta_of(const Config &cfg, uint64_t s
 __global__ void k_init_meta(Config cfg, uint64_t slab_len, uint32_t nb, uint32_t is_last,
                             BlockMeta *meta, uint32_t *redo) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b == 0 && redo) {
-        redo[0] = 0;       // members handed back to k_inflate
-        redo[1 + nb] = 0;  // k_inflate_seg's ticket counter
-    }        // level 1: nothing handed back to the dense kernels yet
+    // Scratch.redo[0] counts the blocks on the encode side's hand-back list (level 1: from k_mparse to the dense pair;
+    // levels 3-4: the stale ones, from k_parse_hc to k_match_hc_stale).  The levels that come here read no such list;
+    // the list is left empty, as the first k_candidates launch leaves it at the others.
+    if (b == 0 && redo) redo[0] = 0;
     if (b >= nb) return;
     meta[b] = block_meta_of(cfg, slab_len, nb, is_last, b);
 }
@@ -604,11 +462,6 @@ constexpr uint32_t kSeg = 272;
 constexpr uint32_t kInWords = kTile / 4 + 132;  // 64 KiB window + max match + alignment slack
 constexpr uint32_t kMpThreads = 1024;
 constexpr uint32_t kMpWaves = kMpThreads / 64;
-
-// four dwords that are only dword-aligned in global memory (the hardware takes such 16-byte loads)
-struct __attribute__((aligned(4))) dword4 {
-    uint32_t x, y, z, w;
-};
 
 // (two aligned reads + v_alignbyte on purpose: gfx950 accepts an under-aligned ds_read_b32, and the
 // compiler emits one for a packed load, but it is slow -- k_match took 5.85 ms instead of 2.03 with it)
@@ -1226,15 +1079,6 @@ __global__ __launch_bounds__(kMpThreads, 8) void k_parse(
 constexpr uint32_t kMpMaxRounds = 24;
 constexpr uint32_t kMhHalf = 32768;  // positions per pass (their d0: 64 KiB of LDS)
 constexpr uint32_t kMhSeg = kMhHalf / kMpThreads;  // 32 positions per walk segment = one 32-bit mask
-#ifdef GZPX_EXPERIMENT
-// k_huffman: setup, litlen code, offset code, precode RLE, precode code, costs, header + tables (rows as below)
-__device__ unsigned long long g_exp_huff[1024 * 8];
-// k_mparse: stage, first walk, later rounds, settle, build, barrier rounds, re-walks (x 1024 rows, a
-// block adds to row blockIdx & 1023: same-address atomics serialise at the L2)
-__device__ unsigned long long g_exp_cycles[1024 * 8];
-// k_match_hc_sparse: window, first nodes, walks, lists, searches (cycles); rounds, listed searches, tiles (counts)
-__device__ unsigned long long g_exp_sparse[1024 * 8];
-#endif
 
 // ht_matchfinder_longest_match at block position p (block byte i sits at LDS byte i + mis; d0_h[i] =
 // d0 of position hb + i).  Returns the match length (0 = none); `older` = the bucket's older entry won.
@@ -4229,9 +4073,6 @@ __global__ __launch_bounds__(64, GZPX_HUFF_WAVES) void k_huffman(Config cfg, Blo
 // crc(A||B) = crc(A) * x^(8|B|) mod P  xor  crc(B), with |B| = 64 * 2^level at every level.
 // crc32_direct (k_crc32): 256 threads, 256-byte segments read straight from global memory, the same tree.
 // ------------------------------------------------------------------------------------------
-#define GZPX_CRC_KERNELS
-#include "gzpx_crc.h"
-
 constexpr uint32_t kCrcThreads = 1024;  // one 64-byte segment per thread and chunk (k_dcrc32)
 constexpr uint32_t kCrcSmall = 256;     // the compressor's k_crc32: one 256-byte segment per thread and chunk
 constexpr uint32_t kCrcSeg = 64;        // bytes per thread and chunk of crc32_workgroup
@@ -5719,7 +5560,7 @@ extern "C" int gzpx_exp_sparse(unsigned long long out[8], int reset) { return ex
 void launch_match(const Config &cfg, const uint8_t *slab, uint64_t slab_len, uint32_t nb, const Scratch &s,
                   hipStream_t stream) {
     const bool fused = level1_fused(cfg);
-    if (fused) {  // (k_init_meta has emptied the redo list)
+    if (fused) {  // (the batch's first k_candidates launch has emptied the redo list)
         const uint32_t wgs = cfg.n_cu ? cfg.n_cu : 256u;  // one per CU, each walking its share of the blocks
         hipLaunchKernelGGL(k_mparse, dim3(nb < wgs ? nb : wgs), dim3(kMpThreads), 0, stream, cfg, slab, s.meta, s.sub,
                            (const uint16_t *)s.cand, s.tok, s.redo, slab_len, nb, s.claim + 0);
@@ -5838,140 +5679,119 @@ static SegLaunch seg_launch_of(const InflateScratch &sc, uint32_t nb) {
     return {big, nb < wgs ? nb : wgs, sc.summary ? sc.summary + kDsSegHint : nullptr};
 }
 
-// The decode of nb members whose records and output offsets are in place (k_dinit + k_dscan, or k_dinit_wrap +
-// k_dscan_slots): k_inflate_seg + k_lzcopy + k_inflate over the redo list, or k_inflate for every member.  The
-// template arguments say which of the three kernels carries its clocks.
-template <bool SEG_DBG, bool LC_DBG, bool INF_DBG>
-static void launch_inflate_members_as(const uint8_t *d_in, uint32_t nb, DBlock *blk, uint64_t *d_out_off, uint8_t *d_out,
-                                      uint64_t out_cap, uint32_t *d_crc_found, const CrcConsts &cc, hipStream_t stream,
-                                      const InflateScratch &sc, bool seg, hipEvent_t ev_mid) {
+// The decode of l.nb members whose records are in place (k_dinit + k_dscan, k_dinit_wrap + k_dscan_slots, or
+// k_dinit_wrap_sizes): k_inflate_seg + k_lzcopy + k_inflate over the redo list, or k_inflate for every member.  The
+// first three template arguments say which of the three kernels carries its clocks.  COUNT: the count-only forms of
+// the inflate kernels (gzpx_inflate_batch_sizes_device) -- nothing but the compressed bytes is read, and nothing written
+// but the records: the launch has no output, and the match list, the tile table and k_lzcopy have no part in it
+// (sc.mlist / sc.tfirst are not looked at).
+template <bool SEG_DBG, bool LC_DBG, bool INF_DBG, bool COUNT>
+static void launch_inflate_members_as(const InflateLaunch &l, DBlock *blk, bool seg) {
+    const InflateScratch &sc = *l.sc;
+    const uint64_t *out_off = l.d_out_off;
+    hipStream_t stream = l.stream;
     if (!seg) {
-        hipLaunchKernelGGL((k_inflate<INF_DBG>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)d_out_off, d_out,
-                           out_cap, (const uint32_t *)nullptr);
+        hipLaunchKernelGGL((k_inflate<INF_DBG, COUNT>), dim3(l.nb), dim3(64), 0, stream, l.d_in, blk, out_off, l.d_out, l.out_cap,
+                           (const uint32_t *)nullptr);
         return;
     }
     // decode (literals + match records), LZ copy, then k_inflate over whatever the two left on the redo list
-    LzMatch *ml = (LzMatch *)sc.mlist;
-    const SegLaunch sl = seg_launch_of(sc, nb);
+    LzMatch *ml = COUNT ? nullptr : (LzMatch *)sc.mlist;
+    uint32_t *tfirst = COUNT ? nullptr : sc.tfirst;
+    const SegLaunch sl = seg_launch_of(sc, l.nb);
     if (sl.big)
-        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegBigW>), dim3(sl.grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
-                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, sl.hint);
+        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegBigW, COUNT>), dim3(sl.grid), dim3(64 * kSegBigW), 0, stream, l.d_in, blk,
+                           out_off, l.d_out, l.out_cap, ml, tfirst, sc.redo, l.nb, sl.hint);
     else
-        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegSmallW>), dim3(sl.grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
-                           (const uint64_t *)d_out_off, d_out, out_cap, ml, sc.tfirst, sc.redo, nb, sl.hint);
-    if (ev_mid) (void)hipEventRecord(ev_mid, stream);
+        hipLaunchKernelGGL((k_inflate_seg<SEG_DBG, kSegSmallW, COUNT>), dim3(sl.grid), dim3(64 * kSegSmallW), 0, stream, l.d_in, blk,
+                           out_off, l.d_out, l.out_cap, ml, tfirst, sc.redo, l.nb, sl.hint);
+    if (l.ev_mid) (void)hipEventRecord(l.ev_mid, stream);
     if (SEG_DBG || LC_DBG)  // (a debug launch: why each member was handed back, InflateHandback)
-        hipLaunchKernelGGL(k_seg_reasons, dim3((nb + 255) / 256), dim3(256), 0, stream, (const DBlock *)blk, sc.redo, nb, SEG_DBG ? 1u : 0u);
-    hipLaunchKernelGGL((k_lzcopy<LC_DBG>), dim3(nb), dim3(kLcThreads), 0, stream, blk, (const uint64_t *)d_out_off, d_out,
-                       (const LzMatch *)ml, (const uint32_t *)sc.tfirst, sc.redo, d_crc_found, cc);
-    hipLaunchKernelGGL((k_inflate<INF_DBG>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)d_out_off, d_out,
-                       out_cap, (const uint32_t *)sc.redo);
+        hipLaunchKernelGGL(k_seg_reasons, dim3((l.nb + 255) / 256), dim3(256), 0, stream, (const DBlock *)blk, sc.redo, l.nb,
+                           SEG_DBG ? 1u : 0u);
+    if (!COUNT)
+        hipLaunchKernelGGL((k_lzcopy<LC_DBG>), dim3(l.nb), dim3(kLcThreads), 0, stream, blk, out_off, l.d_out,
+                           (const LzMatch *)ml, (const uint32_t *)tfirst, sc.redo, l.d_check, *l.cc);
+    hipLaunchKernelGGL((k_inflate<INF_DBG, COUNT>), dim3(l.nb), dim3(64), 0, stream, l.d_in, blk, out_off, l.d_out, l.out_cap,
+                       (const uint32_t *)sc.redo);
 }
 
 // debug 1: k_inflate_seg's and k_inflate's clocks; 2: k_lzcopy's instead.  The k_inflate route has one kernel to
-// instrument and does so for any non-zero value.
-static void launch_inflate_members(const uint8_t *d_in, uint32_t nb, DBlock *blk, uint64_t *d_out_off, uint8_t *d_out,
-                                   uint64_t out_cap, uint32_t *d_crc_found, const CrcConsts &cc, int debug,
-                                   hipStream_t stream, const InflateScratch &sc, bool seg, hipEvent_t ev_mid) {
-    if (debug == 1 || (debug && !seg))
-        launch_inflate_members_as<true, false, true>(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, stream, sc, seg, ev_mid);
-    else if (debug == 2)
-        launch_inflate_members_as<false, true, false>(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, stream, sc, seg, ev_mid);
+// instrument and does so for any non-zero value, and so does the count form, which has no k_lzcopy.
+static void launch_inflate_members(const InflateLaunch &l, DBlock *blk, bool seg, bool count) {
+    if (count && l.debug)
+        launch_inflate_members_as<true, false, true, true>(l, blk, seg);
+    else if (count)
+        launch_inflate_members_as<false, false, false, true>(l, blk, seg);
+    else if (l.debug == 1 || (l.debug && !seg))
+        launch_inflate_members_as<true, false, true, false>(l, blk, seg);
+    else if (l.debug == 2)
+        launch_inflate_members_as<false, true, false, false>(l, blk, seg);
     else
-        launch_inflate_members_as<false, false, false>(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, stream, sc, seg, ev_mid);
+        launch_inflate_members_as<false, false, false, false>(l, blk, seg);
 }
 
-void launch_inflate(uint32_t hdr_len, const uint8_t *d_in, const uint64_t *d_offsets, const uint32_t *d_sizes,
-                    uint32_t nb, void *d_blk, uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap,
-                    uint32_t *d_crc_found, const CrcConsts &cc, int debug, hipEvent_t ev_begin,
-                    hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc, int route, hipEvent_t ev_mid) {
+void launch_inflate(const InflateLaunch &l, uint32_t hdr_len, const uint64_t *d_offsets, const uint32_t *d_sizes) {
     static_assert(sizeof(DBlock) == sizeof(DBlockHost), "the host allocates and reads the records as DBlockHost");
-    DBlock *blk = (DBlock *)d_blk;
-    const bool seg = route != kInflateRouteWave && sc.mlist && sc.tfirst && sc.redo;
-    hipLaunchKernelGGL(k_dinit, dim3((nb + 255) / 256), dim3(256), 0, stream, hdr_len, nb, d_in, d_offsets, d_sizes, blk,
+    const InflateScratch &sc = *l.sc;
+    DBlock *blk = (DBlock *)l.d_blk;
+    const bool seg = l.route != kInflateRouteWave && sc.mlist && sc.tfirst && sc.redo;
+    hipLaunchKernelGGL(k_dinit, dim3((l.nb + 255) / 256), dim3(256), 0, l.stream, hdr_len, l.nb, l.d_in, d_offsets, d_sizes, blk,
                        seg ? sc.redo : (uint32_t *)nullptr);
-    hipLaunchKernelGGL(k_dscan, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, d_out_off);
-    if (ev_begin) (void)hipEventRecord(ev_begin, stream);
-    launch_inflate_members(d_in, nb, blk, d_out_off, d_out, out_cap, d_crc_found, cc, debug, stream, sc, seg, ev_mid);
-    if (ev_end) (void)hipEventRecord(ev_end, stream);
-    hipLaunchKernelGGL(k_dcrc32, dim3(nb), dim3(kCrcThreads), 0, stream, (const uint8_t *)d_out,
-                       (const uint64_t *)d_out_off, (const DBlock *)blk, d_crc_found, cc);
+    hipLaunchKernelGGL(k_dscan, dim3(1), dim3(256), 0, l.stream, l.nb, (const DBlock *)blk, l.d_out_off);
+    if (l.ev_begin) (void)hipEventRecord(l.ev_begin, l.stream);
+    launch_inflate_members(l, blk, seg, false);
+    if (l.ev_end) (void)hipEventRecord(l.ev_end, l.stream);
+    hipLaunchKernelGGL(k_dcrc32, dim3(l.nb), dim3(kCrcThreads), 0, l.stream, (const uint8_t *)l.d_out,
+                       (const uint64_t *)l.d_out_off, (const DBlock *)blk, l.d_check, *l.cc);
     if (sc.summary)
-        hipLaunchKernelGGL(k_dsummary, dim3(1), dim3(256), 0, stream, nb, (const DBlock *)blk, (const uint32_t *)d_crc_found, sc.summary);
+        hipLaunchKernelGGL(k_dsummary, dim3(1), dim3(256), 0, l.stream, l.nb, (const DBlock *)blk, (const uint32_t *)l.d_check,
+                           sc.summary);
 }
 
 // A batch of members in a wrapper (gzpx_wrap.h).  Everything is read from and written to device memory; what the host
 // reads afterwards is k_dresult's record in sc.summary.  `d_slot` is scratch of nb words.
-void launch_inflate_batch(int wrap, int short_ok, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets,
-                          const uint32_t *d_sizes, const uint32_t *d_out_sizes, uint32_t nb, void *d_blk, uint32_t *d_slot,
-                          uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap, uint32_t *d_check, const CrcConsts &cc,
-                          int debug, hipEvent_t ev_begin, hipEvent_t ev_end, hipStream_t stream, const InflateScratch &sc,
-                          int route, uint64_t *d_user_off, void *d_results, hipEvent_t ev_mid, hipEvent_t ev_check) {
-    DBlock *blk = (DBlock *)d_blk;
+void launch_inflate_batch(const InflateLaunch &l, int wrap, int short_ok, uint64_t in_len, const uint64_t *d_offsets,
+                          const uint32_t *d_sizes, const uint32_t *d_out_sizes, uint32_t *d_slot, uint64_t *d_user_off,
+                          void *d_results) {
+    const InflateScratch &sc = *l.sc;
+    DBlock *blk = (DBlock *)l.d_blk;
     // (fewer bytes than the slot are k_inflate's to see: k_inflate_seg hands such a member over anyway)
-    const bool seg = route != kInflateRouteWave && !short_ok && sc.mlist && sc.tfirst && sc.redo;
-    WrapTable t{d_in, in_len, d_offsets, d_sizes, d_out_sizes, (uint32_t)wrap};
-    hipLaunchKernelGGL(k_dinit_wrap, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, t, blk, d_slot,
+    const bool seg = l.route != kInflateRouteWave && !short_ok && sc.mlist && sc.tfirst && sc.redo;
+    WrapTable t{l.d_in, in_len, d_offsets, d_sizes, d_out_sizes, (uint32_t)wrap};
+    hipLaunchKernelGGL(k_dinit_wrap, dim3((l.nb + 255) / 256), dim3(256), 0, l.stream, l.nb, t, blk, d_slot,
                        seg ? sc.redo : (uint32_t *)nullptr);
-    hipLaunchKernelGGL(k_dscan_slots, dim3(1), dim3(256), 0, stream, nb, (const uint32_t *)d_slot, blk, out_cap, d_out_off);
-    if (ev_begin) (void)hipEventRecord(ev_begin, stream);
-    launch_inflate_members(d_in, nb, blk, d_out_off, d_out, out_cap, d_check, cc, debug, stream, sc, seg, ev_mid);
-    if (ev_end) (void)hipEventRecord(ev_end, stream);
+    hipLaunchKernelGGL(k_dscan_slots, dim3(1), dim3(256), 0, l.stream, l.nb, (const uint32_t *)d_slot, blk, l.out_cap,
+                       l.d_out_off);
+    if (l.ev_begin) (void)hipEventRecord(l.ev_begin, l.stream);
+    launch_inflate_members(l, blk, seg, false);
+    if (l.ev_end) (void)hipEventRecord(l.ev_end, l.stream);
     if (wrap == kWrapGzip)
-        hipLaunchKernelGGL(k_dcrc32, dim3(nb), dim3(kCrcThreads), 0, stream, (const uint8_t *)d_out,
-                           (const uint64_t *)d_out_off, (const DBlock *)blk, d_check, cc);
+        hipLaunchKernelGGL(k_dcrc32, dim3(l.nb), dim3(kCrcThreads), 0, l.stream, (const uint8_t *)l.d_out,
+                           (const uint64_t *)l.d_out_off, (const DBlock *)blk, l.d_check, *l.cc);
     else if (wrap == kWrapZlib)
-        hipLaunchKernelGGL(k_dadler32, dim3(nb), dim3(kAdlerThreads), 0, stream, (const uint8_t *)d_out,
-                           (const uint64_t *)d_out_off, (const DBlock *)blk, d_check);
-    if (ev_check) (void)hipEventRecord(ev_check, stream);
-    hipLaunchKernelGGL(k_dresult, dim3(1), dim3(256), 0, stream, nb, (uint32_t)wrap, (uint32_t)(short_ok ? 1 : 0),
-                       (const DBlock *)blk, (const uint32_t *)d_slot, (const uint32_t *)d_check, (const uint64_t *)d_out_off,
+        hipLaunchKernelGGL(k_dadler32, dim3(l.nb), dim3(kAdlerThreads), 0, l.stream, (const uint8_t *)l.d_out,
+                           (const uint64_t *)l.d_out_off, (const DBlock *)blk, l.d_check);
+    if (l.ev_check) (void)hipEventRecord(l.ev_check, l.stream);
+    hipLaunchKernelGGL(k_dresult, dim3(1), dim3(256), 0, l.stream, l.nb, (uint32_t)wrap, (uint32_t)(short_ok ? 1 : 0),
+                       (const DBlock *)blk, (const uint32_t *)d_slot, (const uint32_t *)l.d_check, (const uint64_t *)l.d_out_off,
                        (WrapResult *)d_results, d_user_off, sc.summary);
 }
 
-// The sizes of a batch of members (gzpx_inflate_batch_sizes_device): the count-only forms of the inflate kernels between
-// k_dinit_wrap_sizes and k_dresult_sizes.  Nothing but the compressed bytes is read, and nothing written but the
-// records and the caller's tables: no output, no match list, no tile table (sc.mlist / sc.tfirst are not looked at).
-// The launch forms and their choice are launch_inflate_members_as's.
-template <bool DBG>
-static void launch_inflate_sizes_as(const uint8_t *d_in, uint32_t nb, DBlock *blk, hipStream_t stream, const InflateScratch &sc,
-                                    bool seg, hipEvent_t ev_mid) {
-    if (!seg) {
-        hipLaunchKernelGGL((k_inflate<DBG, true>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)nullptr,
-                           (uint8_t *)nullptr, 0ull, (const uint32_t *)nullptr);
-        return;
-    }
-    const SegLaunch sl = seg_launch_of(sc, nb);
-    if (sl.big)
-        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegBigW, true>), dim3(sl.grid), dim3(64 * kSegBigW), 0, stream, d_in, blk,
-                           (const uint64_t *)nullptr, (uint8_t *)nullptr, 0ull, (LzMatch *)nullptr, (uint32_t *)nullptr, sc.redo,
-                           nb, sl.hint);
-    else
-        hipLaunchKernelGGL((k_inflate_seg<DBG, kSegSmallW, true>), dim3(sl.grid), dim3(64 * kSegSmallW), 0, stream, d_in, blk,
-                           (const uint64_t *)nullptr, (uint8_t *)nullptr, 0ull, (LzMatch *)nullptr, (uint32_t *)nullptr, sc.redo,
-                           nb, sl.hint);
-    if (ev_mid) (void)hipEventRecord(ev_mid, stream);
-    if (DBG) hipLaunchKernelGGL(k_seg_reasons, dim3((nb + 255) / 256), dim3(256), 0, stream, (const DBlock *)blk, sc.redo, nb, 1u);
-    hipLaunchKernelGGL((k_inflate<DBG, true>), dim3(nb), dim3(64), 0, stream, d_in, blk, (const uint64_t *)nullptr,
-                       (uint8_t *)nullptr, 0ull, (const uint32_t *)sc.redo);
-}
-
-void launch_inflate_sizes(int wrap, const uint8_t *d_in, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
-                          uint32_t max_out, uint32_t nb, void *d_blk, int debug, hipEvent_t ev_begin, hipEvent_t ev_end,
-                          hipStream_t stream, const InflateScratch &sc, int route, uint32_t *d_out_sizes, uint32_t *d_in_used,
-                          void *d_results, hipEvent_t ev_mid) {
-    DBlock *blk = (DBlock *)d_blk;
-    const bool seg = route != kInflateRouteWave && sc.redo;
-    WrapTable t{d_in, in_len, d_offsets, d_sizes, nullptr, (uint32_t)wrap};
-    hipLaunchKernelGGL(k_dinit_wrap_sizes, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, t, max_out ? max_out : 0xFFFFFFFFu,
-                       blk, seg ? sc.redo : (uint32_t *)nullptr);
-    if (ev_begin) (void)hipEventRecord(ev_begin, stream);
-    if (debug)
-        launch_inflate_sizes_as<true>(d_in, nb, blk, stream, sc, seg, ev_mid);
-    else
-        launch_inflate_sizes_as<false>(d_in, nb, blk, stream, sc, seg, ev_mid);
-    if (ev_end) (void)hipEventRecord(ev_end, stream);
-    hipLaunchKernelGGL(k_dresult_sizes, dim3(1), dim3(256), 0, stream, nb, (uint32_t)wrap, (const DBlock *)blk, d_out_sizes,
+// The sizes of a batch of members (gzpx_inflate_batch_sizes_device): the count form of launch_inflate_members between
+// k_dinit_wrap_sizes and k_dresult_sizes; the caller's tables are all that is written.
+void launch_inflate_sizes(const InflateLaunch &l, int wrap, uint64_t in_len, const uint64_t *d_offsets, const uint32_t *d_sizes,
+                          uint32_t max_out, uint32_t *d_out_sizes, uint32_t *d_in_used, void *d_results) {
+    const InflateScratch &sc = *l.sc;
+    DBlock *blk = (DBlock *)l.d_blk;
+    const bool seg = l.route != kInflateRouteWave && sc.redo;
+    WrapTable t{l.d_in, in_len, d_offsets, d_sizes, nullptr, (uint32_t)wrap};
+    hipLaunchKernelGGL(k_dinit_wrap_sizes, dim3((l.nb + 255) / 256), dim3(256), 0, l.stream, l.nb, t,
+                       max_out ? max_out : 0xFFFFFFFFu, blk, seg ? sc.redo : (uint32_t *)nullptr);
+    if (l.ev_begin) (void)hipEventRecord(l.ev_begin, l.stream);
+    launch_inflate_members(l, blk, seg, true);
+    if (l.ev_end) (void)hipEventRecord(l.ev_end, l.stream);
+    hipLaunchKernelGGL(k_dresult_sizes, dim3(1), dim3(256), 0, l.stream, l.nb, (uint32_t)wrap, (const DBlock *)blk, d_out_sizes,
                        d_in_used, (WrapResult *)d_results, sc.summary);
 }
 

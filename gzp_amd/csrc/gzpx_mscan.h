@@ -1,6 +1,6 @@
 // gzpx_mscan.h -- member discovery on the device: the table gzpx_scan_blocks (the reader thread's header walk,
 // src/par/decompress.rs:132-160) would produce for a BGZF / Mgzip stream that lies in device memory.  Included from
-// gzpx_kernels.hip.
+// gzpx_kernels.hip behind gzpx_wave.h (block_exclusive_scan256, load_le32_global).
 //
 // The walk is a chain of dependent loads (a member's size says where the next header is), so nothing here follows it.
 //   1. candidates   k_mscan_cand<false> / k_mscan_offsets / k_mscan_cand<true>: every position whose header passes the walk's

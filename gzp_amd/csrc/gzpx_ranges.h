@@ -1,6 +1,6 @@
 // gzpx_ranges.h -- random access by range: a batch of byte ranges of the inflated stream, read from a BGZF / Mgzip
 // stream in device memory through an index that lies there too (RrIndex: member offsets, member sizes, exclusive
-// prefix sum of ISIZE).  Included from gzpx_kernels.hip.
+// prefix sum of ISIZE).  Included from gzpx_kernels.hip behind gzpx_wave.h (block_exclusive_scan256).
 //
 //   1. locate   k_rr_locate: one lane per range.  Virtual offsets are resolved to uncompressed ones (exact-match
 //               binary search on the member offsets), then `first` = the last member whose uncompressed start is

@@ -1,5 +1,6 @@
 // gzpx_snap.h -- gzp's Snap format (src/snap.rs:38-83: snap::read::FrameEncoder over every buffer_size piece of the
-// stream).  Included by gzpx_kernels.hip inside namespace gzpx.
+// stream).  Included by gzpx_kernels.hip inside namespace gzpx, behind
+// gzpx_wave.h (wave_sync, the scans, gzpx_crc.h).
 //
 // A buffer is cut into chunks of 65,536 bytes; every chunk is framed as a 4-byte header (type, 24-bit length), the
 // masked CRC-32C of the uncompressed chunk and a body: the raw Snappy encoding of the chunk (type 0x00), or the chunk

@@ -355,6 +355,29 @@ def max_out_size(lib, count_steps=False):
             assert 0 < capped[4] < whole[4] and capped[5] < whole[5], (capped, whole)
 
 
+# ------------------------------------------------------------------------------------------------ 7b. debug 2
+def debug_two_counts_alike(lib):
+    """debug_inflate(2) asks for k_lzcopy's clocks, and a sizes call launches no k_lzcopy: on both routes it answers what
+    it answers under debug_inflate(0) -- sizes, in_used, verdicts and the call's own out-values, with and without a cap
+    that one member exceeds."""
+    plains = [synth.make("text", 999, 2).tobytes(), bytes(1000), synth.make("dna", 400, 3).tobytes(), b""]
+    for w, wrap in sorted(WRAPS.items()):
+        members = [deflate(p, wrap) for p in plains]
+        blob, offs = layout(members)
+        sizes = [len(m) for m in members]
+        for route, d in contexts(lib):
+            got = {}
+            for debug in (0, 2):
+                d.debug_inflate(debug)
+                got[debug] = [call(lib, d, wrap, blob, offs, sizes, max_out=cap) for cap in (0, 999)]
+            d.debug_inflate(0)
+            check_all_good(got[0][0], plains, members, (w, route, "debug 0"))
+            assert got[0][1].status == [OK, E_SPACE, OK, OK] and got[0][1].out_sizes == [999, 0, 400, 0], (w, route)
+            for a, b in zip(got[0], got[2]):
+                assert (b.out_sizes, b.in_used, b.rows) == (a.out_sizes, a.in_used, a.rows), (w, route, b.rows, a.rows)
+                assert (b.rc, b.n_failed, b.block, b.total) == (a.rc, a.n_failed, a.block, a.total) and b.guard_ok, (w, route)
+
+
 # ------------------------------------------------------------------------------------------------ 8. arguments
 def arguments(lib):
     data = synth.make("text", 2500, 9).tobytes()

@@ -39,6 +39,10 @@ def test_max_out_size(emu_lib):
     size_cases.max_out_size(emu_lib, count_steps=True)
 
 
+def test_debug_two_counts_alike(emu_lib):
+    size_cases.debug_two_counts_alike(emu_lib)
+
+
 def test_arguments(emu_lib):
     size_cases.arguments(emu_lib)
 

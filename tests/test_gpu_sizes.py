@@ -41,5 +41,9 @@ def test_max_out_size(hip_lib):
     size_cases.max_out_size(hip_lib, count_steps=True)
 
 
+def test_debug_two_counts_alike(hip_lib):
+    size_cases.debug_two_counts_alike(hip_lib)
+
+
 def test_arguments(hip_lib):
     size_cases.arguments(hip_lib)

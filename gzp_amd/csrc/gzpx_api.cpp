@@ -41,6 +41,8 @@ uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
     return crc_mulmod<kCrcPoly32>(crc_xpow8<kCrcPoly32>(kCrc32Pow.sq, len2), crc1) ^ crc2;
 }
 
+#include "gzpx_policy.h"  // kMinBlockLen, kFastSeqStoreLen, level_params
+
 constexpr size_t kTrailerBytes = 8;  // CRC-32 + ISIZE behind a member's payload
 // BGZF's end-of-file marker, an empty member: header + the two bytes of an empty static block + trailer
 constexpr size_t kEofMarkerBytes = header_bytes(GZPX_FORMAT_BGZF) + 2 + kTrailerBytes;
@@ -939,22 +941,17 @@ int gzpx_ctx_create(const gzpx_config *cfg, gzpx_ctx **out) {
     ctx->dcfg.debug = 0;
     // per-block strides: padding for k_candidates' last iteration / dword-wide tile loads
     ctx->dcfg.stride = (uint32_t)((cfg->buffer_size + 2047) / 2048 * 2048 + 2048);
-    // level 1 sub-blocks hold 8192 matches (>= 32768 bytes); the block splitter of levels 2-4 may
-    // cut every MIN_BLOCK_LENGTH = 5000 bytes
-    ctx->dcfg.max_sub = (uint32_t)(cfg->buffer_size / (lvl == 1 ? 32768 : 5000) + 2);
+    // level 1 sub-blocks hold FAST_SEQ_STORE_LENGTH matches of at least four bytes; the block splitter of levels
+    // 2-12 may cut every MIN_BLOCK_LENGTH bytes
+    ctx->dcfg.max_sub = (uint32_t)(cfg->buffer_size / (lvl == 1 ? 4 * kFastSeqStoreLen : kMinBlockLen) + 2);
     // deflate_compress: inputs up to 55 - 4*level bytes -- and everything at level 0 -- take
     // deflate_compress_none
     ctx->dcfg.passthrough = lvl == 0 ? 0xFFFFFFFFu : (uint32_t)(55 - 4 * lvl);
-    {
-        // libdeflate_alloc_compressor: max_search_depth / nice_match_length of levels 2-9
-        // (levels 10-12, deflate_compress_near_optimal: + num_optim_passes 2 / 3 / 4)
-        static const uint32_t depth[13] = {0, 0, 6, 12, 16, 16, 35, 100, 300, 600, 35, 70, 150};
-        static const uint32_t nice[13] = {0, 0, 10, 14, 30, 30, 65, 130, 258, 258, 75, 150, 258};
-        ctx->dcfg.hc_depth = depth[lvl];
-        ctx->dcfg.hc_nice = nice[lvl];
-        ctx->dcfg.lazy = lvl >= 10 ? 0u : lvl >= 8 ? 2u : lvl >= 5 ? 1u : 0u;
-        ctx->dcfg.no_passes = lvl >= 10 ? (uint32_t)lvl - 8u : 0u;
-    }
+    const LevelParams lp = level_params((uint32_t)lvl);  // libdeflate_alloc_compressor
+    ctx->dcfg.hc_depth = lp.depth;
+    ctx->dcfg.hc_nice = lp.nice;
+    ctx->dcfg.lazy = lp.lazy;
+    ctx->dcfg.no_passes = lp.passes;
     ctx->crc_consts = crc_consts();
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) {
@@ -1215,10 +1212,10 @@ size_t gzpx_deflate_compress(gzpx_compressor *c, const void *in, size_t n, void 
 }
 
 size_t gzpx_deflate_compress_bound(gzpx_compressor *c, size_t n) {
-    // libdeflate_deflate_compress_bound: worst case = stored blocks of MIN_BLOCK_LENGTH (5000)
+    // libdeflate_deflate_compress_bound: worst case = stored blocks of MIN_BLOCK_LENGTH
     // bytes, 5 bytes of header each.  v1.10 (probed on the image's binary) adds 1 + 8 bytes of
     // slack (OUTPUT_END_PADDING); the pinned v1.24 does not.
-    size_t max_blocks = (n + 4999) / 5000;
+    size_t max_blocks = (n + kMinBlockLen - 1) / kMinBlockLen;
     if (max_blocks < 1) max_blocks = 1;
     const size_t slack = (c && c->compat == GZPX_COMPAT_LIBDEFLATE_1_10) ? 9 : 0;
     return 5 * max_blocks + n + slack;

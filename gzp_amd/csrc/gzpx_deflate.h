@@ -1,6 +1,7 @@
 // gzpx_deflate.h -- RFC 1951's alphabets and code tables, once.  Included inside namespace gzpx by gzpx_wave.h
 // (with GZPX_DEFLATE_WAVE defined, behind wave_sync) and by gzpx_nearopt.hip (the arithmetic alone);
-// gzpx_kernels.hip and gzpx_inflate_seg.h see it through gzpx_wave.h.
+// gzpx_kernels.hip and gzpx_inflate_seg.h see it through gzpx_wave.h.  What libdeflate's compressor decides beyond the
+// RFC -- where a block ends, which matches count -- is in gzpx_policy.h, included the same way.
 //
 //   arithmetic (constexpr, host and device)
 //     length_sym / offset_sym       a symbol's (base, extra bits): seg_entry (k_inflate_seg), k_huffman's bit costs,

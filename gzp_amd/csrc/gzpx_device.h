@@ -13,9 +13,6 @@ namespace gzpx {
 
 constexpr unsigned kTile = 65536;         // positions handled per LDS tile (k_parse) / stage window
 constexpr unsigned kMaxBlockSize = 1u << 26;  // largest buffer_size the kernels accept (64 MiB; round 6: tested at 32 MiB)
-constexpr unsigned kSeqPerSub = 8192;      // FAST_SEQ_STORE_LENGTH
-constexpr unsigned kSoftMaxSub = 65535;    // FAST_SOFT_MAX_BLOCK_LENGTH
-constexpr unsigned kMinBlockLen = 5000;    // MIN_BLOCK_LENGTH
 constexpr unsigned kNumLitlen = 288;
 constexpr unsigned kNumOffset = 32;
 constexpr unsigned kHistStride = kNumLitlen + kNumOffset;  // 320 u32 per sub-block

@@ -42,7 +42,8 @@
 // Integer/byte work only: no MFMA; the path is bound by instruction issue, then LDS.
 //
 // What more than one stage or more than one of the headers included below uses -- wave_sync, the scans, dword4, the
-// experiment counters, and through it gzpx_deflate.h and gzpx_crc.h -- is in gzpx_wave.h, in front of them all.
+// experiment counters, and through it gzpx_policy.h (libdeflate's parsing rules: lz_hash, where a sub-block ends, the
+// minimum match length), gzpx_deflate.h and gzpx_crc.h -- is in gzpx_wave.h, in front of them all.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <cstring>
@@ -159,13 +160,13 @@ constexpr uint32_t kCandWaves = GZPX_CAND_WAVES;  // sixteen: four per SIMD; the
 template <int MODE>
 __device__ __forceinline__ bool cand_bucket(uint32_t v, uint32_t p, uint32_t &h) {
     if (MODE == 0) {
-        h = p != 0 ? lz_hash15(v) : 0;
+        h = p != 0 ? lz_hash(v, 15) : 0;
         return true;
     } else if (MODE == 1) {
-        h = p != 0 ? lz_hash15(v & 0xFFFFFFu) : 0;
+        h = p != 0 ? lz_hash(v & 0xFFFFFFu, 15) : 0;
         return true;
     } else {
-        const uint32_t h16 = p != 0 ? (v * 0x1E35A7BDu) >> 16 : 0;
+        const uint32_t h16 = p != 0 ? lz_hash(v, 16) : 0;
         h = h16 & 32767u;
         return MODE == 2 ? h16 < 32768u : h16 >= 32768u;
     }
@@ -356,10 +357,10 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_candidates(Config cfg,
                 const uint32_t v = __builtin_amdgcn_alignbyte(ring[k].y, ring[k].x, sh);
                 if (MODE <= 1) {  // p != 0, p + 5 <= n: every position has its bucket
                     mine[k] = true;
-                    addr[k] = 4u * lz_hash15(MODE == 0 ? v : v & 0xFFFFFFu);
+                    addr[k] = 4u * lz_hash(MODE == 0 ? v : v & 0xFFFFFFu, 15);
                     val[k] = v0 + 64 * k;
                 } else {
-                    const uint32_t h16 = (v * 0x1E35A7BDu) >> 16;
+                    const uint32_t h16 = lz_hash(v, 16);
                     mine[k] = MODE == 2 ? h16 < 32768u : h16 >= 32768u;
                     addr[k] = 4u * (mine[k] ? h16 & 32767u : kBuckets + lane);
                     val[k] = mine[k] ? v0 + 64 * k : 0u;
@@ -755,14 +756,6 @@ __device__ __forceinline__ void clear_marks(uint32_t seg_begin, uint32_t seg_end
     }
 }
 
-// choose_max_block_end (FAST_SOFT_MAX_BLOCK_LENGTH, MIN_BLOCK_LENGTH): where a sub-block that
-// starts at `start` must end at the latest.  SOFT_MAX: FAST_SOFT_MAX_BLOCK_LENGTH at level 1, SOFT_MAX_BLOCK_LENGTH
-// (kHcSoftMaxSub) at levels 2-9.
-template <uint32_t SOFT_MAX = kSoftMaxSub>
-__device__ __forceinline__ uint32_t sub_limit_of(uint32_t start, uint32_t n) {
-    return (n - start < SOFT_MAX + kMinBlockLen) ? n : start + SOFT_MAX;
-}
-
 constexpr uint32_t kPSeg = 64;  // positions per walk segment = one 64-bit word of the token bitmap
 constexpr uint32_t kRescueTokens = 512;
 
@@ -796,7 +789,7 @@ __device__ __forceinline__ void parse_block(
     uint32_t entry_carry = 0;            // where the parse enters the next tile
     uint32_t tok_carry = 0, mat_carry = 0;
     uint32_t cur_sub = 0, sub_start = 0, sub_start_tok = 0, sub_start_mat = 0;
-    uint32_t sub_limit = sub_limit_of(0, n);
+    uint32_t sub_limit = max_block_end(0, n, kFastSoftMaxBlockLen);
 
     for (uint32_t tile_begin = 0; tile_begin < n; tile_begin += kTile) {
         const uint32_t tile_len = n - tile_begin < kTile ? n - tile_begin : kTile;
@@ -965,7 +958,7 @@ __device__ __forceinline__ void parse_block(
                     const unsigned long long mt = tok_bits[g];
                     const uint32_t pre = rank_pre[g];
                     const uint32_t mat_after = mat_carry + (g + 1 < ngroups ? rank_pre[g + 1] >> 17 : tile_mat);
-                    const bool count_rule = mat_after - sub_start_mat >= kSeqPerSub;  // wave-uniform, rare
+                    const bool count_rule = mat_after - sub_start_mat >= kFastSeqStoreLen;  // wave-uniform, rare
                     const uint32_t r = g * 64 + lane, p = tile_begin + r;
                     if (!((mt >> lane) & 1ull)) continue;
                     const uint32_t ti = tok_carry + (pre & 0x1FFFFu) + (uint32_t)__popcll(mt & lane_below);
@@ -975,7 +968,7 @@ __device__ __forceinline__ void parse_block(
                     if (count_rule) {
                         const unsigned long long mm = mt & nz[(tile_begin >> 6) + g];
                         const uint32_t mi = mat_carry + (pre >> 17) + (uint32_t)__popcll(mm & lane_below);
-                        boundary = boundary || mi - sub_start_mat >= kSeqPerSub;
+                        boundary = boundary || mi - sub_start_mat >= kFastSeqStoreLen;
                     }
                     if (p > sub_start && boundary) atomicMin(&bnd, ((unsigned long long)p << 32) | ti);
                     const uint32_t l = len8[r];
@@ -1012,11 +1005,11 @@ __device__ __forceinline__ void parse_block(
             sub_start = bp;
             sub_start_tok = bti;
             sub_start_mat = bm;
-            sub_limit = sub_limit_of(bp, n);
+            sub_limit = max_block_end(bp, n, kFastSoftMaxBlockLen);
             __syncthreads();
             // another boundary in this tile needs 8192 more matches, or -- when this boundary sits
             // on the tile's first positions -- the 65535-byte soft limit falling on its last ones
-            if (mat_carry + tile_mat - bm < kSeqPerSub && sub_limit >= tile_begin + tile_len) break;
+            if (mat_carry + tile_mat - bm < kFastSeqStoreLen && sub_limit >= tile_begin + tile_len) break;
             build = false;
         }
         tok_carry += tile_tok;
@@ -1428,13 +1421,13 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
         }
 
         // ---- phase 3a: sub-block boundaries.  A new DEFLATE sub-block starts at the first token that
-        // has kSeqPerSub matches of the current one before it (deflate_compress_fastest; the byte
+        // has kFastSeqStoreLen matches of the current one before it (deflate_compress_fastest; the byte
         // limit of choose_max_block_end cannot fire in a block of at most one tile).  Match ranks are
         // known from the scan, so every lane names its own first such token and the smallest wins.
         const uint32_t my_mat0 = mat_carry + (my_pre >> 17);   // matches before my first token
         const uint32_t my_tok0 = tok_carry + (my_pre & 0x1FFFFu);  // tokens before it
         for (;;) {
-            const uint32_t target = sub_start_mat + kSeqPerSub;
+            const uint32_t target = sub_start_mat + kFastSeqStoreLen;
             if (mat_carry + tile_mat < target) break;  // (uniform) the sub-block outlasts this pass
             if (marks) {
                 uint32_t k = 32;  // bit of my first token with >= target matches before it
@@ -1552,25 +1545,14 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kHcTile = 16384;
 constexpr uint32_t kHcInWords = (32768 + kHcTile + 264) / 4 + 8;
-constexpr uint32_t kHcSoftMaxSub = 300000;  // SOFT_MAX_BLOCK_LENGTH
-constexpr uint32_t kHcSeqPerSub = 50000;    // SEQ_STORE_LENGTH
-
-// choose_min_match_len
-__device__ __forceinline__ uint32_t hc_choose_min_len(uint32_t num_used, uint32_t depth) {
-    uint32_t m = num_used < 6 ? 9 : num_used < 8 ? 8 : num_used < 10 ? 7 : num_used < 16 ? 6
-               : num_used < 45 ? 5 : num_used < 80 ? 4 : 3;
-    if (depth < 16) {
-        const uint32_t cap = depth < 5 ? 4 : depth < 10 ? 5 : 7;
-        if (m > cap) m = cap;
-    }
-    return m;
-}
 
 // calculate_min_match_len for the sub-block that starts at `start`; all threads of the workgroup
 // call it (two barriers), `used` is 8 words of LDS.
 __device__ uint32_t hc_calc_min_len(const Config &cfg, const uint8_t *in, uint32_t start, uint32_t n,
                                     uint32_t *used, uint32_t tid, uint32_t nthreads) {
-    uint32_t data_len = sub_limit_of<kHcSoftMaxSub>(start, n) - start;
+    // (min_len_scan_len and min_len_of_census in this kernel's own text -- a short block is scanned and its census dropped:
+    // with the two calls k_parse_hc<true> spills 53 VGPRs, not 43, and levels 3 and 4 lose 0.3 to 0.8 %, gzpx_policy.h)
+    uint32_t data_len = max_block_end(start, n, kSoftMaxBlockLen) - start;
     __syncthreads();
     if (tid < 8) used[tid] = 0;
     __syncthreads();
@@ -1585,7 +1567,7 @@ __device__ uint32_t hc_calc_min_len(const Config &cfg, const uint8_t *in, uint32
     __syncthreads();
     uint32_t num_used = 0;
     for (uint32_t k = 0; k < 8; k++) num_used += (uint32_t)__popc(used[k]);
-    return short_scan ? 3u : hc_choose_min_len(num_used, cfg.hc_depth);
+    return short_scan ? kMinMatchLen : choose_min_match_len(num_used, cfg.hc_depth);
 }
 
 // lz_extend for the chain walk: bytes [0, start) of the two strings at LDS byte addresses a / c are known
@@ -1910,8 +1892,7 @@ __device__ __forceinline__ void hc_dense_block(uint32_t *hc_lds, const Config &c
             uint32_t ln[1], ds[1];
             hc_search<1>(in_w, link, a, li, d3v, max_len, nice_len, depth, ln, ds, cfg.debug);
             const uint32_t len = ln[0], dst = ds[0];
-            // deflate_compress_greedy: a length-3 match is only worth it at a short distance
-            const bool take = len >= min_len && (len > 3 || dst <= 4096u);
+            const bool take = greedy_takes(len, dst, min_len);
             len8[p] = (uint8_t)(take ? len - 3 : 0);
             // val: the match distance, or the literal byte (what k_parse_hc's token needs either way)
             dist[p] = (uint16_t)(take ? dst : lds_le32(in_w, a) & 0xFFu);
@@ -2058,7 +2039,7 @@ __global__ __launch_bounds__(1024) void k_match_hc_sparse(Config cfg, const uint
     const bool depth_is_deep = cfg.hc_depth > 1u;
     {   // a block that may hold an orphan match (k_hc_orphan) is not compacted
         const uint32_t first4 = n >= 9u ? (uint32_t)in[0] | (uint32_t)in[1] << 8 | (uint32_t)in[2] << 16 | (uint32_t)in[3] << 24 : 1u;
-        if (n >= 9u && ((first4 * 0x1E35A7BDu) >> 16) == 0) go_dense = dense_whole = true;  // uniform
+        if (n >= 9u && lz_hash(first4, 16) == 0) go_dense = dense_whole = true;  // uniform
     }
     const uint16_t *d3 = d3_all + (uint64_t)b * cfg.stride;
     const uint16_t *d4 = d4_all + (uint64_t)b * cfg.stride;
@@ -2207,8 +2188,7 @@ __global__ __launch_bounds__(1024) void k_match_hc_sparse(Config cfg, const uint
             bool over = true;
             if (have) search(p, d3v, 1u, len, dst, over);
             if (depth <= 1u) over = true;
-            // deflate_compress_greedy: a length-3 match is only worth it at a short distance
-            const bool take = have && len >= 3u && (len > 3u || dst <= 4096u);
+            const bool take = have && greedy_takes(len, dst, kMinMatchLen);
             const unsigned long long bt = __ballot(take), bf = __ballot(take && len >= min_len), bo = __ballot(over || !have);
             if (have) {
                 len_l[r] = (uint8_t)(take ? len - 3u : 0u);
@@ -2334,7 +2314,7 @@ __global__ __launch_bounds__(1024) void k_match_hc_sparse(Config cfg, const uint
                     uint32_t len, dst;
                     bool over;
                     search(p, p + 5 <= n ? (uint32_t)d3[p] : 0u, depth, len, dst, over);
-                    const bool take = len >= 3u && (len > 3u || dst <= 4096u);
+                    const bool take = greedy_takes(len, dst, kMinMatchLen);
                     const bool had = (mbf[r >> 5] & bit) != 0;
                     const uint32_t old_step = had ? (uint32_t)len_l[r] + 3u : 1u;  // what the walk took here so far
                     uint32_t step = old_step;
@@ -2439,7 +2419,7 @@ __global__ __launch_bounds__(64) void k_hc_orphan(Config cfg, const uint8_t *__r
         return (uint32_t)in[p] | (uint32_t)in[p + 1] << 8 | (uint32_t)in[p + 2] << 16 | (uint32_t)in[p + 3] << 24;
     };
     const uint32_t first4 = le32(0);
-    if (((first4 * 0x1E35A7BDu) >> 16) != 0) return;  // position 0 sits in hash4 bucket 0 and in no other chain
+    if (lz_hash(first4, 16) != 0) return;  // position 0 sits in hash4 bucket 0 and in no other chain
     const uint16_t *d3 = d3_all + (uint64_t)b * cfg.stride;
     const uint16_t *d4 = d4_all + (uint64_t)b * cfg.stride;
     // the orphan: four bytes like the buffer's first, an empty hash3 bucket (at most one position: the next one with
@@ -2595,7 +2575,7 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
     uint32_t cur_sub = ld(&st->cur_sub);
     const uint32_t orphan_at = ld(&st->pad);  // position + 1 of the block's orphan match (k_match_hc), 0 = none
     uint32_t sub_start = entry_carry, sub_start_tok = tok_carry, sub_start_mat = mat_carry;
-    uint32_t sub_limit = sub_limit_of<kHcSoftMaxSub>(sub_start, n);
+    uint32_t sub_limit = max_block_end(sub_start, n, kSoftMaxBlockLen);
     uint32_t min_len = ld(&st->min_len);
     if (LOOP) __syncthreads();  // the previous round is done with the LDS state
     if (min_len == 0) {  // first round: the sub-block that starts the block (calculate_min_match_len)
@@ -2780,7 +2760,7 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
                 unsigned long long cand = 0;
                 const uint32_t lo = sub_limit > sub_start + 1 ? sub_limit : sub_start + 1;
                 if (gb + 64 > lo) cand = lo > gb ? my_tok & (~0ull << (lo - gb)) : my_tok;
-                const uint32_t T = sub_start_mat + kHcSeqPerSub;
+                const uint32_t T = sub_start_mat + kSeqStoreLen;
                 if (pm >= T) {
                     if (gb > sub_start) cand |= my_tok;
                     else if (gb + 63 > sub_start) cand |= my_tok & (~0ull << (sub_start + 1 - gb));
@@ -2793,7 +2773,7 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
                     atomicMin(&bnd, ((unsigned long long)(gb + bit) << 32) | ti);
                 }
                 if (s_next_check == kNoCheckYet) {
-                    const uint32_t A0 = sub_start_tok + 511u, B0 = sub_start + kMinBlockLen;
+                    const uint32_t A0 = sub_start_tok + kObsPerCheck - 1u, B0 = sub_start + kMinBlockLen;  // (split_due, taken apart)
                     const uint32_t cnt = (uint32_t)__popcll(my_tok);
                     if (pt + cnt > A0 && gb + 64 + 258 > B0) {
                         unsigned long long ca = my_tok;
@@ -2859,7 +2839,7 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
                     vals[k] = is_match ? (kTokMatch | ((v & 0x7FFFu) << 9) | len) : v;  // (without k_match_hc's orphan mark)
                     tis[k] = ti;
                     if (ti < stat_from || ti >= lim_tok || GZPX_EXP(cfg, 14)) continue;
-                    const uint32_t cls = is_match ? 8u + (len >= 9u ? 1u : 0u) : (((v >> 5) & 6u) | (v & 1u));
+                    const uint32_t cls = is_match ? obs_match(len) : obs_literal(v);
                     uint32_t bin = 0;
                     if (nc < kNoMoreChecks && ti > nc) bin = 1u + (ti - nc - 1u) / 512u;
                     // (one count per class, bin and wave from ten ballots instead of an LDS atomic per token
@@ -2911,15 +2891,8 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
                 const uint32_t blen = e - sub_start;
                 bool evt = n - e < kMinBlockLen;  // in_end - in_next < MIN_BLOCK_LENGTH: never again
                 if (!evt && num_obs > 0) {
-                    for (int c = 0; c < 10; c++) {
-                        const uint32_t expected = obs[c] * num_new, actual = nw[c] * num_obs;
-                        total_delta += actual > expected ? actual - expected : expected - actual;
-                    }
-                    const uint32_t num_items = num_obs + num_new;
-                    uint32_t cutoff = num_new * 200u / 512u * num_obs;
-                    if (blen < 10000u && num_items < 8192u)
-                        cutoff += (uint32_t)((unsigned long long)cutoff * (8192u - num_items) / 8192u);
-                    evt = total_delta + (blen / 4096u) * num_obs >= cutoff;
+                    for (int c = 0; c < 10; c++) total_delta += split_delta(obs[c], nw[c], num_obs, num_new);
+                    evt = split_verdict(total_delta, num_obs, num_new, blen);
                 }
                 if (evt) atomicMin(&first_evt, k);
             }
@@ -2979,7 +2952,7 @@ __global__ __launch_bounds__(kMpThreads, GZPX_PHC_WAVES) void k_parse_hc(
             sub_start = bp;
             sub_start_tok = bti;
             sub_start_mat = bm;
-            sub_limit = sub_limit_of<kHcSoftMaxSub>(bp, n);
+            sub_limit = max_block_end(bp, n, kSoftMaxBlockLen);
             stat_from = bti;
             const uint32_t new_min_len = hc_calc_min_len(cfg, in, bp, n, used, tid, kMpThreads);
             __syncthreads();
@@ -3148,9 +3121,10 @@ __global__ __launch_bounds__(64) void k_parse_lazy(Config cfg, const uint8_t *__
 #endif
     for (;;) {                            // DEFLATE sub-blocks
         const uint32_t sub_start = pos, sub_start_tok = ti;
-        const uint32_t max_block_end = sub_limit_of<kHcSoftMaxSub>(sub_start, n);
+        const uint32_t block_end = max_block_end(sub_start, n, kSoftMaxBlockLen);
         uint32_t min_len = hc_calc_min_len(cfg, in, sub_start, n, L.used, lane, 64);
-        uint32_t next_recalc = sub_start + (n - sub_start < 10000u ? n - sub_start : 10000u);
+        // (split_due and the two recalculation points below in this kernel's own text: gzpx_policy.h says why)
+        uint32_t next_recalc = sub_start + (n - sub_start < kFirstRecalc ? n - sub_start : kFirstRecalc);
         uint32_t nseq = 0, num_new = 0, num_obs = 0;
         __syncthreads();
         for (uint32_t i = lane; i < 256; i += 64) L.freq[i] = 0;
@@ -3263,8 +3237,8 @@ __global__ __launch_bounds__(64) void k_parse_lazy(Config cfg, const uint8_t *__
             const uint64_t mm = __ballot(in_r && mlen != 0);
             const uint32_t mb = (uint32_t)__popcll(mm & lane_below);
             // ---- the first reached decision in front of which something is due
-            const bool due = in_r && (p >= max_block_end || nseq + mb >= kHcSeqPerSub ||
-                                      (num_new + tb >= 512u && p - sub_start >= kMinBlockLen && n - p >= kMinBlockLen) ||
+            const bool due = in_r && (p >= block_end || nseq + mb >= kSeqStoreLen ||
+                                      (num_new + tb >= kObsPerCheck && p - sub_start >= kMinBlockLen && n - p >= kMinBlockLen) ||
                                       p >= next_recalc);
             const uint64_t dm_real = __ballot(due);
             const uint64_t dm = dm_real | (__ballot(off_tile) & reach);
@@ -3277,11 +3251,11 @@ __global__ __launch_bounds__(64) void k_parse_lazy(Config cfg, const uint8_t *__
                     const uint32_t c = t_in[r + j];
                     tok[o + j] = c;
                     atomicAdd(&L.freq[c], 1u);
-                    atomicAdd(&L.nw[((c >> 5) & 6u) | (c & 1u)], 1u);
+                    atomicAdd(&L.nw[obs_literal(c)], 1u);
                 }
                 if (mlen) {
                     tok[o + nlit] = kTokMatch | (moff << 9) | mlen;
-                    atomicAdd(&L.nw[8u + (mlen >= 9u ? 1u : 0u)], 1u);
+                    atomicAdd(&L.nw[obs_match(mlen)], 1u);
                 }
             }
             const uint32_t done_tok = e < 64u ? (uint32_t)__builtin_amdgcn_readlane((int)tb, (int)e)
@@ -3298,21 +3272,12 @@ __global__ __launch_bounds__(64) void k_parse_lazy(Config cfg, const uint8_t *__
                 continue;
             }
             // ---- what is due at pos, in deflate_compress_lazy_generic's order
-            if (pos >= max_block_end || nseq >= kHcSeqPerSub) break;
-            if (num_new >= 512u && pos - sub_start >= kMinBlockLen && n - pos >= kMinBlockLen) {  // do_end_block_check
+            if (pos >= block_end || nseq >= kSeqStoreLen) break;
+            if (num_new >= kObsPerCheck && pos - sub_start >= kMinBlockLen && n - pos >= kMinBlockLen) {  // do_end_block_check
                 __syncthreads();
                 const uint32_t o = lane < 10 ? L.obs[lane] : 0u, w = lane < 10 ? L.nw[lane] : 0u;
-                const uint32_t expected = o * num_new, actual = w * num_obs;
-                const uint32_t total_delta = wave_reduce_add(actual > expected ? actual - expected : expected - actual);
-                bool end = false;
-                if (num_obs > 0) {
-                    const uint32_t blen = pos - sub_start, num_items = num_obs + num_new;
-                    uint32_t cutoff = num_new * 200u / 512u * num_obs;
-                    if (blen < 10000u && num_items < 8192u)
-                        cutoff += (uint32_t)((unsigned long long)cutoff * (8192u - num_items) / 8192u);
-                    end = total_delta + (blen / 4096u) * num_obs >= cutoff;
-                }
-                if (end) break;
+                const uint32_t total_delta = wave_reduce_add(split_delta(o, w, num_obs, num_new));
+                if (split_verdict(total_delta, num_obs, num_new, pos - sub_start)) break;
                 if (lane < 10) {
                     L.obs[lane] = o + w;
                     L.nw[lane] = 0;
@@ -3329,10 +3294,10 @@ __global__ __launch_bounds__(64) void k_parse_lazy(Config cfg, const uint8_t *__
                     total += f[k];
                 }
                 total = wave_reduce_add(total);
-                const uint32_t cutoff = total >> 10;
+                const uint32_t cutoff = recalc_cutoff(total);
                 uint32_t num_used = 0;
                 for (uint32_t k = 0; k < 4; k++) num_used += (uint32_t)__popcll(__ballot(f[k] > cutoff));
-                min_len = hc_choose_min_len(num_used, cfg.hc_depth);
+                min_len = choose_min_match_len(num_used, cfg.hc_depth);
                 const uint32_t a = n - next_recalc, bb = pos - sub_start;
                 next_recalc += a < bb ? a : bb;
             }

@@ -31,25 +31,19 @@
 namespace gzpx {
 
 #include "gzpx_deflate.h"  // length_slot, offset_slot, offset_sym: the slots and extra bits the costs and tallies go by
+#include "gzpx_policy.h"   // lz_hash, where a block ends (max_block_end, the split check), the minimum match length
 
 namespace {
 
 constexpr uint32_t kNoWindow = 32768;
-constexpr uint32_t kNoMinMatch = 3, kNoMaxMatch = 258;
-constexpr uint32_t kNoSoftMaxBlock = 300000;       // SOFT_MAX_BLOCK_LENGTH
-constexpr uint32_t kNoMaxBlock = kNoSoftMaxBlock + kMinBlockLen - 1;
-constexpr uint32_t kNoCacheLen = kNoSoftMaxBlock * 5;  // MATCH_CACHE_LENGTH
+constexpr uint32_t kNoMinMatch = kMinMatchLen, kNoMaxMatch = 258;
+constexpr uint32_t kNoMaxBlock = kSoftMaxBlockLen + kMinBlockLen - 1;
+constexpr uint32_t kNoCacheLen = kSoftMaxBlockLen * 5;  // MATCH_CACHE_LENGTH
 constexpr uint32_t kNoCacheSlack = (kNoMaxMatch - kNoMinMatch + 1) + kNoMaxMatch - 1;
 constexpr uint32_t kNoBitCost = 16;
 constexpr uint32_t kNoLitNostat = 13, kNoLenNostat = 13, kNoOffNostat = 10;
-constexpr uint32_t kNoNumObs = 10, kNoNumLitObs = 8, kNoObsPerCheck = 512;
 constexpr uint32_t kNoNumLitlen = 288, kNoNumOffset = 32, kNoEob = 256, kNoFirstLen = 257;
 constexpr int32_t kNoDead = -32768;  // MATCHFINDER_INITVAL: never within the window of any position
-
-// choose_min_match_len (deflate_compress.c): by the number of distinct literals in use
-__device__ const uint8_t kNoMinLens[80] = {9, 9, 9, 9, 9, 9, 8, 8, 7, 7, 6, 6, 6, 6, 6, 6, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5,
-                                           5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 4, 4, 4, 4, 4, 4, 4, 4, 4,
-                                           4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4};
 
 struct NoMatch {
     uint16_t length, offset;
@@ -97,7 +91,6 @@ __device__ __forceinline__ uint32_t no_le32(const uint8_t *p) {
 __device__ __forceinline__ uint32_t no_le24(const uint8_t *p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
 }
-__device__ __forceinline__ uint32_t no_hash(uint32_t v, uint32_t bits) { return (v * 0x1E35A7BDu) >> (32 - bits); }
 // lz_extend, four bytes per step (unaligned dword loads are fine in global memory; both pointers stay inside the block:
 // len + 4 <= max_len <= bytes left)
 __device__ uint32_t no_lz_extend(const uint8_t *a, const uint8_t *b, uint32_t len, uint32_t max_len) {
@@ -113,24 +106,12 @@ __device__ uint32_t no_lz_extend(const uint8_t *a, const uint8_t *b, uint32_t le
     return len;
 }
 
-__device__ uint32_t no_choose_min_match_len(uint32_t num_used_literals, uint32_t max_search_depth) {
-    uint32_t min_len = kNoMinMatch;
-    if (num_used_literals < 80) min_len = kNoMinLens[num_used_literals];
-    if (max_search_depth < 16) {
-        const uint32_t cap = max_search_depth < 5 ? 4 : max_search_depth < 10 ? 5 : 7;
-        if (min_len > cap) min_len = cap;
-    }
-    return min_len;
-}
-
-// calculate_min_match_len (the first 4096 bytes of the block; libdeflate >= 1.1x: scans shorter than 512 bytes use 3)
+// calculate_min_match_len (the first 4096 bytes of the block)
 __device__ uint32_t no_calc_min_len(const uint8_t *data, uint32_t data_len, uint32_t depth, uint32_t compat) {
-    uint32_t used[8] = {0, 0, 0, 0, 0, 0, 0, 0}, num_used = 0;
-    if (compat == 0 && data_len < 512) return kNoMinMatch;
-    if (data_len > 4096) data_len = 4096;
-    for (uint32_t i = 0; i < data_len; i++) used[data[i] >> 5] |= 1u << (data[i] & 31u);
-    for (uint32_t k = 0; k < 8; k++) num_used += (uint32_t)__popc(used[k]);
-    return no_choose_min_match_len(num_used, depth);
+    uint32_t used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t scan_len = min_len_scan_len(data_len, compat);
+    for (uint32_t i = 0; i < scan_len; i++) used[data[i] >> 5] |= 1u << (data[i] & 31u);
+    return scan_len ? min_len_of_census(used, depth) : kMinMatchLen;
 }
 
 // bt_matchfinder_advance_one_byte (record = get_matches, else skip_byte); positions are absolute in the block
@@ -141,8 +122,8 @@ __device__ NoMatch *no_bt_advance(NoLane &L, const uint8_t *in, uint32_t cur_pos
     const int32_t cutoff = (int32_t)cur_pos - (int32_t)kNoWindow;
     const uint32_t next_hashseq = no_le32(in_next + 1);
     const uint32_t hash3 = next_hashes[0], hash4 = next_hashes[1];
-    next_hashes[0] = no_hash(next_hashseq & 0xFFFFFFu, 16);
-    next_hashes[1] = no_hash(next_hashseq, 16);
+    next_hashes[0] = lz_hash(next_hashseq & 0xFFFFFFu, 16);
+    next_hashes[1] = lz_hash(next_hashseq, 16);
 
     int32_t cur_node = L.hash3[hash3][0];
     L.hash3[hash3][0] = (int32_t)cur_pos;
@@ -287,35 +268,19 @@ __device__ void no_make_code_lens(NoLane &L, uint32_t num_syms, uint32_t max_len
 }
 
 struct NoStats {
-    uint32_t new_obs[kNoNumObs], obs[kNoNumObs], num_new, num;
-    uint32_t prev_obs[kNoNumObs], prev_num;
+    uint32_t new_obs[kNumObs], obs[kNumObs], num_new, num;
+    uint32_t prev_obs[kNumObs], prev_num;
 };
 
-// do_end_block_check (shared by every splitting parser; restated in k_parse_hc's form as well)
-__device__ bool no_end_block_check(NoStats &st, uint32_t block_length) {
-    if (st.num > 0) {
-        uint32_t total_delta = 0;
-        for (uint32_t i = 0; i < kNoNumObs; i++) {
-            const uint32_t expected = st.obs[i] * st.num_new, actual = st.new_obs[i] * st.num;
-            total_delta += actual > expected ? actual - expected : expected - actual;
-        }
-        const uint32_t num_items = st.num + st.num_new;
-        uint32_t cutoff = st.num_new * 200 / 512 * st.num;
-        if (block_length < 10000 && num_items < 8192)
-            cutoff += (uint32_t)((unsigned long long)cutoff * (8192 - num_items) / 8192);
-        if (total_delta + (block_length / 4096) * st.num >= cutoff) return true;
-    }
-    for (uint32_t i = 0; i < kNoNumObs; i++) {
-        st.num += st.new_obs[i];
-        st.obs[i] += st.new_obs[i];
-        st.new_obs[i] = 0;
-    }
-    st.num_new = 0;
-    return false;
+// do_end_block_check: true ends the block (else the caller merges the new observations: no_merge_stats)
+__device__ bool no_end_block_check(const NoStats &st, uint32_t block_length) {
+    uint32_t total_delta = 0;
+    for (uint32_t i = 0; i < kNumObs; i++) total_delta += split_delta(st.obs[i], st.new_obs[i], st.num, st.num_new);
+    return split_verdict(total_delta, st.num, st.num_new, block_length);
 }
 
 __device__ void no_merge_stats(NoLane &L, NoStats &st) {
-    for (uint32_t i = 0; i < kNoNumObs; i++) {
+    for (uint32_t i = 0; i < kNumObs; i++) {
         st.num += st.new_obs[i];
         st.obs[i] += st.new_obs[i];
         st.new_obs[i] = 0;
@@ -347,7 +312,7 @@ __device__ void no_optimize_block(NoLane &L, NoStats &st, NoNode *nodes, const u
         const uint32_t hi = block_length - 1 + kNoMaxMatch < kNoMaxBlock ? block_length - 1 + kNoMaxMatch : kNoMaxBlock;
         for (uint32_t i = block_length; i <= hi; i++) nodes[i].cost_to_end = 0x80000000u;
     }
-    // deflate_choose_default_litlen_costs
+    // deflate_choose_default_litlen_costs (its cutoff, 1/2048 of the block, is its own: not recalc_cutoff)
     uint32_t lit_cost, len_sym_cost;
     {
         uint32_t num_used = 0, literal_freq = block_length, match_freq = 0, i;
@@ -357,7 +322,7 @@ __device__ void no_optimize_block(NoLane &L, NoStats &st, NoNode *nodes, const u
         for (i = 0; i < 256; i++)
             if (L.litfreq[i] > cutoff) num_used++;
         if (num_used == 0) num_used = 1;
-        for (i = no_choose_min_match_len(num_used, depth); i <= kNoMaxMatch; i++) {
+        for (i = choose_min_match_len(num_used, depth); i <= kNoMaxMatch; i++) {
             match_freq += L.mlf[i];
             literal_freq -= i * L.mlf[i];
         }
@@ -372,7 +337,7 @@ __device__ void no_optimize_block(NoLane &L, NoStats &st, NoNode *nodes, const u
         for (uint32_t i = 0; i < 30; i++) L.cost_off[i] = no_default_offset_cost(i);
     } else {  // deflate_adjust_costs: the more the block differs from the previous one, the more the defaults count
         unsigned long long total_delta = 0;
-        for (uint32_t i = 0; i < kNoNumObs; i++) {
+        for (uint32_t i = 0; i < kNumObs; i++) {
             const unsigned long long prev = (unsigned long long)st.prev_obs[i] * st.num;
             const unsigned long long cur = (unsigned long long)st.obs[i] * st.prev_num;
             total_delta += prev > cur ? prev - cur : cur - prev;
@@ -484,7 +449,7 @@ __global__ __launch_bounds__(64, GZPX_NO_WAVES) void k_near_optimal(Config cfg, 
             L.child[i] = kNoDead;
         }
         NoStats st;
-        for (uint32_t i = 0; i < kNoNumObs; i++) st.new_obs[i] = st.obs[i] = st.prev_obs[i] = 0;
+        for (uint32_t i = 0; i < kNumObs; i++) st.new_obs[i] = st.obs[i] = st.prev_obs[i] = 0;
         st.num_new = st.num = st.prev_num = 0;
         for (uint32_t i = 0; i <= kNoMaxMatch; i++) L.new_mlf[i] = L.mlf[i] = 0;
 
@@ -494,11 +459,11 @@ __global__ __launch_bounds__(64, GZPX_NO_WAVES) void k_near_optimal(Config cfg, 
         uint32_t next_hashes[2] = {0, 0};
         do {
             // a new DEFLATE block
-            const uint32_t max_block_end = (n - block_begin < kNoSoftMaxBlock + kMinBlockLen) ? n : block_begin + kNoSoftMaxBlock;
+            const uint32_t block_limit = max_block_end(block_begin, n, kSoftMaxBlockLen);
             uint32_t prev_check = 0xFFFFFFFFu;  // prev_end_block_check (none yet)
             bool change_detected = false;
             uint32_t next_observation = in_next;
-            const uint32_t min_len = no_calc_min_len(in + block_begin, max_block_end - block_begin, depth, cfg.compat == 0 ? 0u : 1u);
+            const uint32_t min_len = no_calc_min_len(in + block_begin, block_limit - block_begin, depth, cfg.compat == 0 ? 0u : 1u);
             for (;;) {
                 NoMatch *matches = cache_ptr;
                 uint32_t best_len = 0;
@@ -513,13 +478,12 @@ __global__ __launch_bounds__(64, GZPX_NO_WAVES) void k_near_optimal(Config cfg, 
                 }
                 if (in_next >= next_observation) {
                     if (best_len >= min_len) {
-                        st.new_obs[kNoNumLitObs + (best_len >= 9 ? 1u : 0u)]++;
+                        st.new_obs[obs_match(best_len)]++;
                         st.num_new++;
                         next_observation = in_next + best_len;
                         L.new_mlf[best_len]++;
                     } else {
-                        const uint32_t lit = in[in_next];
-                        st.new_obs[((lit >> 5) & 0x6u) | (lit & 1u)]++;
+                        st.new_obs[obs_literal(in[in_next])]++;
                         st.num_new++;
                         next_observation = in_next + 1;
                     }
@@ -544,9 +508,9 @@ __global__ __launch_bounds__(64, GZPX_NO_WAVES) void k_near_optimal(Config cfg, 
                         cache_ptr++;
                     } while (--best_len);
                 }
-                if (in_next >= max_block_end) break;
+                if (in_next >= block_limit) break;
                 if (cache_ptr >= cache + kNoCacheLen) break;
-                if (!(st.num_new >= kNoObsPerCheck && in_next - block_begin >= kMinBlockLen && n - in_next >= kMinBlockLen)) continue;
+                if (!split_due(st.num_new, in_next, block_begin, n)) continue;
                 if (no_end_block_check(st, in_next - block_begin)) {
                     change_detected = true;
                     break;
@@ -587,19 +551,19 @@ __global__ __launch_bounds__(64, GZPX_NO_WAVES) void k_near_optimal(Config cfg, 
             }
             nsub++;
             // deflate_near_optimal_save_stats
-            for (uint32_t i = 0; i < kNoNumObs; i++) st.prev_obs[i] = st.obs[i];
+            for (uint32_t i = 0; i < kNumObs; i++) st.prev_obs[i] = st.obs[i];
             st.prev_num = st.num;
             if (rewind) {
                 const size_t keep = (size_t)(orig_cache_ptr - cache_ptr);
                 for (size_t i = 0; i < keep; i++) cache[i] = cache_ptr[i];  // (memmove towards lower addresses)
                 cache_ptr = cache + keep;
                 // deflate_near_optimal_clear_old_stats: only the chunk behind the block's end stays
-                for (uint32_t i = 0; i < kNoNumObs; i++) st.obs[i] = 0;
+                for (uint32_t i = 0; i < kNumObs; i++) st.obs[i] = 0;
                 st.num = 0;
                 for (uint32_t i = 0; i <= kNoMaxMatch; i++) L.mlf[i] = 0;
             } else {
                 cache_ptr = cache;
-                for (uint32_t i = 0; i < kNoNumObs; i++) st.new_obs[i] = st.obs[i] = 0;
+                for (uint32_t i = 0; i < kNumObs; i++) st.new_obs[i] = st.obs[i] = 0;
                 st.num_new = st.num = 0;
                 for (uint32_t i = 0; i <= kNoMaxMatch; i++) L.new_mlf[i] = L.mlf[i] = 0;
             }

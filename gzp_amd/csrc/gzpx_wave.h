@@ -1,12 +1,12 @@
 // gzpx_wave.h -- what more than one stage or more than one header of gzpx_kernels.hip uses: the measurement switch
-// GZPX_EXP and the GZPX_EXPERIMENT counter tables, wave_sync, rdlane / uniform, the two pinning macros, lz_hash15,
+// GZPX_EXP and the GZPX_EXPERIMENT counter tables, wave_sync, rdlane / uniform, the two pinning macros,
 // load_le32_global, the wave and workgroup scans, dword4, length_entry / build_length_table.  It also brings in the
-// two headers of shared arithmetic, gzpx_deflate.h (with its wave routines, behind wave_sync) and gzpx_crc.h (with its
-// device half, behind dword4), so that every stage of gzpx_kernels.hip and every decode header finds all of this in
-// front of it.
+// three headers of shared arithmetic, gzpx_policy.h (libdeflate's parsing rules: lz_hash, where a sub-block ends, which
+// matches count), gzpx_deflate.h (with its wave routines, behind wave_sync) and gzpx_crc.h (with its device half,
+// behind dword4), so that every stage of gzpx_kernels.hip and every decode header finds all of this in front of it.
 //
 // Nothing here replaces a routine of the reference: these are the lane-level idioms its scalar loops turn into on a
-// 64-lane wave.  lz_hash15 is libdeflate's lz_hash over 15 bits (ht_matchfinder, hc_matchfinder).
+// 64-lane wave.
 //
 // Included once by gzpx_kernels.hip inside namespace gzpx, in front of the first kernel.  Needs gzpx_device.h (Config)
 // and <hip/hip_runtime.h> alone.
@@ -19,6 +19,9 @@
 #else
 #define GZPX_EXP(cfg, bit) 0u
 #endif
+
+// libdeflate's parsing rules: lz_hash, the block-end constants, the split check, the minimum match length
+#include "gzpx_policy.h"
 
 // ------------------------------------------------------------------------------------------
 // small device helpers
@@ -54,8 +57,6 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 #else
 #define GZPX_KEEP_ARM_APART() ((void)0)
 #endif
-
-__device__ __forceinline__ uint32_t lz_hash15(uint32_t v) { return (v * 0x1E35A7BDu) >> 17; }
 
 // little-endian u32 at an arbitrary byte address of global memory via two aligned loads
 __device__ __forceinline__ uint32_t load_le32_global(const uint8_t *p) {

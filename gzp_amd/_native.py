@@ -53,6 +53,9 @@ FIND_NO_LINES = -1      # GZPX_FIND_NO_LINES
 SELECT_INVERT = 1       # GZPX_SELECT_INVERT
 FINDSET_MAX_PATTERNS = 256  # GZPX_FINDSET_MAX_PATTERNS
 FINDSET_MAX_BYTES = 16384   # GZPX_FINDSET_MAX_BYTES: the sum of a set's pattern lengths
+FIELDS_MAX_RANGES = 64           # GZPX_FIELDS_MAX_RANGES
+FIELDS_COMPLEMENT = 1            # GZPX_FIELDS_COMPLEMENT
+FIELDS_TO_END = (1 << 64) - 1    # GZPX_FIELDS_TO_END: as a field range's end, through the line's last field
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -85,6 +88,7 @@ EXPORTS = [
     "gzpx_find_device", "gzpx_dctx_last_find_ms",
     "gzpx_select_lines_device", "gzpx_dctx_last_select_ms", "gzpx_read_lines_table_device",
     "gzpx_find_set_device", "gzpx_dctx_last_find_set_ms", "gzpx_select_lines_set_device",
+    "gzpx_read_fields_device", "gzpx_read_fields_table_device", "gzpx_dctx_last_fields_ms",
 ]
 
 
@@ -308,6 +312,12 @@ class GzpxLib:
         L.gzpx_read_lines_table_device.restype = i32
         L.gzpx_read_lines_table_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, sz, psz, vp, vp, psz,
                                                    ctypes.POINTER(GzpxCheckInfo), vp]
+        for fn in (L.gzpx_read_fields_device, L.gzpx_read_fields_table_device):
+            fn.restype = i32
+            fn.argtypes = [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint, vp, sz, ctypes.c_uint, vp, sz, psz, vp, psz,
+                           ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_fields_ms.restype = i32
+        L.gzpx_dctx_last_fields_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_inflate_batch_device.restype = i32
         L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
                                                 ctypes.POINTER(GzpxCheckInfo), vp]
@@ -1162,6 +1172,51 @@ class DContext:
         if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
             self._raise(rc, info)
         raise GzpxError(rc, self.lib.strerror(rc))
+
+    # ---- fields of lines (gzpx_fields.h)
+    def _read_fields(self, fn, index, lines, d_in_ptr, in_len, ranges_ptr, n_ranges, field_delim, fields, complement, d_out_ptr,
+                     out_cap, offsets_ptr, stream):
+        f = np.ascontiguousarray(np.asarray(fields, dtype=np.uint64).reshape(-1, 2))
+        out_len, bad = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = fn(self.h, index.h, lines.h, d_in_ptr, in_len, ranges_ptr, n_ranges, int(field_delim), f.ctypes.data, f.shape[0],
+                FIELDS_COMPLEMENT if complement else 0, d_out_ptr, out_cap if d_out_ptr is not None else 0, ctypes.byref(out_len),
+                offsets_ptr, ctypes.byref(bad), ctypes.byref(info), stream)
+        if rc == OK:
+            return out_len.value
+        if bad.value != ctypes.c_size_t(-1).value:
+            raise GzpxError(rc, "line range %d does not lie in the stream" % bad.value, range_index=bad.value)
+        if rc == ERR_INSUFFICIENT_SPACE and out_len.value:
+            raise GzpxError(rc, "the selected fields hold %d bytes" % out_len.value, needed=out_len.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def read_fields_device(self, index, lines, d_in_ptr, in_len, line_ranges, field_delim, fields, d_out_ptr, out_cap,
+                           complement=False, stream=None):
+        """cut -f on the lines of line_ranges[n, 2]: of every line the fields whose numbers (from 0) lie in `fields`, a
+        sequence of [begin, end) pairs, ascending and disjoint, FIELDS_TO_END as the last end for "through the last field"
+        (complement: every field that does not), joined by the byte field_delim, then the line's delimiter if it has one;
+        into d_out back to back.  Returns (out_len, out_offsets uint64[n + 1]).  d_out_ptr None is the size query.  A bad
+        line range raises GzpxError with .range_index; too small an out_cap raises it with .needed."""
+        r = np.ascontiguousarray(np.asarray(line_ranges, dtype=np.uint64).reshape(-1, 2))
+        offs = np.zeros(r.shape[0] + 1, dtype=np.uint64)
+        out_len = self._read_fields(self.lib.L.gzpx_read_fields_device, index, lines, d_in_ptr, in_len, r.ctypes.data, r.shape[0],
+                                    field_delim, fields, complement, d_out_ptr, out_cap, offs.ctypes.data, stream)
+        return out_len, offs
+
+    def read_fields_table_device(self, index, lines, d_in_ptr, in_len, d_line_ranges_ptr, n_ranges, field_delim, fields, d_out_ptr,
+                                 out_cap, complement=False, d_out_offsets_ptr=None, stream=None):
+        """read_fields_device with its tables in device memory: d_line_ranges_ptr is uint64[n_ranges, 2] (the table
+        select_lines_device wrote, for one), the optional d_out_offsets_ptr uint64[n_ranges + 1].  Returns out_len."""
+        return self._read_fields(self.lib.L.gzpx_read_fields_table_device, index, lines, d_in_ptr, in_len, d_line_ranges_ptr,
+                                 n_ranges, field_delim, fields, complement, d_out_ptr, out_cap, d_out_offsets_ptr, stream)
+
+    def last_fields_ms(self):
+        """HIP-event durations of the last read_fields call's passes behind the search: (carry + scan, count + scan, write)."""
+        ms = (ctypes.c_float * 3)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_fields_ms(self.h, ms))
+        return ms[0], ms[1], ms[2]
 
     # ---- batches of raw / zlib / gzip members that lie in device memory (gzpx_wrap.h)
     def inflate_batch_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr,

@@ -1603,6 +1603,43 @@ struct FindSetState : NoCopy {
     }
 };
 
+// fields of lines (gzpx_read_fields_device and its table form): the line search's state in front, then its own pieces
+struct FieldsState : NoCopy {
+    Event ev[4];        // carry + scan [0..1], count + scan [1..2], write [2..3]
+    bool have = false;  // ev[0..2] hold the last call's two counting stages; wrote: ev[3] its writing pass
+    bool wrote = false;
+    FieldsScratch fl;
+    FlSet *h_set = nullptr;     // pinned: the compiled field list on its way in
+    uint64_t *h_rec = nullptr;  // pinned: the record on its way out
+    Allocs once;                // fl.set, fl.rec and the two pinned arrays above
+    size_t range_cap = 0, host_cap = 0, piece_cap = 0;
+    uint64_t *h_out_off = nullptr;  // pinned: out_offsets on their way out
+    Allocs ranges;  // fl.pfirst, fl.out_off
+    Allocs host;    // h_out_off: a call whose tables lie in device memory needs none
+    Allocs pieces;  // fl.carry, cin, cnt, obase
+    int reserve(size_t n_ranges, size_t n_pieces, bool host_tables) {
+        if (!fl.rec) {
+            GZPX_TRY(once.dev(fl.set, sizeof(FlSet)));
+            GZPX_TRY(once.dev(fl.rec, kFlRecWords * 8));
+            GZPX_TRY(once.pinned(h_set, sizeof(FlSet)));
+            GZPX_TRY(once.pinned(h_rec, kFlRecWords * 8));
+            for (Event &e : ev) GZPX_TRY(e.create(true));
+        }
+        GZPX_TRY(grow(ranges, range_cap, n_ranges, n_ranges + n_ranges / 4 + 64, [&](size_t cap) -> int {
+            GZPX_TRY(ranges.dev(fl.pfirst, (cap + 1) * 8));
+            return ranges.dev(fl.out_off, (cap + 1) * 8);
+        }));
+        GZPX_TRY(grow(host, host_cap, host_tables ? n_ranges : 0, n_ranges + n_ranges / 4 + 64,
+                      [&](size_t cap) { return host.pinned(h_out_off, (cap + 1) * 8); }));
+        return grow(pieces, piece_cap, n_pieces + 1, n_pieces + n_pieces / 8 + 16, [&](size_t cap) -> int {
+            GZPX_TRY(pieces.dev(fl.carry, cap * 4));
+            GZPX_TRY(pieces.dev(fl.cin, cap * 8));
+            GZPX_TRY(pieces.dev(fl.cnt, cap * 4));
+            return pieces.dev(fl.obase, (cap + 1) * 8);
+        });
+    }
+};
+
 }  // namespace
 
 // (members are destroyed last to first: memory and events of the slots and of each kind of call, then the streams)
@@ -1626,6 +1663,7 @@ struct gzpx_dctx : NoCopy {
     FindState find;
     SelectState select;
     FindSetState find_set;
+    FieldsState fields;
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -2801,6 +2839,138 @@ int gzpx_read_lines_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx
                                  void *hip_stream) {
     return read_lines(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, d_out, out_cap, out_len, d_out_offsets,
                       d_byte_ranges, bad_range, info, hip_stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- fields of lines (gzpx_fields.h)
+namespace {
+
+// The field list and the flags as the kernels take them: the field numbers at which membership in S changes, ascending
+// (ranges that touch are one), field 0 outside S, UINT64_MAX behind them.  False: the list breaks a rule of gzpx.h.
+bool fields_compile(const gzpx_range *fields, size_t n_fields, unsigned flags, FlSet &s) {
+    static_assert(kFlMaxRanges == GZPX_FIELDS_MAX_RANGES, "the public constant states the kernels' limit");
+    if (!fields || n_fields == 0 || n_fields > kFlMaxRanges || (flags & ~GZPX_FIELDS_COMPLEMENT)) return false;
+    size_t n = 0;
+    for (size_t i = 0; i < n_fields; i++) {
+        const uint64_t b = fields[i].begin, e = fields[i].end;
+        if (b >= e || (i && fields[i - 1].end > b) || (e == GZPX_FIELDS_TO_END && i + 1 != n_fields)) return false;
+        if (n && s.b[n - 1] == b) n--;
+        else s.b[n++] = b;
+        if (e != GZPX_FIELDS_TO_END) s.b[n++] = e;
+    }
+    if (flags & GZPX_FIELDS_COMPLEMENT) {
+        if (n && s.b[0] == 0) {
+            for (size_t i = 1; i < n; i++) s.b[i - 1] = s.b[i];
+            n--;
+        } else {
+            for (size_t i = n; i > 0; i--) s.b[i] = s.b[i - 1];
+            s.b[0] = 0;
+            n++;
+        }
+    }
+    s.n = n;
+    for (size_t i = n; i < kFlBounds; i++) s.b[i] = UINT64_MAX;
+    return true;
+}
+
+// gzpx_read_fields_device, and with `on_device` gzpx_read_fields_table_device: line_ranges and out_offsets are then
+// device arrays.  The line search of read_lines, then the three passes of gzpx_fields.h in place of the gather, enqueued
+// together: whether the output fits is decided on the device, and one record comes back behind the last of them.
+int read_fields(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                const gzpx_range *line_ranges, bool on_device, size_t n_ranges, unsigned field_delim, const gzpx_range *fields,
+                size_t n_fields, unsigned flags, void *d_out, size_t out_cap, size_t *out_len, uint64_t *out_offsets,
+                size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
+    if (!c || !ix || !lt || !out_len || (!line_ranges && n_ranges) || (!d_in && in_len) || (!d_out && out_cap))
+        return GZPX_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (bad_range) *bad_range = (size_t)-1;
+    std::unique_lock<std::mutex> lk(c->mu);
+    FieldsState &f = c->fields;
+    c->lines.stages = 0;
+    c->lines.last_members = 0;
+    f.have = f.wrote = false;
+    if (!lines_match(c, ix, lt, in_len) || n_ranges > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    if (field_delim > 255u || field_delim == lt->delim) return GZPX_ERR_INVALID_ARG;
+    FlSet set;
+    if (!fields_compile(fields, n_fields, flags, set)) return GZPX_ERR_INVALID_ARG;
+    if (n_ranges == 0) {
+        if (out_offsets && !on_device) out_offsets[0] = 0;
+        if (out_offsets && on_device) {
+            if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+            HIP_TRY(hipMemset(out_offsets, 0, 8));
+        }
+        return GZPX_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    uint64_t bytes = 0;  // of the ranges, in staging
+    GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, (const uint64_t *)line_ranges, n_ranges, 2u, bad_range, info,
+                          (hipStream_t)hip_stream, &bytes, on_device));
+    const uint64_t grid = fields_pieces(bytes, n_ranges);
+    if (grid > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;  // (the passes' grid)
+    GZPX_TRY(f.reserve(n_ranges, (size_t)grid, !on_device));
+    hipStream_t stream = c->stream;
+    Drain drain{{stream}, 1};
+    const RangeScratch &rr = c->ranges.rr;
+    uint64_t *d_off = on_device && out_offsets ? out_offsets : f.fl.out_off;
+    *f.h_set = set;
+    HIP_TRY(hipMemcpyAsync(f.fl.set, f.h_set, sizeof(FlSet), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(f.ev[0], stream));
+    launch_fields_carry(c->stage.d, (uint32_t)n_ranges, rr, f.fl, lt->delim, field_delim, (uint32_t)grid, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f.ev[1], stream));
+    launch_fields_count(c->stage.d, (uint32_t)n_ranges, rr, f.fl, lt->delim, field_delim, (uint32_t)grid, d_off, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f.ev[2], stream));
+    if (d_out) {
+        launch_fields_write(c->stage.d, (uint32_t)n_ranges, rr, f.fl, lt->delim, field_delim, (uint32_t)grid, (uint8_t *)d_out,
+                            out_cap, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(f.ev[3], stream));
+    }
+    HIP_TRY(hipMemcpyAsync(f.h_rec, f.fl.rec, kFlRecWords * 8, hipMemcpyDeviceToHost, stream));
+    if (out_offsets && !on_device) HIP_TRY(hipMemcpyAsync(f.h_out_off, d_off, (n_ranges + 1) * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    f.have = true;
+    const uint64_t total = f.h_rec[kFlRecTotal];
+    f.wrote = d_out && total <= out_cap;
+    *out_len = (size_t)total;
+    if (out_offsets && !on_device) memcpy(out_offsets, f.h_out_off, (n_ranges + 1) * 8);
+    return d_out && total > out_cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gzpx_read_fields_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                            const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_range *fields,
+                            size_t n_fields, unsigned flags, void *d_out, size_t out_cap, size_t *out_len, uint64_t *out_offsets,
+                            size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
+    return read_fields(c, ix, lt, d_in, in_len, line_ranges, false, n_ranges, field_delim, fields, n_fields, flags, d_out, out_cap,
+                       out_len, out_offsets, bad_range, info, hip_stream);
+}
+
+int gzpx_read_fields_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                                  const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_range *fields,
+                                  size_t n_fields, unsigned flags, void *d_out, size_t out_cap, size_t *out_len,
+                                  uint64_t *d_out_offsets, size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
+    return read_fields(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, field_delim, fields, n_fields, flags, d_out, out_cap,
+                       out_len, d_out_offsets, bad_range, info, hip_stream);
+}
+
+int gzpx_dctx_last_fields_ms(gzpx_dctx *ctx, float ms[3]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ms[0] = ms[1] = ms[2] = 0.0f;
+    const FieldsState &f = ctx->fields;
+    if (!f.have) return GZPX_OK;
+    if (hipEventElapsedTime(&ms[0], f.ev[0], f.ev[1]) != hipSuccess || hipEventElapsedTime(&ms[1], f.ev[1], f.ev[2]) != hipSuccess)
+        return GZPX_ERR_DEVICE;
+    if (f.wrote && hipEventElapsedTime(&ms[2], f.ev[2], f.ev[3]) != hipSuccess) return GZPX_ERR_DEVICE;
+    return GZPX_OK;
 }
 
 }  // extern "C"

@@ -419,6 +419,43 @@ void launch_select_mark(const FindBatch &b, const FindScratch &f, const FindMatc
 void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n_records, uint64_t group, uint64_t n_lines,
                         int invert, uint64_t *d_runs, uint64_t cap, hipStream_t stream);
 
+// Fields of lines (gzpx_fields.h): behind a line search of line ranges (launch_lines_find, per == 2) the ranges' bytes
+// lie in staging, range r at r.src[r] with r.out_off[r + 1] - r.out_off[r] bytes.  They are cut on the 16 KiB grid of
+// staging into PIECES, the pieces of all ranges numbered in one row; three passes over them (carry, count, write) keep
+// the bytes of the selected fields.  The host compiles the field list into an FlSet: the field numbers at which
+// membership in S changes, ascending, field 0 outside S; n of them, the rest of the array UINT64_MAX.
+constexpr uint32_t kFlPiece = 16384;
+constexpr uint32_t kFlMaxRanges = 64;                  // GZPX_FIELDS_MAX_RANGES
+constexpr uint32_t kFlBounds = 2u * kFlMaxRanges + 8u;  // 129 changes at most (64 ranges, complemented), and sentinels
+struct FlSet {
+    uint64_t b[kFlBounds];
+    uint64_t n;
+};
+// the record (u64 words): bytes of output, pieces
+enum { kFlRecTotal = 0, kFlRecPieces = 1, kFlRecWords = 4 };
+struct FieldsScratch {
+    FlSet *set = nullptr;         // the compiled field list
+    uint64_t *pfirst = nullptr;   // [ranges + 1] the first piece of every range; [ranges] = the pieces
+    uint64_t *out_off = nullptr;  // [ranges + 1] where every range's output starts (a caller's device array takes its place)
+    uint32_t *carry = nullptr;    // [pieces] of a piece: bit 31 it holds a line delimiter or is a range's first, bit 30 it is a
+                                  //          range's first, below them the field delimiters behind its last line delimiter
+    uint64_t *cin = nullptr;      // [pieces] the field number of a piece's first byte
+    uint32_t *cnt = nullptr;      // [pieces] the bytes a piece keeps
+    uint64_t *obase = nullptr;    // [pieces + 1] where they go in the output
+    uint64_t *rec = nullptr;      // [kFlRecWords]
+};
+// the pieces of n_ranges ranges that hold `total` bytes, at most: a range of len > 0 bytes touches at most len / 16 KiB + 2
+inline uint64_t fields_pieces(uint64_t total, uint64_t n_ranges) { return total / kFlPiece + 2u * n_ranges; }
+// the pieces, the carries and their scan: f.pfirst, f.carry, f.cin
+void launch_fields_carry(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
+                         uint32_t field_delim, uint32_t grid, hipStream_t stream);
+// behind it: f.cnt, f.obase, d_out_off[n_ranges + 1] and the record
+void launch_fields_count(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
+                         uint32_t field_delim, uint32_t grid, uint64_t *d_out_off, hipStream_t stream);
+// behind both: the kept bytes to d_out, unless the record's total exceeds out_cap
+void launch_fields_write(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
+                         uint32_t field_delim, uint32_t grid, uint8_t *d_out, uint64_t out_cap, hipStream_t stream);
+
 // Search for a set of patterns (gzpx_findset.h).  The host compiles the set into an FsSet, the form the kernels stage
 // into LDS: q = min(shortest pattern, 4); the WINDOW of a pattern is its first q bytes as a little-endian number.
 constexpr uint32_t kFsMaxPatterns = 256;  // GZPX_FINDSET_MAX_PATTERNS

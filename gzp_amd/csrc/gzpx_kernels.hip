@@ -5415,6 +5415,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_lines.h"
 #include "gzpx_find.h"
 #include "gzpx_select.h"
+#include "gzpx_fields.h"
 #include "gzpx_findset.h"
 #include "gzpx_wrap.h"
 #include "gzpx_cksum.h"
@@ -5949,6 +5950,41 @@ void launch_select_runs(const SelectScratch &s, const FindScratch &f, uint64_t n
     if (d_runs && cap)
         hipLaunchKernelGGL(k_sl_runs_write, dim3(groups), dim3(kSlRunThreads), 0, stream, bits, n_records, inv,
                            (const uint32_t *)s.cnt, (const uint32_t *)s.bases, group, n_lines, d_runs, cap);
+}
+
+// Fields of lines (gzpx_fields.h), behind launch_lines_find of line ranges: three passes over the ranges' bytes in
+// staging with no host round trip between them.  `grid` = fields_pieces(): the pieces are counted on the device.
+static FlArgs fields_args(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
+                          uint32_t field_delim) {
+    return FlArgs{d_stage, r.src, r.out_off, f.pfirst, n_ranges, delim, field_delim};
+}
+
+void launch_fields_carry(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
+                         uint32_t field_delim, uint32_t grid, hipStream_t stream) {
+    hipLaunchKernelGGL(k_fl_plan, dim3(1), dim3(kFlThreads), 0, stream, n_ranges, (const uint64_t *)r.src,
+                       (const uint64_t *)r.out_off, f.pfirst, f.rec);
+    if (grid)
+        hipLaunchKernelGGL(k_fl_carry, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, f, delim, field_delim),
+                           f.carry);
+    hipLaunchKernelGGL(k_fl_carry_scan, dim3(1), dim3(kFlThreads), 0, stream, (const uint32_t *)f.carry, (const uint64_t *)f.pfirst,
+                       n_ranges, f.cin);
+}
+
+void launch_fields_count(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
+                         uint32_t field_delim, uint32_t grid, uint64_t *d_out_off, hipStream_t stream) {
+    if (grid)
+        hipLaunchKernelGGL(k_fl_count, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, f, delim, field_delim),
+                           (const FlSet *)f.set, (const uint64_t *)f.cin, f.cnt);
+    hipLaunchKernelGGL(k_fl_scan, dim3(1), dim3(kFlThreads), 0, stream, (const uint32_t *)f.cnt, (const uint64_t *)f.pfirst, n_ranges,
+                       f.obase, d_out_off, f.rec);
+}
+
+void launch_fields_write(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
+                         uint32_t field_delim, uint32_t grid, uint8_t *d_out, uint64_t out_cap, hipStream_t stream) {
+    if (grid)
+        hipLaunchKernelGGL(k_fl_write, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, f, delim, field_delim),
+                           (const FlSet *)f.set, (const uint64_t *)f.cin, (const uint32_t *)f.cnt, (const uint64_t *)f.obase,
+                           (const uint64_t *)f.rec, d_out, out_cap);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

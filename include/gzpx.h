@@ -517,6 +517,58 @@ int gzpx_read_lines_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gz
                                  size_t in_len, const gzpx_range *d_line_ranges, size_t n_ranges, void *d_out, size_t out_cap,
                                  size_t *out_len, uint64_t *d_out_offsets, gzpx_range *d_byte_ranges, size_t *bad_range,
                                  gzpx_check_info *info, void *hip_stream);
+/* ---- fields of lines (gzpx_fields.h): the column half of "rows and columns of a compressed table in HBM" -- the
+ * eight fixed columns of a VCF without its thousands of sample columns, one column of a TSV, the name field of a
+ * SAM-like line -- cut -f with -d on the lines of a device-resident BGZF / Mgzip stream.  The table that
+ * gzpx_select_lines_device leaves in device memory goes straight in; the output is bytes in device memory.
+ * Lines, delimiter and covers.  `plain`, `delim`, D, L, start(k), "line", line ranges, the covers and the members read
+ *   are those of gzpx_read_lines_device, word for word, and so are validation and *bad_range, empty ranges, overlapping
+ *   and repeated ranges (their output is repeated), the context's lock, the slot, hip_stream, "returns synchronised",
+ *   both inflate routes and the report of a failing member (the inflate's error, info->block = its index in the stream).
+ * Field delimiter and field list.  `field_delim` is one byte, any value; above 255, or equal to the lines table's
+ *   delimiter: GZPX_ERR_INVALID_ARG.  The BODY of a line is the line without its delimiter; the unterminated last line
+ *   is all body.  The body splits at every field_delim byte into F = (the number of such bytes) + 1 FIELDS, numbered
+ *   from 0: an empty body is one empty field, consecutive delimiters give empty fields.
+ *   `fields` is a HOST array of 1..GZPX_FIELDS_MAX_RANGES half-open ranges [begin, end) of field numbers, each with
+ *   begin < end, ascending and disjoint (fields[i].end <= fields[i + 1].begin); end == GZPX_FIELDS_TO_END (through the
+ *   line's last field) is allowed in the last range only.  S is the union of the ranges, or with
+ *   GZPX_FIELDS_COMPLEMENT its complement in [0, infinity); an empty S is legal.  A list that breaks a rule, or a flag bit
+ *   other than GZPX_FIELDS_COMPLEMENT: GZPX_ERR_INVALID_ARG with nothing inflated.
+ * Output of one line.  The fields k in S with k < F, ascending, joined by one field_delim; then the line's delimiter,
+ *   if and only if the line has one.  A line in which no selected field exists yields just its delimiter.  Field order
+ *   is never changed and nothing is repeated within a line.  This is cut -f with -d (--complement), WITHOUT cut's special
+ *   case for lines that hold no delimiter: such a line is one field, number 0, and is kept or dropped like any other.
+ *   The same rule per byte, as the kernels apply it -- every output byte is an input byte, in input order; s0 = min S:
+ *   a body byte of field k is kept iff k is in S; the j-th field delimiter of a line (j >= 1, the one in front of field
+ *   j) is kept iff j is in S and j > s0; the line delimiter is always kept.  Field numbers are counted and compared as
+ *   64-bit values from the range's first byte to its last, across pieces of any number: nothing saturates.
+ * Output of the call.  The lines of range 0, then those of range 1, and so on; *out_len = the total; out_offsets[r] =
+ *   where range r's output starts, out_offsets[n_ranges] = *out_len (optional; n_ranges + 1 entries; written whenever
+ *   the call returns GZPX_OK or GZPX_ERR_INSUFFICIENT_SPACE).  d_out == NULL (out_cap 0) is a size query: GZPX_OK, *out_len
+ *   and the offsets are written, and the writing pass does not run.  With d_out given and the total above out_cap the
+ *   call returns GZPX_ERR_INSUFFICIENT_SPACE with *out_len = the bytes needed and no byte of d_out written.  Bytes of
+ *   d_out at and behind *out_len are never written.  n_ranges == 0 is OK with 0 bytes.  The result is the same bit for
+ *   bit from run to run: no atomics place it.
+ * gzpx_read_fields_device takes line_ranges and out_offsets as HOST arrays, gzpx_read_fields_table_device as DEVICE
+ *   arrays (d_line_ranges is read where it lies, ordered behind hip_stream like d_in).  In the table form only
+ *   fixed-size records cross to the host: no table sized by n_ranges or by the output does.
+ * gzpx_dctx_last_fields_ms: HIP-event durations of the last call's three stages behind the search: [0] the field-carry
+ *   pass and its scan, [1] the counting pass and its scan, [2] the writing pass (0 when it did not run).  The search's
+ *   stages stay readable through gzpx_dctx_last_lines_ms, whose [3], the gather, is 0 for these calls;
+ *   gzpx_dctx_last_lines_members answers as for a read by line. */
+#define GZPX_FIELDS_MAX_RANGES 64
+#define GZPX_FIELDS_COMPLEMENT 1u     /* cut --complement: every field NOT listed */
+#define GZPX_FIELDS_TO_END UINT64_MAX /* as a range's `end`: through the line's last field */
+int gzpx_read_fields_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in, size_t in_len,
+                            const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_range *fields,
+                            size_t n_fields, unsigned flags, void *d_out, size_t out_cap, size_t *out_len, uint64_t *out_offsets,
+                            size_t *bad_range, gzpx_check_info *info, void *hip_stream);
+int gzpx_read_fields_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in,
+                                  size_t in_len, const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim,
+                                  const gzpx_range *fields, size_t n_fields, unsigned flags, void *d_out, size_t out_cap,
+                                  size_t *out_len, uint64_t *d_out_offsets, size_t *bad_range, gzpx_check_info *info,
+                                  void *hip_stream);
+int gzpx_dctx_last_fields_ms(gzpx_dctx *ctx, float ms[3]);
 /* ---- search for a SET of byte strings (gzpx_findset.h): grep -F -e A -e B -f list on a device-resident BGZF / Mgzip
  * stream -- the VCF rows of a handful of contigs, the FASTQ records that carry any of 96 barcodes, the log lines with
  * any of a list of error codes -- in ONE inflate and one pass over it, the hits of all patterns already merged by

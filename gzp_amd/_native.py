@@ -56,6 +56,11 @@ FINDSET_MAX_BYTES = 16384   # GZPX_FINDSET_MAX_BYTES: the sum of a set's pattern
 FIELDS_MAX_RANGES = 64           # GZPX_FIELDS_MAX_RANGES
 FIELDS_COMPLEMENT = 1            # GZPX_FIELDS_COMPLEMENT
 FIELDS_TO_END = (1 << 64) - 1    # GZPX_FIELDS_TO_END: as a field range's end, through the line's last field
+COLUMNS_MAX = 16                 # GZPX_COLUMNS_MAX
+CELL_MAX_BYTES = 64              # GZPX_CELL_MAX_BYTES
+COL_INT64, COL_FLOAT64 = 0, 1    # GZPX_COL_*
+CELL_OK, CELL_MISSING, CELL_EMPTY, CELL_INVALID, CELL_RANGE = range(5)  # GZPX_CELL_*
+COLUMN_DTYPE = [("field", "<u8"), ("type", "<u4"), ("reserved", "<u4")]  # gzpx_column, as a numpy record
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -89,6 +94,7 @@ EXPORTS = [
     "gzpx_select_lines_device", "gzpx_dctx_last_select_ms", "gzpx_read_lines_table_device",
     "gzpx_find_set_device", "gzpx_dctx_last_find_set_ms", "gzpx_select_lines_set_device",
     "gzpx_read_fields_device", "gzpx_read_fields_table_device", "gzpx_dctx_last_fields_ms",
+    "gzpx_read_columns_device", "gzpx_read_columns_table_device", "gzpx_dctx_last_columns_ms",
 ]
 
 
@@ -318,6 +324,12 @@ class GzpxLib:
                            ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_dctx_last_fields_ms.restype = i32
         L.gzpx_dctx_last_fields_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        for fn in (L.gzpx_read_columns_device, L.gzpx_read_columns_table_device):
+            fn.restype = i32
+            fn.argtypes = [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint, vp, sz, vp, vp, sz, pu64, pu64, vp, vp, psz,
+                           ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_columns_ms.restype = i32
+        L.gzpx_dctx_last_columns_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_inflate_batch_device.restype = i32
         L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
                                                 ctypes.POINTER(GzpxCheckInfo), vp]
@@ -1217,6 +1229,58 @@ class DContext:
         ms = (ctypes.c_float * 3)()
         self.lib.check(self.lib.L.gzpx_dctx_last_fields_ms(self.h, ms))
         return ms[0], ms[1], ms[2]
+
+    # ---- numeric columns of lines (gzpx_columns.h)
+    def _read_columns(self, fn, index, lines, d_in_ptr, in_len, ranges_ptr, n_ranges, field_delim, cols, d_values_ptr, d_status_ptr,
+                      rows_cap, d_col_not_ok_ptr, offsets_ptr, stream):
+        cl = np.zeros(len(cols), dtype=COLUMN_DTYPE)
+        for i, (field, kind) in enumerate(cols):
+            cl[i] = (field, kind, 0)
+        n_rows, n_not_ok, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_size_t(0)
+        info = GzpxCheckInfo()
+        rc = fn(self.h, index.h, lines.h, d_in_ptr, in_len, ranges_ptr, n_ranges, int(field_delim), cl.ctypes.data, cl.shape[0],
+                d_values_ptr, d_status_ptr, rows_cap, ctypes.byref(n_rows), ctypes.byref(n_not_ok), d_col_not_ok_ptr, offsets_ptr,
+                ctypes.byref(bad), ctypes.byref(info), stream)
+        if rc == OK:
+            return n_rows.value, n_not_ok.value
+        if bad.value != ctypes.c_size_t(-1).value:
+            raise GzpxError(rc, "line range %d does not lie in the stream" % bad.value, range_index=bad.value)
+        if rc == ERR_INSUFFICIENT_SPACE and n_rows.value:
+            raise GzpxError(rc, "the line ranges hold %d rows" % n_rows.value, needed=n_rows.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def read_columns_device(self, index, lines, d_in_ptr, in_len, line_ranges, field_delim, cols, d_values_ptr, d_status_ptr,
+                            rows_cap, d_col_not_ok_ptr=None, stream=None):
+        """Numbers of the lines of line_ranges[n, 2]: `cols` is a sequence of (field number, COL_INT64 | COL_FLOAT64), the
+        field numbers strictly ascending, COLUMNS_MAX at most.  Line i of range r is row row_offsets[r] + i; column c, row i is
+        the 8-byte cell d_values[c * rows_cap + i] (int64 / float64) with its CELL_* byte at d_status[c * rows_cap + i].
+        Either pointer may be None; with both None the call only counts.  d_col_not_ok_ptr: an optional device array
+        uint64[len(cols)].  Returns (n_rows, n_not_ok, row_offsets uint64[n + 1]).  A bad line range raises GzpxError with
+        .range_index; more rows than rows_cap raises it with .needed."""
+        r = np.ascontiguousarray(np.asarray(line_ranges, dtype=np.uint64).reshape(-1, 2))
+        offs = np.zeros(r.shape[0] + 1, dtype=np.uint64)
+        n_rows, n_not_ok = self._read_columns(self.lib.L.gzpx_read_columns_device, index, lines, d_in_ptr, in_len, r.ctypes.data,
+                                              r.shape[0], field_delim, cols, d_values_ptr, d_status_ptr, rows_cap, d_col_not_ok_ptr,
+                                              offs.ctypes.data, stream)
+        return n_rows, n_not_ok, offs
+
+    def read_columns_table_device(self, index, lines, d_in_ptr, in_len, d_line_ranges_ptr, n_ranges, field_delim, cols, d_values_ptr,
+                                  d_status_ptr, rows_cap, d_col_not_ok_ptr=None, d_row_offsets_ptr=None, stream=None):
+        """read_columns_device with its tables in device memory: d_line_ranges_ptr is uint64[n_ranges, 2] (the table
+        select_lines_device wrote, for one), the optional d_row_offsets_ptr uint64[n_ranges + 1].  Returns (n_rows, n_not_ok,
+        d_row_offsets_ptr): the third is the device array that was given."""
+        n_rows, n_not_ok = self._read_columns(self.lib.L.gzpx_read_columns_table_device, index, lines, d_in_ptr, in_len,
+                                              d_line_ranges_ptr, n_ranges, field_delim, cols, d_values_ptr, d_status_ptr, rows_cap,
+                                              d_col_not_ok_ptr, d_row_offsets_ptr, stream)
+        return n_rows, n_not_ok, d_row_offsets_ptr
+
+    def last_columns_ms(self):
+        """HIP-event durations of the last read_columns call's stages behind the search: (carries + row scan, parse)."""
+        ms = (ctypes.c_float * 2)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_columns_ms(self.h, ms))
+        return ms[0], ms[1]
 
     # ---- batches of raw / zlib / gzip members that lie in device memory (gzpx_wrap.h)
     def inflate_batch_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr,

@@ -1640,6 +1640,45 @@ struct FieldsState : NoCopy {
     }
 };
 
+// numeric columns of lines (gzpx_read_columns_device and its table form): the line search's state in front, the pieces
+// and carries of the fields' first pass in its own scratch, then the rows and the parse
+struct ColumnsState : NoCopy {
+    Event ev[3];        // carries + row scan [0..1], the parse [1..2]
+    bool have = false;  // ev holds the last call's stages
+    ColumnsScratch cl;
+    ClCols *h_cols = nullptr;   // pinned: the column list on its way in
+    uint64_t *h_rec = nullptr;  // pinned: the record on its way out
+    Allocs once;                // cl.cols, cl.rec, cl.fl.rec and the two pinned arrays above
+    size_t range_cap = 0, host_cap = 0, piece_cap = 0;
+    uint64_t *h_row_off = nullptr;  // pinned: row_offsets on their way out
+    Allocs ranges;  // cl.fl.pfirst, cl.row_off
+    Allocs host;    // h_row_off: a call whose tables lie in device memory needs none
+    Allocs pieces;  // cl.fl.carry, cl.fl.cin, cl.rcnt, cl.rin
+    int reserve(size_t n_ranges, size_t n_pieces, bool host_tables) {
+        if (!cl.rec) {
+            once.release();  // (an earlier attempt that failed half way)
+            GZPX_TRY(once.dev(cl.cols, sizeof(ClCols)));
+            GZPX_TRY(once.dev(cl.fl.rec, kFlRecWords * 8));
+            GZPX_TRY(once.pinned(h_cols, sizeof(ClCols)));
+            GZPX_TRY(once.pinned(h_rec, kClRecWords * 8));
+            for (Event &e : ev) GZPX_TRY(e.create(true));
+            GZPX_TRY(once.dev(cl.rec, kClRecWords * 8));
+        }
+        GZPX_TRY(grow(ranges, range_cap, n_ranges, n_ranges + n_ranges / 4 + 64, [&](size_t cap) -> int {
+            GZPX_TRY(ranges.dev(cl.fl.pfirst, (cap + 1) * 8));
+            return ranges.dev(cl.row_off, (cap + 1) * 8);
+        }));
+        GZPX_TRY(grow(host, host_cap, host_tables ? n_ranges : 0, n_ranges + n_ranges / 4 + 64,
+                      [&](size_t cap) { return host.pinned(h_row_off, (cap + 1) * 8); }));
+        return grow(pieces, piece_cap, n_pieces + 1, n_pieces + n_pieces / 8 + 16, [&](size_t cap) -> int {
+            GZPX_TRY(pieces.dev(cl.fl.carry, cap * 4));
+            GZPX_TRY(pieces.dev(cl.fl.cin, cap * 8));
+            GZPX_TRY(pieces.dev(cl.rcnt, cap * 4));
+            return pieces.dev(cl.rin, cap * 8);
+        });
+    }
+};
+
 }  // namespace
 
 // (members are destroyed last to first: memory and events of the slots and of each kind of call, then the streams)
@@ -1664,6 +1703,7 @@ struct gzpx_dctx : NoCopy {
     SelectState select;
     FindSetState find_set;
     FieldsState fields;
+    ColumnsState columns;
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -2970,6 +3010,132 @@ int gzpx_dctx_last_fields_ms(gzpx_dctx *ctx, float ms[3]) {
     if (hipEventElapsedTime(&ms[0], f.ev[0], f.ev[1]) != hipSuccess || hipEventElapsedTime(&ms[1], f.ev[1], f.ev[2]) != hipSuccess)
         return GZPX_ERR_DEVICE;
     if (f.wrote && hipEventElapsedTime(&ms[2], f.ev[2], f.ev[3]) != hipSuccess) return GZPX_ERR_DEVICE;
+    return GZPX_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- numeric columns of lines (gzpx_columns.h)
+namespace {
+
+// the column list as the kernels take it; false: it breaks a rule of gzpx.h
+bool columns_compile(const gzpx_column *cols, size_t n_cols, ClCols &s) {
+    static_assert(kClMaxCols == GZPX_COLUMNS_MAX && kClMaxBytes == GZPX_CELL_MAX_BYTES, "the public constants state the kernels' limits");
+    if (!cols || n_cols == 0 || n_cols > kClMaxCols) return false;
+    for (size_t i = 0; i < kClMaxCols; i++) {
+        s.field[i] = UINT64_MAX;
+        s.type[i] = 0;
+    }
+    for (size_t i = 0; i < n_cols; i++) {
+        if ((i && cols[i - 1].field >= cols[i].field) || cols[i].reserved) return false;
+        if (cols[i].type != GZPX_COL_INT64 && cols[i].type != GZPX_COL_FLOAT64) return false;
+        s.field[i] = cols[i].field;
+        s.type[i] = cols[i].type;
+    }
+    s.n = (uint32_t)n_cols;
+    s.pad = 0;
+    return true;
+}
+
+// gzpx_read_columns_device, and with `on_device` gzpx_read_columns_table_device: line_ranges and row_offsets are then
+// device arrays.  The line search of read_lines, then the carries of gzpx_fields.h, the rows and the parse of
+// gzpx_columns.h, enqueued together: whether the rows fit is decided on the device, and one record comes back.
+int read_columns(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                 const gzpx_range *line_ranges, bool on_device, size_t n_ranges, unsigned field_delim, const gzpx_column *cols,
+                 size_t n_cols, void *d_values, uint8_t *d_status, size_t rows_cap, uint64_t *n_rows, uint64_t *n_not_ok,
+                 uint64_t *d_col_not_ok, uint64_t *row_offsets, size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
+    if (!c || !ix || !lt || !n_rows || (!line_ranges && n_ranges) || (!d_in && in_len)) return GZPX_ERR_INVALID_ARG;
+    *n_rows = 0;
+    if (n_not_ok) *n_not_ok = 0;
+    if (bad_range) *bad_range = (size_t)-1;
+    std::unique_lock<std::mutex> lk(c->mu);
+    ColumnsState &f = c->columns;
+    c->lines.stages = 0;
+    c->lines.last_members = 0;
+    f.have = false;
+    if (!lines_match(c, ix, lt, in_len) || n_ranges > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    if (field_delim > 255u || field_delim == lt->delim || ((uintptr_t)d_values & 7u)) return GZPX_ERR_INVALID_ARG;
+    ClCols list;
+    if (!columns_compile(cols, n_cols, list)) return GZPX_ERR_INVALID_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    if (n_ranges == 0) {
+        if (row_offsets && !on_device) row_offsets[0] = 0;
+        if ((row_offsets && on_device) || d_col_not_ok) {  // (device arrays: behind the caller's stream, as every other call)
+            hipStream_t stream = c->stream;
+            GZPX_TRY(order_behind(stream, (hipStream_t)hip_stream, c->ev_dep));
+            Drain drain{{stream}, 1};
+            if (row_offsets && on_device) HIP_TRY(hipMemsetAsync(row_offsets, 0, 8, stream));
+            if (d_col_not_ok) HIP_TRY(hipMemsetAsync(d_col_not_ok, 0, n_cols * 8, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            drain.armed = false;
+        }
+        return GZPX_OK;
+    }
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    uint64_t bytes = 0;  // of the ranges, in staging
+    GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, (const uint64_t *)line_ranges, n_ranges, 2u, bad_range, info,
+                          (hipStream_t)hip_stream, &bytes, on_device));
+    const uint64_t grid = fields_pieces(bytes, n_ranges);
+    if (grid > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;  // (the passes' grid)
+    GZPX_TRY(f.reserve(n_ranges, (size_t)grid, !on_device));
+    hipStream_t stream = c->stream;
+    Drain drain{{stream}, 1};
+    const RangeScratch &rr = c->ranges.rr;
+    uint64_t *d_off = on_device && row_offsets ? row_offsets : f.cl.row_off;
+    const bool stores = d_values || d_status;
+    *f.h_cols = list;
+    HIP_TRY(hipMemcpyAsync(f.cl.cols, f.h_cols, sizeof(ClCols), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(f.ev[0], stream));
+    launch_fields_carry(c->stage.d, (uint32_t)n_ranges, rr, f.cl.fl, lt->delim, field_delim, (uint32_t)grid, stream);
+    launch_columns_rows(c->stage.d, (uint32_t)n_ranges, rr, c->lines.ln, f.cl, lt->delim, field_delim, (uint32_t)grid, d_off, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f.ev[1], stream));
+    launch_columns_parse(c->stage.d, (uint32_t)n_ranges, rr, f.cl, lt->delim, field_delim, (uint32_t)grid, d_off, (uint64_t *)d_values,
+                         d_status, stores ? rows_cap : 0, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f.ev[2], stream));
+    HIP_TRY(hipMemcpyAsync(f.h_rec, f.cl.rec, kClRecWords * 8, hipMemcpyDeviceToHost, stream));
+    if (d_col_not_ok) HIP_TRY(hipMemcpyAsync(d_col_not_ok, f.cl.rec + kClRecCol, n_cols * 8, hipMemcpyDeviceToDevice, stream));
+    if (row_offsets && !on_device) HIP_TRY(hipMemcpyAsync(f.h_row_off, d_off, (n_ranges + 1) * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    f.have = true;
+    *n_rows = f.h_rec[kClRecRows];
+    if (n_not_ok) *n_not_ok = f.h_rec[kClRecNotOk];
+    if (row_offsets && !on_device) memcpy(row_offsets, f.h_row_off, (n_ranges + 1) * 8);
+    return stores && f.h_rec[kClRecRows] > rows_cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gzpx_read_columns_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                             const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_column *cols,
+                             size_t n_cols, void *d_values, uint8_t *d_status, size_t rows_cap, uint64_t *n_rows, uint64_t *n_not_ok,
+                             uint64_t *d_col_not_ok, uint64_t *row_offsets, size_t *bad_range, gzpx_check_info *info,
+                             void *hip_stream) {
+    return read_columns(c, ix, lt, d_in, in_len, line_ranges, false, n_ranges, field_delim, cols, n_cols, d_values, d_status, rows_cap,
+                        n_rows, n_not_ok, d_col_not_ok, row_offsets, bad_range, info, hip_stream);
+}
+
+int gzpx_read_columns_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                                   const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_column *cols,
+                                   size_t n_cols, void *d_values, uint8_t *d_status, size_t rows_cap, uint64_t *n_rows,
+                                   uint64_t *n_not_ok, uint64_t *d_col_not_ok, uint64_t *d_row_offsets, size_t *bad_range,
+                                   gzpx_check_info *info, void *hip_stream) {
+    return read_columns(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, field_delim, cols, n_cols, d_values, d_status,
+                        rows_cap, n_rows, n_not_ok, d_col_not_ok, d_row_offsets, bad_range, info, hip_stream);
+}
+
+int gzpx_dctx_last_columns_ms(gzpx_dctx *ctx, float ms[2]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ms[0] = ms[1] = 0.0f;
+    const ColumnsState &f = ctx->columns;
+    if (!f.have) return GZPX_OK;
+    if (hipEventElapsedTime(&ms[0], f.ev[0], f.ev[1]) != hipSuccess || hipEventElapsedTime(&ms[1], f.ev[1], f.ev[2]) != hipSuccess)
+        return GZPX_ERR_DEVICE;
     return GZPX_OK;
 }
 

@@ -456,6 +456,37 @@ void launch_fields_count(const uint8_t *d_stage, uint32_t n_ranges, const RangeS
 void launch_fields_write(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const FieldsScratch &f, uint32_t delim,
                          uint32_t field_delim, uint32_t grid, uint8_t *d_out, uint64_t out_cap, hipStream_t stream);
 
+// Numeric columns of lines (gzpx_columns.h): behind the same line search, the pieces and cin of launch_fields_carry,
+// then a row number per piece and one parsing pass that stores a cell and a status byte per (column, row).
+constexpr uint32_t kClMaxCols = 16;    // GZPX_COLUMNS_MAX
+constexpr uint32_t kClMaxBytes = 64;   // GZPX_CELL_MAX_BYTES
+constexpr uint32_t kClOverhang = 80;   // bytes behind a piece that k_cl_parse stages: a field opened by the piece's last byte
+struct ClCols {
+    uint64_t field[kClMaxCols];  // ascending; UINT64_MAX behind the n in use
+    uint32_t type[kClMaxCols];   // GZPX_COL_*
+    uint32_t n, pad;
+};
+// the record (u64 words): rows, cells that are not OK, then the same count per column
+enum { kClRecRows = 0, kClRecNotOk = 1, kClRecCol = 2, kClRecWords = 2 + kClMaxCols };
+struct ColumnsScratch {
+    FieldsScratch fl;             // pfirst, carry, cin and k_fl_plan's record; the rest of it stays null
+    ClCols *cols = nullptr;       // the column list
+    uint32_t *rcnt = nullptr;     // [pieces] the line delimiters of a piece
+    uint64_t *rin = nullptr;      // [pieces] the lines of its range in front of a piece's first byte
+    uint64_t *row_off = nullptr;  // [ranges + 1] rbase (a caller's device array takes its place)
+    uint64_t *rec = nullptr;      // [kClRecWords]
+};
+// behind launch_fields_carry on c.fl: c.rcnt, c.rin, d_row_off[n_ranges + 1] and the record's rows; the record is cleared
+// first.  l.bounds holds the (begin, end) line numbers of the ranges.
+void launch_columns_rows(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const LinesScratch &l,
+                         const ColumnsScratch &c, uint32_t delim, uint32_t field_delim, uint32_t grid, uint64_t *d_row_off,
+                         hipStream_t stream);
+// behind it: the cells to d_values / d_status (either may be null), unless one is given and the rows exceed rows_cap; the
+// counts of cells that are not OK into the record
+void launch_columns_parse(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const ColumnsScratch &c, uint32_t delim,
+                          uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t *d_values, uint8_t *d_status,
+                          uint64_t rows_cap, hipStream_t stream);
+
 // Search for a set of patterns (gzpx_findset.h).  The host compiles the set into an FsSet, the form the kernels stage
 // into LDS: q = min(shortest pattern, 4); the WINDOW of a pattern is its first q bytes as a little-endian number.
 constexpr uint32_t kFsMaxPatterns = 256;  // GZPX_FINDSET_MAX_PATTERNS

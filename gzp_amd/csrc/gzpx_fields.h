@@ -117,10 +117,12 @@ __device__ __forceinline__ uint64_t fl_scan64(uint64_t v, uint64_t *wsum, uint64
 // the pieces of a range of len > 0 bytes at s of staging
 __device__ __forceinline__ uint64_t fl_pieces(uint64_t s, uint64_t len) { return (s + len - 1u) / kFlPiece - s / kFlPiece + 1u; }
 
-// Piece x: its bytes [a0, a1) of staging and whether it is its range's first.  False: there is no such piece.
-__device__ __forceinline__ bool fl_piece(const FlArgs &a, uint64_t x, uintptr_t &a0, uintptr_t &a1, bool &head) {
+// Piece x: its bytes [a0, a1) of staging, whether it is its range's first, the range and where that ends in staging.
+// False: there is no such piece.
+__device__ __forceinline__ bool fl_piece(const FlArgs &a, uint64_t x, uintptr_t &a0, uintptr_t &a1, bool &head, uint32_t &r,
+                                         uintptr_t &end) {
     if (x >= a.pfirst[a.n]) return false;  // (the whole workgroup)
-    const uint32_t r = rr_bound<true>(a.pfirst + 1, 0, a.n, x);  // the range with pfirst[r] <= x < pfirst[r + 1]
+    r = rr_bound<true>(a.pfirst + 1, 0, a.n, x);  // the range with pfirst[r] <= x < pfirst[r + 1]
     const uint64_t j = x - a.pfirst[r];
     const uint64_t s = a.src[r], e = s + (a.in_off[r + 1u] - a.in_off[r]);
     const uint64_t cell = s / kFlPiece + j;
@@ -128,8 +130,14 @@ __device__ __forceinline__ bool fl_piece(const FlArgs &a, uint64_t x, uintptr_t 
     const uint64_t b1 = (cell + 1u) * kFlPiece < e ? (cell + 1u) * kFlPiece : e;  // (b0 < b1: the range touches the cell)
     a0 = (uintptr_t)a.stage + b0;
     a1 = (uintptr_t)a.stage + b1;
+    end = (uintptr_t)a.stage + e;
     head = j == 0;
     return true;
+}
+__device__ __forceinline__ bool fl_piece(const FlArgs &a, uint64_t x, uintptr_t &a0, uintptr_t &a1, bool &head) {
+    uint32_t r;
+    uintptr_t end;
+    return fl_piece(a, x, a0, a1, head, r, end);
 }
 
 // The rows of piece [a0, a1) for this lane: the aligned words (zero where the lane has none), the masks of the two

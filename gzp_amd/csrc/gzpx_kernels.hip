@@ -5416,6 +5416,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_find.h"
 #include "gzpx_select.h"
 #include "gzpx_fields.h"
+#include "gzpx_columns.h"
 #include "gzpx_findset.h"
 #include "gzpx_wrap.h"
 #include "gzpx_cksum.h"
@@ -5985,6 +5986,27 @@ void launch_fields_write(const uint8_t *d_stage, uint32_t n_ranges, const RangeS
         hipLaunchKernelGGL(k_fl_write, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, f, delim, field_delim),
                            (const FlSet *)f.set, (const uint64_t *)f.cin, (const uint32_t *)f.cnt, (const uint64_t *)f.obase,
                            (const uint64_t *)f.rec, d_out, out_cap);
+}
+
+// Numeric columns of lines (gzpx_columns.h), behind launch_fields_carry on c.fl: the rows, then the one parsing pass.
+void launch_columns_rows(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const LinesScratch &l,
+                         const ColumnsScratch &c, uint32_t delim, uint32_t field_delim, uint32_t grid, uint64_t *d_row_off,
+                         hipStream_t stream) {
+    (void)hipMemsetAsync(c.rec, 0, kClRecWords * 8, stream);
+    if (grid)
+        hipLaunchKernelGGL(k_cl_rows, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, c.fl, delim, field_delim),
+                           c.rcnt);
+    hipLaunchKernelGGL(k_cl_rows_scan, dim3(1), dim3(kFlThreads), 0, stream, (const uint64_t *)l.bounds, (const uint32_t *)c.fl.carry,
+                       (const uint32_t *)c.rcnt, (const uint64_t *)c.fl.pfirst, n_ranges, c.rin, d_row_off, c.rec);
+}
+
+void launch_columns_parse(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const ColumnsScratch &c, uint32_t delim,
+                          uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t *d_values, uint8_t *d_status,
+                          uint64_t rows_cap, hipStream_t stream) {
+    if (grid)
+        hipLaunchKernelGGL(k_cl_parse, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, c.fl, delim, field_delim),
+                           (const ClCols *)c.cols, (const uint64_t *)c.fl.cin, (const uint64_t *)c.rin, d_row_off, c.rec, d_values,
+                           d_status, rows_cap);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

@@ -569,6 +569,71 @@ int gzpx_read_fields_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const g
                                   size_t *out_len, uint64_t *d_out_offsets, size_t *bad_range, gzpx_check_info *info,
                                   void *hip_stream);
 int gzpx_dctx_last_fields_ms(gzpx_dctx *ctx, float ms[3]);
+/* ---- numeric columns of lines (gzpx_columns.h): the last step of grep ... | cut -f ... | <numbers> -- POS and QUAL
+ * of a VCF, a column of measurements of a TSV -- one value per line and column as int64 / float64 arrays in device
+ * memory, with a status byte per value.  gzpx_read_fields_device and everything in front of it are untouched.
+ * Lines, delimiters, fields.  `plain`, `delim`, line ranges, covers and members read, validation and *bad_range, the
+ *   context's lock, the slot, hip_stream, "returns synchronised", both inflate routes and the report of a failing member
+ *   are gzpx_read_fields_device's, word for word.  So are field_delim (one byte, not the lines table's delimiter) and
+ *   the split of a line's body at every field_delim into F fields numbered from 0.  '\r' is an ordinary byte.
+ * Columns.  `cols` is a HOST array of 1..GZPX_COLUMNS_MAX entries: field numbers strictly ascending, `type` one of
+ *   GZPX_COL_INT64 and GZPX_COL_FLOAT64, `reserved` 0.  Anything else: GZPX_ERR_INVALID_ARG with nothing inflated.
+ * Rows.  Line i of range r is row rbase[r] + i, rbase the exclusive sum of (end - begin) over the ranges as given:
+ *   overlapping and repeated ranges repeat their rows, empty ranges add none.  R is the total.  *n_rows = R always.
+ *   row_offsets[r] = rbase[r], row_offsets[n_ranges] = R (optional; n_ranges + 1 entries; written whenever the call
+ *   returns GZPX_OK or GZPX_ERR_INSUFFICIENT_SPACE).
+ * Cells.  Column c, row i is the 8-byte cell d_values[c * rows_cap + i] (int64_t or double by the column's type) with
+ *   its status byte at d_status[c * rows_cap + i].  d_values must be 8-byte aligned.  Either array may be NULL; with
+ *   both NULL the call still counts and rows_cap is ignored.  With an array given and R > rows_cap:
+ *   GZPX_ERR_INSUFFICIENT_SPACE, *n_rows = R, no byte of either array is written and the counts are 0.  Otherwise every
+ *   cell with i < R is written exactly once and no cell with i >= R is touched in any column.  *n_not_ok is the number of
+ *   cells whose status is not GZPX_CELL_OK; d_col_not_ok, an optional DEVICE array of n_cols entries, holds the same
+ *   count per column.  A cell that is not OK holds 0 (INT64) or the quiet NaN 0x7FF8000000000000 (FLOAT64).
+ * Status of the cell for field number f; the first rule that applies decides.  f >= F: MISSING.  A field of 0 bytes:
+ *   EMPTY.  More than GZPX_CELL_MAX_BYTES bytes: INVALID, and its bytes are not looked at.  Not matched in full by the
+ *   type's grammar: INVALID.  Otherwise RANGE or OK:
+ *   INT64    [+-]?[0-9]+ ; OK iff the value lies in [-2^63, 2^63 - 1] (leading zeros do not count against it).
+ *   FLOAT64  [+-]?([0-9]+(\.[0-9]*)?|\.[0-9]+)([eE][+-]?[0-9]+)? or, case-insensitively, [+-]?(nan|inf|infinity).
+ *            nan gives the quiet NaN above whatever its sign, inf the signed infinity.  A decimal number: join the
+ *            integer and fraction digits and strip leading and trailing zeros; w = the value of what is left (0 if
+ *            nothing is); q = exponent - (fraction digits) + (trailing zeros stripped).  w == 0: the signed zero, OK.
+ *            w <= 2^53 and -22 <= q <= 22: OK, and the value is the ONE IEEE operation double(w) * 10^q or
+ *            double(w) / 10^-q on two exact operands, negated for '-': the correctly rounded value (Clinger).
+ *            Everything else is RANGE, an exponent of any number of digits included.  Plainly: numbers of up to 15
+ *            significant digits with small exponents convert; the 16- and 17-digit output of repr() is mostly RANGE.
+ *            A later version may convert RANGE cells in full; the status code keeps the ABI stable for it.
+ * The result is the same bit for bit from run to run: scans place every cell, and the two counts are integer sums.
+ * gzpx_read_columns_device takes line_ranges and row_offsets as HOST arrays, gzpx_read_columns_table_device as DEVICE
+ *   arrays (d_line_ranges is read where it lies, ordered behind hip_stream like d_in).  In the table form only
+ *   fixed-size records cross to the host.  n_ranges == 0 is OK with 0 rows.
+ * gzpx_dctx_last_columns_ms: HIP-event durations of the last call's stages behind the search: [0] the field carries,
+ *   the pieces' line counts and their scans, [1] the parsing pass.  gzpx_dctx_last_lines_ms and
+ *   gzpx_dctx_last_lines_members answer as for gzpx_read_fields_device. */
+#define GZPX_COLUMNS_MAX 16
+#define GZPX_CELL_MAX_BYTES 64
+#define GZPX_COL_INT64 0
+#define GZPX_COL_FLOAT64 1
+#define GZPX_CELL_OK 0      /* the value is the field's number */
+#define GZPX_CELL_MISSING 1 /* the line has no field of that number */
+#define GZPX_CELL_EMPTY 2   /* the field has no bytes */
+#define GZPX_CELL_INVALID 3 /* longer than GZPX_CELL_MAX_BYTES, or not in the grammar */
+#define GZPX_CELL_RANGE 4   /* in the grammar, outside what this call converts exactly */
+typedef struct gzpx_column {
+    uint64_t field;
+    uint32_t type;
+    uint32_t reserved;
+} gzpx_column;
+int gzpx_read_columns_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in, size_t in_len,
+                             const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_column *cols,
+                             size_t n_cols, void *d_values, uint8_t *d_status, size_t rows_cap, uint64_t *n_rows,
+                             uint64_t *n_not_ok, uint64_t *d_col_not_ok, uint64_t *row_offsets, size_t *bad_range,
+                             gzpx_check_info *info, void *hip_stream);
+int gzpx_read_columns_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in,
+                                   size_t in_len, const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim,
+                                   const gzpx_column *cols, size_t n_cols, void *d_values, uint8_t *d_status, size_t rows_cap,
+                                   uint64_t *n_rows, uint64_t *n_not_ok, uint64_t *d_col_not_ok, uint64_t *d_row_offsets,
+                                   size_t *bad_range, gzpx_check_info *info, void *hip_stream);
+int gzpx_dctx_last_columns_ms(gzpx_dctx *ctx, float ms[2]);
 /* ---- search for a SET of byte strings (gzpx_findset.h): grep -F -e A -e B -f list on a device-resident BGZF / Mgzip
  * stream -- the VCF rows of a handful of contigs, the FASTQ records that carry any of 96 barcodes, the log lines with
  * any of a list of error codes -- in ONE inflate and one pass over it, the hits of all patterns already merged by

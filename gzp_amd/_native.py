@@ -5,6 +5,7 @@ creation raises -- the product path never routes through a CPU implementation.
 """
 import ctypes
 import os
+import struct
 
 import numpy as np
 
@@ -61,6 +62,10 @@ CELL_MAX_BYTES = 64              # GZPX_CELL_MAX_BYTES
 COL_INT64, COL_FLOAT64 = 0, 1    # GZPX_COL_*
 CELL_OK, CELL_MISSING, CELL_EMPTY, CELL_INVALID, CELL_RANGE = range(5)  # GZPX_CELL_*
 COLUMN_DTYPE = [("field", "<u8"), ("type", "<u4"), ("reserved", "<u4")]  # gzpx_column, as a numpy record
+WHERE_MAX_TERMS = 32             # GZPX_WHERE_MAX_TERMS
+WHERE_LT, WHERE_LE, WHERE_EQ, WHERE_NE, WHERE_GE, WHERE_GT, WHERE_IS_OK, WHERE_NOT_OK = range(8)  # GZPX_WHERE_*: a term's op
+WHERE_ANY, WHERE_INVERT = 1, 2   # GZPX_WHERE_ANY, GZPX_WHERE_INVERT: flags
+WHERE_TERM_DTYPE = [("field", "<u8"), ("type", "<u4"), ("op", "<u4"), ("value", "<u8")]  # gzpx_where_term, as a numpy record
 
 EXPORTS = [
     "gzpx_config_default", "gzpx_ctx_create", "gzpx_ctx_destroy", "gzpx_slab_bound",
@@ -95,6 +100,7 @@ EXPORTS = [
     "gzpx_find_set_device", "gzpx_dctx_last_find_set_ms", "gzpx_select_lines_set_device",
     "gzpx_read_fields_device", "gzpx_read_fields_table_device", "gzpx_dctx_last_fields_ms",
     "gzpx_read_columns_device", "gzpx_read_columns_table_device", "gzpx_dctx_last_columns_ms",
+    "gzpx_where_lines_device", "gzpx_where_lines_table_device", "gzpx_dctx_last_where_ms",
 ]
 
 
@@ -330,6 +336,12 @@ class GzpxLib:
                            ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_dctx_last_columns_ms.restype = i32
         L.gzpx_dctx_last_columns_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        for fn in (L.gzpx_where_lines_device, L.gzpx_where_lines_table_device):
+            fn.restype = i32
+            fn.argtypes = [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint, vp, sz, ctypes.c_uint, vp, sz, pu64, pu64, pu64, pu64, psz,
+                           ctypes.POINTER(GzpxCheckInfo), vp]
+        L.gzpx_dctx_last_where_ms.restype = i32
+        L.gzpx_dctx_last_where_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_inflate_batch_device.restype = i32
         L.gzpx_inflate_batch_device.argtypes = [vp, i32, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, psz, psz,
                                                 ctypes.POINTER(GzpxCheckInfo), vp]
@@ -1281,6 +1293,62 @@ class DContext:
         ms = (ctypes.c_float * 2)()
         self.lib.check(self.lib.L.gzpx_dctx_last_columns_ms(self.h, ms))
         return ms[0], ms[1]
+
+    # ---- selection of lines by their numbers (gzpx_where.h)
+    @staticmethod
+    def where_terms(terms):
+        """`terms` as gzpx_where_term records: (field, COL_*, WHERE_*, value), the value a Python int or float packed by the type."""
+        tm = np.zeros(len(terms), dtype=WHERE_TERM_DTYPE)
+        for i, (field, kind, op, value) in enumerate(terms):
+            bits = struct.unpack("<Q", struct.pack("<d", float(value)) if kind == COL_FLOAT64 else struct.pack("<q", int(value)))[0]
+            tm[i] = (field, kind, op, bits)
+        return tm
+
+    def _where_lines(self, fn, index, lines, d_in_ptr, in_len, ranges_ptr, n_ranges, field_delim, terms, any, invert, d_runs_ptr,
+                     runs_cap, stream):
+        tm = self.where_terms(terms)
+        runs, selected, rows, not_ok, bad = (ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0),
+                                             ctypes.c_size_t(0))
+        info = GzpxCheckInfo()
+        rc = fn(self.h, index.h, lines.h, d_in_ptr, in_len, ranges_ptr, n_ranges, int(field_delim), tm.ctypes.data, tm.shape[0],
+                (WHERE_ANY if any else 0) | (WHERE_INVERT if invert else 0), d_runs_ptr, runs_cap, ctypes.byref(runs),
+                ctypes.byref(selected), ctypes.byref(rows), ctypes.byref(not_ok), ctypes.byref(bad), ctypes.byref(info), stream)
+        if rc == OK:
+            return runs.value, selected.value, rows.value, not_ok.value
+        if bad.value != ctypes.c_size_t(-1).value:
+            raise GzpxError(rc, "line range %d does not lie in the stream" % bad.value, range_index=bad.value)
+        if rc == ERR_INSUFFICIENT_SPACE and runs.value:
+            raise GzpxError(rc, "the selection has %d runs" % runs.value, needed=runs.value)
+        if rc in (ERR_INVALID_CHECK, ERR_BAD_DATA, ERR_INSUFFICIENT_SPACE):
+            self._raise(rc, info)
+        raise GzpxError(rc, self.lib.strerror(rc))
+
+    def where_lines_device(self, index, lines, d_in_ptr, in_len, line_ranges, field_delim, terms, any=False, invert=False,
+                           d_runs_ptr=None, runs_cap=0, stream=None):
+        """The lines of line_ranges[n, 2] whose numbers pass a predicate: `terms` is a sequence of (field number, COL_INT64 |
+        COL_FLOAT64, WHERE_*, value), the field numbers non-descending, WHERE_MAX_TERMS at most on COLUMNS_MAX distinct
+        fields.  A row passes when all terms hold (any: when one does); invert selects the rows that do not pass.  The
+        selected rows as runs of consecutive rows of one range: line ranges (begin, end) uint64 pairs, in row order, into
+        the device array d_runs_ptr (runs_cap entries; None counts only).  Returns (n_runs, n_selected, n_rows, n_not_ok).
+        A bad line range raises GzpxError with .range_index; more runs than runs_cap: the first runs_cap are written and
+        GzpxError is raised with .needed = n_runs."""
+        r = np.ascontiguousarray(np.asarray(line_ranges, dtype=np.uint64).reshape(-1, 2))
+        return self._where_lines(self.lib.L.gzpx_where_lines_device, index, lines, d_in_ptr, in_len, r.ctypes.data, r.shape[0],
+                                 field_delim, terms, any, invert, d_runs_ptr, runs_cap, stream)
+
+    def where_lines_table_device(self, index, lines, d_in_ptr, in_len, d_line_ranges_ptr, n_ranges, field_delim, terms, any=False,
+                                 invert=False, d_runs_ptr=None, runs_cap=0, stream=None):
+        """where_lines_device with its line ranges in device memory: d_line_ranges_ptr is uint64[n_ranges, 2] (the table
+        select_lines_device wrote, for one)."""
+        return self._where_lines(self.lib.L.gzpx_where_lines_table_device, index, lines, d_in_ptr, in_len, d_line_ranges_ptr,
+                                 n_ranges, field_delim, terms, any, invert, d_runs_ptr, runs_cap, stream)
+
+    def last_where_ms(self):
+        """HIP-event durations of the last where_lines call's stages behind the search: (carries + row scan, parse with the
+        predicate, runs)."""
+        ms = (ctypes.c_float * 3)()
+        self.lib.check(self.lib.L.gzpx_dctx_last_where_ms(self.h, ms))
+        return ms[0], ms[1], ms[2]
 
     # ---- batches of raw / zlib / gzip members that lie in device memory (gzpx_wrap.h)
     def inflate_batch_device(self, wrap, d_in_ptr, in_len, d_in_offsets_ptr, d_in_sizes_ptr, d_out_sizes_ptr, n, d_out_ptr,

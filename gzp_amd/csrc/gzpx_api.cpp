@@ -1679,6 +1679,54 @@ struct ColumnsState : NoCopy {
     }
 };
 
+// selection of lines by their numbers (gzpx_where_lines_device and its table form): the line search's state in front,
+// then the columns' stages in scratch of its own, the two bitmaps and the runs
+struct WhereState : NoCopy {
+    Event ev[4];        // carries + row scan [0..1], the parse with the predicate [1..2], the runs [2..3]
+    bool have = false;  // ev holds the last call's stages
+    WhereScratch wh;
+    ClCols *h_cols = nullptr;     // pinned: the distinct fields on their way in
+    WhTerms *h_terms = nullptr;   // pinned: the compiled terms on their way in
+    uint64_t *h_rec = nullptr;    // pinned: the record on its way out
+    Allocs once;                  // wh.cl.cols, wh.cl.rec, wh.cl.fl.rec, wh.terms, wh.rec and the three pinned arrays above
+    size_t range_cap = 0, piece_cap = 0, bit_cap = 0;
+    Allocs ranges;  // wh.cl.fl.pfirst, wh.cl.row_off
+    Allocs pieces;  // wh.cl.fl.carry, wh.cl.fl.cin, wh.cl.rcnt, wh.cl.rin
+    Allocs rows;    // wh.bitmap (wh.starts behind it), wh.cnt, wh.bases
+    int reserve(size_t n_ranges, size_t n_pieces, uint64_t bits) {
+        ColumnsScratch &cl = wh.cl;
+        if (!wh.rec) {
+            once.release();  // (an earlier attempt that failed half way)
+            GZPX_TRY(once.dev(cl.cols, sizeof(ClCols)));
+            GZPX_TRY(once.dev(cl.fl.rec, kFlRecWords * 8));
+            GZPX_TRY(once.dev(cl.rec, kClRecWords * 8));
+            GZPX_TRY(once.dev(wh.terms, sizeof(WhTerms)));
+            GZPX_TRY(once.pinned(h_cols, sizeof(ClCols)));
+            GZPX_TRY(once.pinned(h_terms, sizeof(WhTerms)));
+            GZPX_TRY(once.pinned(h_rec, kWhRecWords * 8));
+            for (Event &e : ev) GZPX_TRY(e.create(true));
+            GZPX_TRY(once.dev(wh.rec, kWhRecWords * 8));
+        }
+        GZPX_TRY(grow(ranges, range_cap, n_ranges, n_ranges + n_ranges / 4 + 64, [&](size_t cap) -> int {
+            GZPX_TRY(ranges.dev(cl.fl.pfirst, (cap + 1) * 8));
+            return ranges.dev(cl.row_off, (cap + 1) * 8);
+        }));
+        GZPX_TRY(grow(pieces, piece_cap, n_pieces + 1, n_pieces + n_pieces / 8 + 16, [&](size_t cap) -> int {
+            GZPX_TRY(pieces.dev(cl.fl.carry, cap * 4));
+            GZPX_TRY(pieces.dev(cl.fl.cin, cap * 8));
+            GZPX_TRY(pieces.dev(cl.rcnt, cap * 4));
+            return pieces.dev(cl.rin, cap * 8);
+        }));
+        // (the call's bitmaps are where_bits() bits each, back to back: wh.starts is placed per call)
+        return grow(rows, bit_cap, (size_t)bits, (size_t)where_bits(bits + bits / 8 + 4096), [&](size_t cap) -> int {
+            const size_t groups = cap / kSlRunRecords;
+            GZPX_TRY(rows.dev(wh.bitmap, cap / 8 * 2));
+            GZPX_TRY(rows.dev(wh.cnt, groups * 8));
+            return rows.dev(wh.bases, groups * 4);
+        });
+    }
+};
+
 }  // namespace
 
 // (members are destroyed last to first: memory and events of the slots and of each kind of call, then the streams)
@@ -1704,6 +1752,7 @@ struct gzpx_dctx : NoCopy {
     FindSetState find_set;
     FieldsState fields;
     ColumnsState columns;
+    WhereState where;
     DSlot slots[kSlots];
     std::mutex mu;
     std::condition_variable cv_slot;
@@ -3136,6 +3185,158 @@ int gzpx_dctx_last_columns_ms(gzpx_dctx *ctx, float ms[2]) {
     if (!f.have) return GZPX_OK;
     if (hipEventElapsedTime(&ms[0], f.ev[0], f.ev[1]) != hipSuccess || hipEventElapsedTime(&ms[1], f.ev[1], f.ev[2]) != hipSuccess)
         return GZPX_ERR_DEVICE;
+    return GZPX_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- selection of lines by their numbers (gzpx_where.h)
+namespace {
+
+// The terms as the kernels take them: the distinct fields as a column list, and the terms grouped by column.  False:
+// they break a rule of gzpx.h.
+bool where_compile(const gzpx_where_term *terms, size_t n_terms, unsigned flags, ClCols &list, WhTerms &t) {
+    static_assert(kWhMaxTerms == GZPX_WHERE_MAX_TERMS && kWhLt == GZPX_WHERE_LT && kWhLe == GZPX_WHERE_LE && kWhEq == GZPX_WHERE_EQ &&
+                      kWhNe == GZPX_WHERE_NE && kWhGe == GZPX_WHERE_GE && kWhGt == GZPX_WHERE_GT && kWhIsOk == GZPX_WHERE_IS_OK &&
+                      kWhNotOk == GZPX_WHERE_NOT_OK,
+                  "the public constants state the kernels' limit and codes");
+    if (!terms || n_terms == 0 || n_terms > kWhMaxTerms || (flags & ~(GZPX_WHERE_ANY | GZPX_WHERE_INVERT))) return false;
+    for (size_t i = 0; i < kClMaxCols; i++) {
+        list.field[i] = UINT64_MAX;
+        list.type[i] = 0;
+    }
+    memset(&t, 0, sizeof t);
+    uint32_t n = 0;  // distinct fields so far
+    for (size_t i = 0; i < n_terms; i++) {
+        const gzpx_where_term &m = terms[i];
+        if (m.type != GZPX_COL_INT64 && m.type != GZPX_COL_FLOAT64) return false;
+        if (m.op > GZPX_WHERE_NOT_OK) return false;
+        const bool status_op = m.op == GZPX_WHERE_IS_OK || m.op == GZPX_WHERE_NOT_OK;
+        if (status_op && m.value) return false;
+        if (!status_op && m.type == GZPX_COL_FLOAT64 && (m.value & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return false;  // a NaN
+        if (i && terms[i - 1].field > m.field) return false;
+        if (i && terms[i - 1].field == m.field) {
+            if (terms[i - 1].type != m.type) return false;
+        } else {
+            if (n == kClMaxCols) return false;
+            list.field[n] = m.field;
+            list.type[n] = m.type;
+            t.first[n++] = (uint32_t)i;
+        }
+        t.value[i] = m.value;
+        t.op[i] = m.op;
+    }
+    for (uint32_t c = n; c <= kClMaxCols; c++) t.first[c] = (uint32_t)n_terms;
+    t.any = (flags & GZPX_WHERE_ANY) ? 1u : 0u;
+    list.n = n;
+    list.pad = 0;
+    return true;
+}
+
+// gzpx_where_lines_device, and with `on_device` gzpx_where_lines_table_device: line_ranges is then a device array.  The
+// line search of read_lines, then the carries of gzpx_fields.h, the rows of gzpx_columns.h, the parse with the predicate
+// and the runs of gzpx_where.h, enqueued together; one record comes back.  The bitmaps are sized by a bound on the rows
+// that the host knows: the rows themselves in the host form, the ranges' bytes in the table form.
+int where_lines(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                const gzpx_range *line_ranges, bool on_device, size_t n_ranges, unsigned field_delim, const gzpx_where_term *terms,
+                size_t n_terms, unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_selected,
+                uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
+    if (!c || !ix || !lt || !n_runs || !n_selected || !n_rows || (!line_ranges && n_ranges) || (!d_in && in_len))
+        return GZPX_ERR_INVALID_ARG;
+    *n_runs = *n_selected = *n_rows = 0;
+    if (n_not_ok) *n_not_ok = 0;
+    if (bad_range) *bad_range = (size_t)-1;
+    std::unique_lock<std::mutex> lk(c->mu);
+    WhereState &f = c->where;
+    c->lines.stages = 0;
+    c->lines.last_members = 0;
+    f.have = false;
+    if (!lines_match(c, ix, lt, in_len) || n_ranges > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    if (field_delim > 255u || field_delim == lt->delim || ((uintptr_t)d_runs & 7u)) return GZPX_ERR_INVALID_ARG;
+    ClCols list;
+    WhTerms compiled;
+    if (!where_compile(terms, n_terms, flags, list, compiled)) return GZPX_ERR_INVALID_ARG;
+    if (n_ranges == 0) return GZPX_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
+    const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
+    uint64_t bytes = 0;  // of the ranges, in staging
+    GZPX_TRY(lines_search(c, si, ix, lt, (const uint8_t *)d_in, (const uint64_t *)line_ranges, n_ranges, 2u, bad_range, info,
+                          (hipStream_t)hip_stream, &bytes, on_device));
+    // every line of a range holds at least one byte of it: R <= bytes
+    uint64_t bound = bytes;
+    if (!on_device) {
+        bound = 0;
+        for (size_t r = 0; r < n_ranges; r++) bound += line_ranges[r].end - line_ranges[r].begin;  // (valid: the search said so)
+    }
+    if (bound > 0xFFFFFFF0ull) return GZPX_ERR_INVALID_ARG;
+    if (bound == 0) return GZPX_OK;  // every range is empty
+    const uint64_t grid = fields_pieces(bytes, n_ranges), bits = where_bits(bound);
+    if (grid > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;  // (the passes' grid)
+    GZPX_TRY(f.reserve(n_ranges, (size_t)grid, bits));
+    f.wh.starts = f.wh.bitmap + bits / 32u;
+    hipStream_t stream = c->stream;
+    Drain drain{{stream}, 1};
+    const RangeScratch &rr = c->ranges.rr;
+    const ColumnsScratch &cl = f.wh.cl;
+    const uint64_t cap = d_runs ? runs_cap : 0;
+    const int invert = ((flags & GZPX_WHERE_ANY) ? 0 : 1) ^ ((flags & GZPX_WHERE_INVERT) ? 1 : 0);  // without ANY the bits say "rejected"
+    *f.h_cols = list;
+    *f.h_terms = compiled;
+    HIP_TRY(hipMemcpyAsync(cl.cols, f.h_cols, sizeof(ClCols), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(f.wh.terms, f.h_terms, sizeof(WhTerms), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(f.ev[0], stream));
+    launch_fields_carry(c->stage.d, (uint32_t)n_ranges, rr, cl.fl, lt->delim, field_delim, (uint32_t)grid, stream);
+    launch_columns_rows(c->stage.d, (uint32_t)n_ranges, rr, c->lines.ln, cl, lt->delim, field_delim, (uint32_t)grid, cl.row_off, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f.ev[1], stream));
+    launch_where_parse(c->stage.d, (uint32_t)n_ranges, rr, f.wh, lt->delim, field_delim, (uint32_t)grid, cl.row_off, bits, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f.ev[2], stream));
+    launch_where_runs((uint32_t)n_ranges, c->lines.ln, f.wh, cl.row_off, bits, invert, (uint64_t *)d_runs, cap, stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f.ev[3], stream));
+    HIP_TRY(hipMemcpyAsync(f.h_rec, f.wh.rec, kWhRecWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    f.have = true;
+    *n_runs = f.h_rec[kWhRecRuns];
+    *n_selected = f.h_rec[kWhRecSelected];
+    *n_rows = f.h_rec[kWhRecRows];
+    if (n_not_ok) *n_not_ok = f.h_rec[kWhRecNotOk];
+    if (*n_rows > bits) return GZPX_ERR_INVALID_ARG;  // (the table and the stream do not belong together: nothing was marked)
+    return d_runs && *n_runs > cap ? GZPX_ERR_INSUFFICIENT_SPACE : GZPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gzpx_where_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                            const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_where_term *terms,
+                            size_t n_terms, unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs,
+                            uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info,
+                            void *hip_stream) {
+    return where_lines(c, ix, lt, d_in, in_len, line_ranges, false, n_ranges, field_delim, terms, n_terms, flags, d_runs, runs_cap,
+                       n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
+}
+
+int gzpx_where_lines_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                                  const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim,
+                                  const gzpx_where_term *terms, size_t n_terms, unsigned flags, gzpx_range *d_runs, size_t runs_cap,
+                                  uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range,
+                                  gzpx_check_info *info, void *hip_stream) {
+    return where_lines(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, field_delim, terms, n_terms, flags, d_runs, runs_cap,
+                       n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
+}
+
+int gzpx_dctx_last_where_ms(gzpx_dctx *ctx, float ms[3]) {
+    if (!ctx || !ms) return GZPX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ms[0] = ms[1] = ms[2] = 0.0f;
+    const WhereState &f = ctx->where;
+    if (!f.have) return GZPX_OK;
+    for (int j = 0; j < 3; j++)
+        if (hipEventElapsedTime(&ms[j], f.ev[j], f.ev[j + 1]) != hipSuccess) return GZPX_ERR_DEVICE;
     return GZPX_OK;
 }
 

@@ -9,7 +9,7 @@
 //   k_cl_rows_scan   one workgroup: rbase = the exclusive sum of the ranges' line counts -> row_off, the rows R into the
 //                    record; a scan of the pieces' counts restarted at every range's first piece -> rin[x], the lines of
 //                    its range in front of piece x.  The row of piece x's first byte is row_off[r] + rin[x].
-//   k_cl_parse       one workgroup per piece, fl_walk's geometry: 256 lanes x one aligned 16-byte word a row, the four
+//   k_cl_parse       cl_parse with the storing sink.  One workgroup per piece, fl_walk's geometry: 256 lanes x one aligned 16-byte word a row, the four
 //                    rows loaded together; the segmented scan gives the field number of every word's first byte, a
 //                    plain scan of the line delimiters its row.  The piece and the kClOverhang bytes behind it (clamped
 //                    at the range's end) are staged in LDS, so the parser's byte steps are LDS reads.
@@ -24,6 +24,10 @@
 // counts are integer atomicAdds of per-workgroup sums: the result is the same bit for bit from run to run.
 // A row at or behind its range's row_off[r + 1] -- staging does not hold the stream the table was built from -- is
 // not stored: nothing is written outside the rows the table promised.
+//
+// THE SINK.  What happens to a cell is a type parameter of the walk (cl_parse<Sink>): ClStore keeps it in the arrays,
+// gzpx_where.h's sink tests it against the terms of its column and keeps nothing.  cl_int, cl_float, cl_open, cl_close
+// and the walk itself are the same code for both, so a cell cannot be parsed differently by the two calls.
 
 constexpr uint32_t kClStageWords = kFlPiece / 16u + (kClOverhang + 15u) / 16u + 1u;
 static_assert(kClOverhang >= kClMaxBytes + 1u, "a field opened by a piece's last byte is parsed from LDS");
@@ -133,7 +137,7 @@ __device__ __forceinline__ uint32_t cl_float(const uint8_t *b, uint32_t len, uin
     return kClOk;
 }
 
-// what k_cl_parse's lanes share
+// what the walk's lanes share
 struct ClWalk {
     const uint64_t *field;  // LDS: the columns' field numbers, ascending
     const uint32_t *type;   // LDS
@@ -144,21 +148,32 @@ struct ClWalk {
     uintptr_t w0, end;      // the range ends at address `end`
     uint32_t delim, fdelim;
     uint64_t row_end;       // the first row behind the range's
+};
+
+// the sink of gzpx_read_columns_device: the cell and its status byte into the arrays
+struct ClStore {
     uint64_t *values;
     uint8_t *status;
     uint64_t rows_cap;
+    // every piece leaves at once when an array is given and the rows do not fit
+    __device__ __forceinline__ bool leaves(uint64_t rows) const { return (values || status) && rows > rows_cap; }
+    __device__ __forceinline__ void operator()(const ClWalk &, uint32_t c, uint64_t row, uint64_t bits, uint32_t st) const {
+        const uint64_t at = (uint64_t)c * rows_cap + row;
+        if (values) values[at] = bits;
+        if (status) status[at] = (uint8_t)st;
+    }
 };
 
-__device__ __forceinline__ void cl_store(const ClWalk &k, uint32_t c, uint64_t row, uint64_t bits, uint32_t st) {
+template <class Sink>
+__device__ __forceinline__ void cl_store(const ClWalk &k, const Sink &sink, uint32_t c, uint64_t row, uint64_t bits, uint32_t st) {
     if (row >= k.row_end) return;
     if (st != kClOk) atomicAdd(&k.bad[c], 1u);
-    const uint64_t at = (uint64_t)c * k.rows_cap + row;
-    if (k.values) k.values[at] = bits;
-    if (k.status) k.status[at] = (uint8_t)st;
+    sink(k, c, row, bits, st);
 }
 
 // the field of number f that starts at address s, in row `row`
-__device__ __forceinline__ void cl_open(const ClWalk &k, uint64_t f, uintptr_t s, uint64_t row) {
+template <class Sink>
+__device__ __forceinline__ void cl_open(const ClWalk &k, const Sink &sink, uint64_t f, uintptr_t s, uint64_t row) {
     if (f < k.lo || f > k.hi) return;
     uint32_t lo = 0, hi = k.n;
     while (lo < hi) {
@@ -178,13 +193,15 @@ __device__ __forceinline__ void cl_open(const ClWalk &k, uint64_t f, uintptr_t s
     else if (len > kClMaxBytes) st = kClInvalid;
     else st = is_int ? cl_int(b, len, &bits) : cl_float(b, len, &bits);
     if (st != kClOk) bits = is_int ? 0u : kClNaN;
-    cl_store(k, lo, row, bits, st);
+    cl_store(k, sink, lo, row, bits, st);
 }
 
 // a line of F fields ends in row `row`
-__device__ __forceinline__ void cl_close(const ClWalk &k, uint64_t F, uint64_t row) {
+template <class Sink>
+__device__ __forceinline__ void cl_close(const ClWalk &k, const Sink &sink, uint64_t F, uint64_t row) {
     if (F > k.hi) return;
-    for (uint32_t c = k.n; c > 0u && k.field[c - 1u] >= F; c--) cl_store(k, c - 1u, row, k.type[c - 1u] == 0u ? 0u : kClNaN, kClMissing);
+    for (uint32_t c = k.n; c > 0u && k.field[c - 1u] >= F; c--)
+        cl_store(k, sink, c - 1u, row, k.type[c - 1u] == 0u ? 0u : kClNaN, kClMissing);
 }
 
 // Workgroup x: rcnt[x] = the line delimiters of piece x.
@@ -246,26 +263,31 @@ __global__ __launch_bounds__(kFlThreads) void k_cl_rows_scan(const uint64_t *__r
     }
 }
 
-// Workgroup x: the cells of the fields that piece x's bytes open, and MISSING for the lines it closes.  Every piece
-// leaves at once when an array is given and the rows do not fit.
-__global__ __launch_bounds__(kFlThreads) void k_cl_parse(FlArgs a, const ClCols *__restrict__ cols, const uint64_t *__restrict__ cin,
-                                                         const uint64_t *__restrict__ rin, const uint64_t *__restrict__ row_off,
-                                                         uint64_t *rec, uint64_t *__restrict__ values, uint8_t *__restrict__ status,
-                                                         uint64_t rows_cap) {
-    __shared__ uint64_t s_field[kClMaxCols];
-    __shared__ uint32_t s_type[kClMaxCols];
-    __shared__ uint32_t s_bad[kClMaxCols];
-    __shared__ uint32_t wsum[4u * kFlItems];
-    __shared__ uint4 buf[kClStageWords];
+// what a workgroup of the walk keeps in LDS
+struct ClLds {
+    uint64_t field[kClMaxCols];
+    uint32_t type[kClMaxCols];
+    uint32_t bad[kClMaxCols];
+    uint32_t wsum[4u * kFlItems];
+    uint4 buf[kClStageWords];
+};
+
+// Workgroup x: the cells of the fields that piece x's bytes open, and MISSING for the lines it closes, each handed to
+// the sink.  Every piece leaves at once when the sink says so of the rows.  (Whatever the caller staged in LDS of its
+// own is readable in the sink: the scans' barriers stand in front of the walk.)
+template <class Sink>
+__device__ __forceinline__ void cl_parse(const FlArgs &a, ClLds &l, const ClCols *__restrict__ cols, const uint64_t *__restrict__ cin,
+                                         const uint64_t *__restrict__ rin, const uint64_t *__restrict__ row_off, uint64_t *rec,
+                                         const Sink &sink) {
     uintptr_t a0, a1, end;
     bool head;
     uint32_t r;
     if (!fl_piece(a, blockIdx.x, a0, a1, head, r, end)) return;
-    if ((values || status) && rec[kClRecRows] > rows_cap) return;  // (the whole workgroup)
+    if (sink.leaves(rec[kClRecRows])) return;  // (the whole workgroup)
     if (threadIdx.x < kClMaxCols) {
-        s_field[threadIdx.x] = cols->field[threadIdx.x];
-        s_type[threadIdx.x] = cols->type[threadIdx.x];
-        s_bad[threadIdx.x] = 0;
+        l.field[threadIdx.x] = cols->field[threadIdx.x];
+        l.type[threadIdx.x] = cols->type[threadIdx.x];
+        l.bad[threadIdx.x] = 0;
     }
     FlRows w;
     fl_rows(a, a0, a1, w);
@@ -273,34 +295,31 @@ __global__ __launch_bounds__(kFlThreads) void k_cl_parse(FlArgs a, const ClCols 
 #pragma unroll
     for (uint32_t u = 0; u < kFlItems; u++) {
         const uint32_t i = u * kFlThreads + threadIdx.x;
-        if (w0 + 16u * (uintptr_t)i < a1) buf[i] = w.v[u];
+        if (w0 + 16u * (uintptr_t)i < a1) l.buf[i] = w.v[u];
     }
     {  // the overhang: the words behind the piece's that hold a byte in front of min(end, a1 + kClOverhang)
         const uintptr_t lim = end - a1 < kClOverhang ? end : a1 + kClOverhang;
         const uint32_t first = (uint32_t)((a1 - w0 + 15u) / 16u), last = (uint32_t)((lim - w0 + 15u) / 16u);
-        if (first + threadIdx.x < last) buf[first + threadIdx.x] = *(const uint4 *)(w0 + 16u * (uintptr_t)(first + threadIdx.x));
+        if (first + threadIdx.x < last) l.buf[first + threadIdx.x] = *(const uint4 *)(w0 + 16u * (uintptr_t)(first + threadIdx.x));
     }
     uint32_t ex[kFlItems], rx[kFlItems], dc[kFlItems], total;
-    fl_scan<kFlItems>(w.e, wsum, ex, &total);  // (its barriers stand between the stores to LDS above and the reads below)
+    fl_scan<kFlItems>(w.e, l.wsum, ex, &total);  // (its barriers stand between the stores to LDS above and the reads below)
 #pragma unroll
     for (uint32_t u = 0; u < kFlItems; u++) dc[u] = (uint32_t)__popc(w.dm[u]);
-    fl_scan<kFlItems>(dc, wsum, rx, &total);  // (plain sums)
+    fl_scan<kFlItems>(dc, l.wsum, rx, &total);  // (plain sums)
     ClWalk k;
-    k.field = s_field;
-    k.type = s_type;
-    k.bad = s_bad;
+    k.field = l.field;
+    k.type = l.type;
+    k.bad = l.bad;
     k.n = cols->n;
-    k.lo = s_field[0];
-    k.hi = s_field[k.n - 1u];
-    k.lds = (const uint8_t *)buf;
+    k.lo = l.field[0];
+    k.hi = l.field[k.n - 1u];
+    k.lds = (const uint8_t *)l.buf;
     k.w0 = w0;
     k.end = end;
     k.delim = a.delim;
     k.fdelim = a.fdelim;
     k.row_end = row_off[r + 1u];
-    k.values = values;
-    k.status = status;
-    k.rows_cap = rows_cap;
     const uint64_t cin_x = cin[blockIdx.x], row_x = row_off[r] + rin[blockIdx.x];
 #pragma unroll
     for (uint32_t u = 0; u < kFlItems; u++) {
@@ -308,28 +327,37 @@ __global__ __launch_bounds__(kFlThreads) void k_cl_parse(FlArgs a, const ClCols 
         const uintptr_t p = w0 + 16u * (uintptr_t)(u * kFlThreads + threadIdx.x);
         uint64_t f = ((ex[u] & kFlReset) ? 0u : cin_x) + (ex[u] & ~kFlReset);
         uint64_t row = row_x + rx[u];
-        if (head && p <= a0) cl_open(k, 0, a0, row);  // the range's first byte (vm: a0 < p + 16)
+        if (head && p <= a0) cl_open(k, sink, 0, a0, row);  // the range's first byte (vm: a0 < p + 16)
         for (uint32_t marks = w.fm[u] | w.dm[u]; marks; marks &= marks - 1u) {
             const uint32_t bit = marks & (0u - marks);
             const uintptr_t s = p + (uint32_t)__ffs((int)bit);  // the byte behind the mark
             if (w.dm[u] & bit) {
-                cl_close(k, f + 1u, row);
+                cl_close(k, sink, f + 1u, row);
                 row++;
                 f = 0;
-                if (s < end) cl_open(k, 0, s, row);
+                if (s < end) cl_open(k, sink, 0, s, row);
             } else {
                 f++;
-                cl_open(k, f, s, row);
+                cl_open(k, sink, f, s, row);
             }
         }
         // the range's last byte, when it does not end its line
-        if (a1 == end && end - p <= 16u && !((w.dm[u] >> (uint32_t)(end - 1u - p)) & 1u)) cl_close(k, f + 1u, row);
+        if (a1 == end && end - p <= 16u && !((w.dm[u] >> (uint32_t)(end - 1u - p)) & 1u)) cl_close(k, sink, f + 1u, row);
     }
     __syncthreads();
-    if (threadIdx.x < k.n && s_bad[threadIdx.x]) atomicAdd((unsigned long long *)&rec[kClRecCol + threadIdx.x], (unsigned long long)s_bad[threadIdx.x]);
+    if (threadIdx.x < k.n && l.bad[threadIdx.x]) atomicAdd((unsigned long long *)&rec[kClRecCol + threadIdx.x], (unsigned long long)l.bad[threadIdx.x]);
     if (threadIdx.x == 0) {
         uint32_t sum = 0;
-        for (uint32_t c = 0; c < k.n; c++) sum += s_bad[c];
+        for (uint32_t c = 0; c < k.n; c++) sum += l.bad[c];
         if (sum) atomicAdd((unsigned long long *)&rec[kClRecNotOk], (unsigned long long)sum);
     }
+}
+
+// The walk with the storing sink: every cell of rows [0, R) into d_values / d_status.
+__global__ __launch_bounds__(kFlThreads) void k_cl_parse(FlArgs a, const ClCols *__restrict__ cols, const uint64_t *__restrict__ cin,
+                                                         const uint64_t *__restrict__ rin, const uint64_t *__restrict__ row_off,
+                                                         uint64_t *rec, uint64_t *__restrict__ values, uint8_t *__restrict__ status,
+                                                         uint64_t rows_cap) {
+    __shared__ ClLds l;
+    cl_parse(a, l, cols, cin, rin, row_off, rec, ClStore{values, status, rows_cap});
 }

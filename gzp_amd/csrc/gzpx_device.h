@@ -487,6 +487,40 @@ void launch_columns_parse(const uint8_t *d_stage, uint32_t n_ranges, const Range
                           uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t *d_values, uint8_t *d_status,
                           uint64_t rows_cap, hipStream_t stream);
 
+// Selection of lines by their numbers (gzpx_where.h): the columns' stages with the distinct fields of the terms as the
+// column list, the parse testing every cell against the terms of its column instead of storing it, then the runs of the
+// row bitmap, cut at every range's first row.  The host compiles the terms into a WhTerms; the terms of column c are
+// [first[c], first[c + 1]), in the caller's order.
+constexpr uint32_t kWhMaxTerms = 32;  // GZPX_WHERE_MAX_TERMS
+enum { kWhLt = 0, kWhLe = 1, kWhEq = 2, kWhNe = 3, kWhGe = 4, kWhGt = 5, kWhIsOk = 6, kWhNotOk = 7 };  // GZPX_WHERE_*
+struct WhTerms {
+    uint64_t value[kWhMaxTerms];
+    uint32_t op[kWhMaxTerms];
+    uint32_t first[kClMaxCols + 1u];
+    uint32_t any;  // 1: a cell that makes a term TRUE marks its row; 0: one that makes a term FALSE does
+};
+// the record (u64 words): runs, selected rows, rows, cells that are not OK
+enum { kWhRecRuns = 0, kWhRecSelected = 1, kWhRecRows = 2, kWhRecNotOk = 3, kWhRecWords = 4 };
+struct WhereScratch {
+    ColumnsScratch cl;           // the columns' stages: every member but the arrays of cells
+    WhTerms *terms = nullptr;    // the compiled terms
+    uint32_t *bitmap = nullptr;  // [bits / 32] bit i: a cell of row i decided its row (rejected it, or under ANY accepted it)
+    uint32_t *starts = nullptr;  // [bits / 32] bit i: row i is the first of its range; it lies behind bitmap, one memset clears both
+    uint32_t *cnt = nullptr;     // [2 * groups] (rising edges, set bits) of every kSlRunRecords rows
+    uint32_t *bases = nullptr;   // [groups] the rank of a group's first rising edge
+    uint64_t *rec = nullptr;     // [kWhRecWords]
+};
+// the bits of a bitmap that serves `bound` rows: whole groups of the runs kernels
+inline uint64_t where_bits(uint64_t bound) { return select_groups(bound) * kSlRunRecords; }
+// behind launch_columns_rows on w.cl: both bitmaps cleared (`bits` = where_bits()), then the parse with the predicate;
+// nothing is marked when the record's rows exceed `bits`
+void launch_where_parse(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const WhereScratch &w, uint32_t delim,
+                        uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t bits, hipStream_t stream);
+// behind it: w.rec, and the runs below rank `cap` into d_runs (null: counts only) as (begin, end) pairs of line numbers.
+// `invert`: the selected rows are those whose bit is clear.  l.bounds holds the (begin, end) line numbers of the ranges.
+void launch_where_runs(uint32_t n_ranges, const LinesScratch &l, const WhereScratch &w, const uint64_t *d_row_off, uint64_t bits,
+                       int invert, uint64_t *d_runs, uint64_t cap, hipStream_t stream);
+
 // Search for a set of patterns (gzpx_findset.h).  The host compiles the set into an FsSet, the form the kernels stage
 // into LDS: q = min(shortest pattern, 4); the WINDOW of a pattern is its first q bytes as a little-endian number.
 constexpr uint32_t kFsMaxPatterns = 256;  // GZPX_FINDSET_MAX_PATTERNS

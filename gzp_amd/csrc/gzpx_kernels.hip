@@ -5417,6 +5417,7 @@ __global__ __launch_bounds__(64, GZPX_INF_WAVES) void k_inflate(const uint8_t *_
 #include "gzpx_select.h"
 #include "gzpx_fields.h"
 #include "gzpx_columns.h"
+#include "gzpx_where.h"
 #include "gzpx_findset.h"
 #include "gzpx_wrap.h"
 #include "gzpx_cksum.h"
@@ -6007,6 +6008,32 @@ void launch_columns_parse(const uint8_t *d_stage, uint32_t n_ranges, const Range
         hipLaunchKernelGGL(k_cl_parse, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, c.fl, delim, field_delim),
                            (const ClCols *)c.cols, (const uint64_t *)c.fl.cin, (const uint64_t *)c.rin, d_row_off, c.rec, d_values,
                            d_status, rows_cap);
+}
+
+// Selection of lines by their numbers (gzpx_where.h), behind launch_columns_rows on w.cl: the parse with the predicate,
+// then the runs.  The rows are known on the device only: `bits` sizes the bitmaps and bounds the grids.
+void launch_where_parse(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const WhereScratch &w, uint32_t delim,
+                        uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t bits, hipStream_t stream) {
+    (void)hipMemsetAsync(w.bitmap, 0, (size_t)(bits / 8u) * 2u, stream);  // (w.starts lies behind w.bitmap)
+    if (grid)
+        hipLaunchKernelGGL(k_wh_parse, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, w.cl.fl, delim, field_delim),
+                           (const ClCols *)w.cl.cols, (const WhTerms *)w.terms, (const uint64_t *)w.cl.fl.cin, (const uint64_t *)w.cl.rin,
+                           d_row_off, w.cl.rec, w.bitmap, bits);
+}
+
+void launch_where_runs(uint32_t n_ranges, const LinesScratch &l, const WhereScratch &w, const uint64_t *d_row_off, uint64_t bits,
+                       int invert, uint64_t *d_runs, uint64_t cap, hipStream_t stream) {
+    const uint64_t groups = bits / kSlRunRecords;
+    const uint32_t grid = (uint32_t)(groups < kWhRunGrid ? groups : kWhRunGrid), inv = invert ? 1u : 0u;
+    const uint8_t *rows = (const uint8_t *)w.bitmap, *starts = (const uint8_t *)w.starts;
+    hipLaunchKernelGGL(k_wh_starts, dim3((n_ranges + kFlThreads - 1u) / kFlThreads), dim3(kFlThreads), 0, stream, d_row_off, n_ranges, bits,
+                       w.starts);
+    if (grid) hipLaunchKernelGGL(k_wh_runs_count, dim3(grid), dim3(kSlRunThreads), 0, stream, rows, starts, (const uint64_t *)w.cl.rec, bits, inv, w.cnt);
+    hipLaunchKernelGGL(k_wh_runs_scan, dim3(1), dim3(kFdThreads), 0, stream, (const uint32_t *)w.cnt, (const uint64_t *)w.cl.rec, bits,
+                       w.bases, w.rec);
+    if (grid && d_runs && cap)
+        hipLaunchKernelGGL(k_wh_runs_write, dim3(grid), dim3(kSlRunThreads), 0, stream, rows, starts, (const uint64_t *)w.cl.rec, bits, inv,
+                           (const uint32_t *)w.cnt, (const uint32_t *)w.bases, d_row_off, (const uint64_t *)l.bounds, n_ranges, d_runs, cap);
 }
 
 size_t inflate_mlist_bytes(uint64_t out_cap, uint64_t nb) { return (size_t)((out_cap / 3u + nb + 2u) * sizeof(LzMatch)); }

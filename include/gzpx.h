@@ -634,6 +634,74 @@ int gzpx_read_columns_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const 
                                    uint64_t *n_rows, uint64_t *n_not_ok, uint64_t *d_col_not_ok, uint64_t *d_row_offsets,
                                    size_t *bad_range, gzpx_check_info *info, void *hip_stream);
 int gzpx_dctx_last_columns_ms(gzpx_dctx *ctx, float ms[2]);
+/* ---- selection of lines by their numbers (gzpx_where.h): awk '$6 >= 30' between grep and cut -- the VCF rows with
+ * QUAL >= 30 and 1000000 <= POS < 2000000, the TSV rows whose measurement is above a threshold -- as a table of line
+ * ranges in device memory that gzpx_read_lines_table_device, gzpx_read_fields_table_device and
+ * gzpx_read_columns_table_device take where it lies.  No cell array is materialised and only fixed-size records cross
+ * to the host.  gzpx_read_columns_device and everything in front of it are untouched.
+ * Lines, delimiters, fields, cells, rows.  `plain`, `delim`, line ranges, covers and members read, validation and
+ *   *bad_range, empty, overlapping and repeated ranges, field_delim, the split of a line into fields, the cell grammar
+ *   of both types and the five statuses, the rows (line i of range r is row rbase[r] + i, R the total), the context's
+ *   lock, the slot, hip_stream, "returns synchronised", both inflate routes and the report of a failing member are
+ *   gzpx_read_columns_device's, word for word: the two calls share the code that parses a cell.
+ * Terms.  `terms` is a HOST array of 1..GZPX_WHERE_MAX_TERMS entries with `field` non-descending.  Several terms may
+ *   name one field (100 <= POS, POS < 200); their `type` must then agree.  At most GZPX_COLUMNS_MAX distinct fields.
+ *   `type` is GZPX_COL_INT64 or GZPX_COL_FLOAT64, `op` one of the eight GZPX_WHERE_*; `value` holds the bits of an
+ *   int64_t or of a double by the type, must be 0 for IS_OK and NOT_OK, and for FLOAT64 must not be a NaN.  No flag bit
+ *   beyond GZPX_WHERE_ANY and GZPX_WHERE_INVERT.  Anything else: GZPX_ERR_INVALID_ARG with nothing inflated.
+ * Truth of a term on a row.  Take the row's cell for `field` by the type's rules.  IS_OK / NOT_OK look at the status
+ *   alone.  A comparison on a cell that is not OK (MISSING, EMPTY, INVALID, RANGE) is FALSE, NE included.  On an OK cell
+ *   INT64 compares as signed 64-bit integers and FLOAT64 by IEEE rules: -0.0 == 0.0, an OK cell that is NaN (the text
+ *   "nan") is false for everything but NE, infinities order as usual.
+ * Selected rows.  A row PASSES when all terms hold, with GZPX_WHERE_ANY when at least one does.  The selected set is the
+ *   rows that pass, with GZPX_WHERE_INVERT the rows of [0, R) that do not -- so inversion selects rows whose cells are
+ *   not OK: it negates the predicate, not each comparison.
+ * Runs.  A RUN is a maximal interval of consecutive selected rows OF ONE RANGE: runs never join across two ranges, even
+ *   if the ranges are adjacent or overlap ({0, 5}, {5, 9} all selected gives two runs).  Runs are written in row order
+ *   as LINE ranges {ranges[r].begin + i0, ranges[r].begin + i1}; there are at most (R + n_ranges) / 2, so a table can be
+ *   sized in advance.  With the one range {0, L} this is the table gzpx_select_lines_device writes with group 1.
+ * Outputs.  *n_runs, *n_selected and *n_rows (= R) are always the totals; *n_not_ok (optional) is the number of cells of
+ *   the distinct fields whose status is not OK, what gzpx_read_columns_device reports for the same columns.  d_runs ==
+ *   NULL: count only, runs_cap is ignored.  d_runs (8-byte aligned) with more runs than runs_cap: the first runs_cap are
+ *   written, nothing behind them is touched, and the call returns GZPX_ERR_INSUFFICIENT_SPACE.  n_ranges == 0, or all
+ *   ranges empty: GZPX_OK, all counts 0.  On a failing member all counts are 0.  More than 0xFFFFFFF0 rows:
+ *   GZPX_ERR_INVALID_ARG, behind the search; gzpx_where_lines_device decides by R itself, gzpx_where_lines_table_device,
+ *   where R is known on the device only, by the bound the host knows: the bytes the ranges hold (every line holds at
+ *   least one byte, so R is never above them), which also sizes its row bitmaps.  The result is the same bit for bit
+ *   from run to run: bits set with atomicOr do not depend on order, scans place every run, the counts are integer sums.
+ * gzpx_where_lines_device takes line_ranges as a HOST array, gzpx_where_lines_table_device as a DEVICE array (read
+ *   where it lies, ordered behind hip_stream like d_in): the table gzpx_select_lines_device wrote, for one.
+ * gzpx_dctx_last_where_ms: HIP-event durations of the last call's stages behind the search: [0] the field carries, the
+ *   pieces' row counts and their scans, [1] the parse with the predicate, [2] the runs.  gzpx_dctx_last_lines_ms and
+ *   gzpx_dctx_last_lines_members answer as for gzpx_read_columns_device. */
+#define GZPX_WHERE_MAX_TERMS 32
+#define GZPX_WHERE_LT 0
+#define GZPX_WHERE_LE 1
+#define GZPX_WHERE_EQ 2
+#define GZPX_WHERE_NE 3
+#define GZPX_WHERE_GE 4
+#define GZPX_WHERE_GT 5
+#define GZPX_WHERE_IS_OK 6   /* the cell's status is GZPX_CELL_OK; value must be 0 */
+#define GZPX_WHERE_NOT_OK 7  /* it is not; value must be 0 */
+#define GZPX_WHERE_ANY 1u    /* flags: a row passes when at least one term holds (default: when all hold) */
+#define GZPX_WHERE_INVERT 2u /* flags: select the rows that do not pass */
+typedef struct gzpx_where_term {
+    uint64_t field; /* field number, as gzpx_column.field */
+    uint32_t type;  /* GZPX_COL_INT64 / GZPX_COL_FLOAT64 */
+    uint32_t op;    /* GZPX_WHERE_* */
+    uint64_t value; /* the bits of an int64_t or of a double, by type */
+} gzpx_where_term;
+int gzpx_where_lines_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in, size_t in_len,
+                            const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_where_term *terms,
+                            size_t n_terms, unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs,
+                            uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info,
+                            void *hip_stream);
+int gzpx_where_lines_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in,
+                                  size_t in_len, const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim,
+                                  const gzpx_where_term *terms, size_t n_terms, unsigned flags, gzpx_range *d_runs,
+                                  size_t runs_cap, uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok,
+                                  size_t *bad_range, gzpx_check_info *info, void *hip_stream);
+int gzpx_dctx_last_where_ms(gzpx_dctx *ctx, float ms[3]);
 /* ---- search for a SET of byte strings (gzpx_findset.h): grep -F -e A -e B -f list on a device-resident BGZF / Mgzip
  * stream -- the VCF rows of a handful of contigs, the FASTQ records that carry any of 96 barcodes, the log lines with
  * any of a list of error codes -- in ONE inflate and one pass over it, the hits of all patterns already merged by

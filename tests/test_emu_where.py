@@ -20,6 +20,10 @@ def test_runs(emu_lib):
     where_cases.runs(emu_lib)
 
 
+def test_scan_step(emu_lib):
+    where_cases.scan_step(emu_lib, both_forms=False)
+
+
 def test_capacity(emu_lib):
     where_cases.capacity(emu_lib)
 

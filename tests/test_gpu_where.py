@@ -31,6 +31,10 @@ def test_runs(hip_lib):
     where_cases.runs(hip_lib)
 
 
+def test_scan_step(hip_lib):
+    where_cases.scan_step(hip_lib)
+
+
 def test_capacity(hip_lib):
     where_cases.capacity(hip_lib)
 

@@ -22,6 +22,7 @@ from gzp_amd import _native
 from line_cases import Lines, Opened, cut
 from range_cases import Plain, ROUTES
 from scan_cases import BGZF, MGZIP, HDR, Mem
+from select_cases import RUN_RECORDS, SCAN_STEP
 
 GUARD = 4    # entries behind runs_cap that must stay as they were
 FILL = 0xEE
@@ -309,6 +310,74 @@ def runs(lib):
             # the bound with several ranges: n ranges of one row each, every row selected -- (R + n) / 2 = n runs
             got = check(mem, o, ln, sets["odd lines"], TAB, [(ODD_F, INT, EQ, 1)], False, False, "the bound, ranges")
             assert got == sets["odd lines"]
+
+
+STEP_A, STEP_B, STEP_C, STEP_ALT, STEP_ALL = range(5)  # the fields of step_text
+
+
+def step_runs(L):
+    """select_cases.scan_step's runs for W = kSlRunRecords rows a group and S = W * kSlScanStep rows a step: per field runs
+    across row S, ending at it, starting at it; the same at the group edge 5 W; the first and the last row; both sides of
+    a byte of the bitmap."""
+    W, S = RUN_RECORDS, RUN_RECORDS * SCAN_STEP
+    return {STEP_A: [(0, 1), (3 * W - 1, 3 * W + 1), (S - 2, S + 3), (L - 1, L)],
+            STEP_B: [(7, 8), (5 * W, 5 * W + 2), (S - 3, S), (S + W - 1, S + W), (S + 2 * W, S + 2 * W + 1)],
+            STEP_C: [(8, 9), (5 * W - 2, 5 * W), (S, S + 2), (S + 3 * W - 64, S + 3 * W + 64)]}
+
+
+def step_text(L):
+    """L lines of five 0/1 fields: the three of step_runs, every 16th row from row 1 on, all."""
+    a = np.full((L, 10), TAB, dtype=np.uint8)
+    a[:, 9] = NL
+    a[:, 0:9:2] = ord("0")
+    for f, rs in step_runs(L).items():
+        for b, e in rs:
+            a[b:e, 2 * f] = ord("1")
+    a[1::16, 2 * STEP_ALT] = ord("1")
+    a[:, 2 * STEP_ALL] = ord("1")
+    return a.tobytes()
+
+
+def scan_step(lib, both_forms=True):
+    """k_wh_runs_scan (gzpx_where.h) across its step of kSlScanStep groups of kSlRunRecords rows: about 135,000 lines, so
+    that the ranks of the runs behind row S = 131,072 need the first step's total.  Runs across the step, ending at it and
+    starting at it, one field each, all lines as one range; then sets of ranges whose starts -- the second bitmap, which
+    breaks a run -- fall at rows S - 1, S, S + 1 and S + W, and one of a repeated range with more than two steps of
+    rows: ALL (every 16th row: every group has 32 rising edges of its own) and ANY (the three fields' runs), plain and
+    inverted, the host form and the table form (`both_forms` False, for the emulator: a set takes one form and one of the
+    two formats, in turn)."""
+    mem = Mem(lib)
+    W, S = RUN_RECORDS, RUN_RECORDS * SCAN_STEP
+    L = S + 4 * W + 37
+    assert 130000 <= L <= 290000
+    text = step_text(L)
+    one = lambda f: [(f, INT, EQ, 1)]
+    any_terms = one(STEP_A) + one(STEP_B) + one(STEP_C)
+    all_terms = one(STEP_ALT) + one(STEP_ALL)
+    sets = [[(0, L)], [(0, S - 1), (S - 1, L)], [(0, S), (S, L)], [(0, S + 1), (S + 1, L)], [(0, S + W), (S + W, L)], [(0, L // 3)] * 7]
+    assert 7 * (L // 3) > 2 * S
+    ln = None
+    for fmt in FORMATS:
+        s = cut(fmt, text, list(range(60000, len(text), 60000)))
+        pl = Plain(fmt, s)
+        assert pl.plain == text and len(s) <= 300000
+        ln = ln or Lines(pl, NL)  # (the same lines in both formats: the model's cells are made once)
+        assert ln.L == L
+        for f, rs in step_runs(L).items():  # the model's own runs are the intended ones
+            assert model(ln, NL, TAB, [(0, L)], one(f))[0] == rs
+        assert len(model(ln, NL, TAB, [(0, L)], all_terms)[0]) == -(-(L - 1) // 16) > L // W
+        assert model(ln, NL, TAB, sets[2], one(STEP_A))[0][2:4] == [(S - 2, S), (S, S + 3)]  # a range's start breaks a run
+        with Opened(lib, mem, fmt, s, NL, ROUTES[fmt == MGZIP]) as o:
+            for f in step_runs(L):
+                for invert in (False, True):
+                    check(mem, o, ln, [(0, L)], TAB, one(f), False, invert, ("scan step", fmt, f, invert), table=invert, count=not invert)
+            for i, rs in enumerate(sets):
+                if not both_forms and FORMATS[i % 2] != fmt:
+                    continue
+                for terms, any_ in ((all_terms, False), (any_terms, True)):
+                    for invert in (False, True):
+                        for table in ((False, True) if both_forms else (i in (1, 2, 5),)):
+                            check(mem, o, ln, rs, TAB, terms, any_, invert, ("scan step", fmt, rs[:2], any_, invert, table), table=table)
 
 
 # ------------------------------------------------------------------------------------------------ 4. capacity

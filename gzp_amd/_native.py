@@ -65,6 +65,10 @@ COLUMN_DTYPE = [("field", "<u8"), ("type", "<u4"), ("reserved", "<u4")]  # gzpx_
 WHERE_MAX_TERMS = 32             # GZPX_WHERE_MAX_TERMS
 WHERE_LT, WHERE_LE, WHERE_EQ, WHERE_NE, WHERE_GE, WHERE_GT, WHERE_IS_OK, WHERE_NOT_OK = range(8)  # GZPX_WHERE_*: a term's op
 WHERE_ANY, WHERE_INVERT = 1, 2   # GZPX_WHERE_ANY, GZPX_WHERE_INVERT: flags
+COL_TEXT = 2                     # GZPX_COL_TEXT: gzpx_where_text_device's terms only
+WHERE_PREFIX, WHERE_NOT_PREFIX = 8, 9  # GZPX_WHERE_PREFIX, GZPX_WHERE_NOT_PREFIX: ops of TEXT terms
+WHERE_TEXT_MAX = 64              # GZPX_WHERE_TEXT_MAX: the bytes of one constant
+WHERE_TEXT_POOL_MAX = 2048       # GZPX_WHERE_TEXT_POOL_MAX
 WHERE_TERM_DTYPE = [("field", "<u8"), ("type", "<u4"), ("op", "<u4"), ("value", "<u8")]  # gzpx_where_term, as a numpy record
 
 EXPORTS = [
@@ -101,6 +105,7 @@ EXPORTS = [
     "gzpx_read_fields_device", "gzpx_read_fields_table_device", "gzpx_dctx_last_fields_ms",
     "gzpx_read_columns_device", "gzpx_read_columns_table_device", "gzpx_dctx_last_columns_ms",
     "gzpx_where_lines_device", "gzpx_where_lines_table_device", "gzpx_dctx_last_where_ms",
+    "gzpx_where_text_device", "gzpx_where_text_table_device",
 ]
 
 
@@ -340,6 +345,10 @@ class GzpxLib:
             fn.restype = i32
             fn.argtypes = [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint, vp, sz, ctypes.c_uint, vp, sz, pu64, pu64, pu64, pu64, psz,
                            ctypes.POINTER(GzpxCheckInfo), vp]
+        for fn in (L.gzpx_where_text_device, L.gzpx_where_text_table_device):
+            fn.restype = i32
+            fn.argtypes = [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint, vp, sz, vp, sz, ctypes.c_uint, vp, sz, pu64, pu64, pu64, pu64,
+                           psz, ctypes.POINTER(GzpxCheckInfo), vp]
         L.gzpx_dctx_last_where_ms.restype = i32
         L.gzpx_dctx_last_where_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gzpx_inflate_batch_device.restype = i32
@@ -1304,13 +1313,40 @@ class DContext:
             tm[i] = (field, kind, op, bits)
         return tm
 
+    @staticmethod
+    def where_text_terms(terms):
+        """`terms` as (gzpx_where_term records, the pool of constants): (field, COL_*, WHERE_*, value), the value of a COL_TEXT
+        term a bytes object (None or b"" for IS_OK / NOT_OK), of the others as for where_terms.  A constant that the pool
+        already holds is not added again."""
+        tm = np.zeros(len(terms), dtype=WHERE_TERM_DTYPE)
+        pool = bytearray()
+        for i, (field, kind, op, value) in enumerate(terms):
+            if kind != COL_TEXT:
+                tm[i] = DContext.where_terms([(field, kind, op, value)])[0]
+            elif op in (WHERE_IS_OK, WHERE_NOT_OK):
+                if value:
+                    raise ValueError("IS_OK and NOT_OK take no constant")
+                tm[i] = (field, kind, op, 0)
+            else:
+                value = bytes(value)
+                at = pool.find(value)
+                if at < 0:
+                    at = len(pool)
+                    pool += value
+                tm[i] = (field, kind, op, at | len(value) << 32)
+        return tm, bytes(pool)
+
     def _where_lines(self, fn, index, lines, d_in_ptr, in_len, ranges_ptr, n_ranges, field_delim, terms, any, invert, d_runs_ptr,
-                     runs_cap, stream):
-        tm = self.where_terms(terms)
+                     runs_cap, stream, text=False):
+        if text:
+            tm, pool = self.where_text_terms(terms)
+            extra = (pool if pool else None, len(pool))
+        else:
+            tm, extra = self.where_terms(terms), ()
         runs, selected, rows, not_ok, bad = (ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0),
                                              ctypes.c_size_t(0))
         info = GzpxCheckInfo()
-        rc = fn(self.h, index.h, lines.h, d_in_ptr, in_len, ranges_ptr, n_ranges, int(field_delim), tm.ctypes.data, tm.shape[0],
+        rc = fn(self.h, index.h, lines.h, d_in_ptr, in_len, ranges_ptr, n_ranges, int(field_delim), tm.ctypes.data, tm.shape[0], *extra,
                 (WHERE_ANY if any else 0) | (WHERE_INVERT if invert else 0), d_runs_ptr, runs_cap, ctypes.byref(runs),
                 ctypes.byref(selected), ctypes.byref(rows), ctypes.byref(not_ok), ctypes.byref(bad), ctypes.byref(info), stream)
         if rc == OK:
@@ -1342,6 +1378,24 @@ class DContext:
         select_lines_device wrote, for one)."""
         return self._where_lines(self.lib.L.gzpx_where_lines_table_device, index, lines, d_in_ptr, in_len, d_line_ranges_ptr,
                                  n_ranges, field_delim, terms, any, invert, d_runs_ptr, runs_cap, stream)
+
+    def where_text_device(self, index, lines, d_in_ptr, in_len, line_ranges, field_delim, terms, any=False, invert=False,
+                          d_runs_ptr=None, runs_cap=0, stream=None):
+        """where_lines_device with terms on the TEXT of fields as well: a term may be (field number, COL_TEXT, WHERE_* |
+        WHERE_PREFIX | WHERE_NOT_PREFIX, bytes of at most WHERE_TEXT_MAX), compared with the field's bytes as Python
+        compares bytes; a field that the line does not have fails every op but WHERE_NOT_OK.  awk '$1 == "chr7" && $7 ==
+        "PASS" && $6 >= 30' is [(0, COL_TEXT, WHERE_EQ, b"chr7"), (5, COL_FLOAT64, WHERE_GE, 30.0), (6, COL_TEXT, WHERE_EQ,
+        b"PASS")].  Everything else, the return value and the errors are where_lines_device's."""
+        r = np.ascontiguousarray(np.asarray(line_ranges, dtype=np.uint64).reshape(-1, 2))
+        return self._where_lines(self.lib.L.gzpx_where_text_device, index, lines, d_in_ptr, in_len, r.ctypes.data, r.shape[0],
+                                 field_delim, terms, any, invert, d_runs_ptr, runs_cap, stream, text=True)
+
+    def where_text_table_device(self, index, lines, d_in_ptr, in_len, d_line_ranges_ptr, n_ranges, field_delim, terms, any=False,
+                                invert=False, d_runs_ptr=None, runs_cap=0, stream=None):
+        """where_text_device with its line ranges in device memory, as where_lines_table_device: "CHROM in {a, b, c} and QUAL
+        >= 30" is an `any` call on CHROM whose table this call takes with the term on QUAL."""
+        return self._where_lines(self.lib.L.gzpx_where_text_table_device, index, lines, d_in_ptr, in_len, d_line_ranges_ptr,
+                                 n_ranges, field_delim, terms, any, invert, d_runs_ptr, runs_cap, stream, text=True)
 
     def last_where_ms(self):
         """HIP-event durations of the last where_lines call's stages behind the search: (carries + row scan, parse with the

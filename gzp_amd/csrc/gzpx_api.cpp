@@ -1686,7 +1686,7 @@ struct WhereState : NoCopy {
     bool have = false;  // ev holds the last call's stages
     WhereScratch wh;
     ClCols *h_cols = nullptr;     // pinned: the distinct fields on their way in
-    WhTerms *h_terms = nullptr;   // pinned: the compiled terms on their way in
+    WhTextTerms *h_terms = nullptr;  // pinned: the compiled terms on their way in
     uint64_t *h_rec = nullptr;    // pinned: the record on its way out
     Allocs once;                  // wh.cl.cols, wh.cl.rec, wh.cl.fl.rec, wh.terms, wh.rec and the three pinned arrays above
     size_t range_cap = 0, piece_cap = 0, bit_cap = 0;
@@ -1700,9 +1700,9 @@ struct WhereState : NoCopy {
             GZPX_TRY(once.dev(cl.cols, sizeof(ClCols)));
             GZPX_TRY(once.dev(cl.fl.rec, kFlRecWords * 8));
             GZPX_TRY(once.dev(cl.rec, kClRecWords * 8));
-            GZPX_TRY(once.dev(wh.terms, sizeof(WhTerms)));
+            GZPX_TRY(once.dev(wh.terms, sizeof(WhTextTerms)));
             GZPX_TRY(once.pinned(h_cols, sizeof(ClCols)));
-            GZPX_TRY(once.pinned(h_terms, sizeof(WhTerms)));
+            GZPX_TRY(once.pinned(h_terms, sizeof(WhTextTerms)));
             GZPX_TRY(once.pinned(h_rec, kWhRecWords * 8));
             for (Event &e : ev) GZPX_TRY(e.create(true));
             GZPX_TRY(once.dev(wh.rec, kWhRecWords * 8));
@@ -3193,26 +3193,40 @@ int gzpx_dctx_last_columns_ms(gzpx_dctx *ctx, float ms[2]) {
 // ---------------------------------------------------------------- selection of lines by their numbers (gzpx_where.h)
 namespace {
 
-// The terms as the kernels take them: the distinct fields as a column list, and the terms grouped by column.  False:
-// they break a rule of gzpx.h.
-bool where_compile(const gzpx_where_term *terms, size_t n_terms, unsigned flags, ClCols &list, WhTerms &t) {
+// The terms as the kernels take them: the distinct fields as a column list, the terms grouped by column, and the pool of
+// the TEXT terms' constants as the caller gave it.  `with_text` false (gzpx_where_lines_device): a TEXT term and the two
+// prefix ops break the rules like any unknown code.  *has_text: a term is on a TEXT column.  False: they break a rule of
+// gzpx.h.
+bool where_compile(const gzpx_where_term *terms, size_t n_terms, unsigned flags, const void *text, size_t text_len, bool with_text,
+                   ClCols &list, WhTextTerms &tt, bool *has_text) {
     static_assert(kWhMaxTerms == GZPX_WHERE_MAX_TERMS && kWhLt == GZPX_WHERE_LT && kWhLe == GZPX_WHERE_LE && kWhEq == GZPX_WHERE_EQ &&
                       kWhNe == GZPX_WHERE_NE && kWhGe == GZPX_WHERE_GE && kWhGt == GZPX_WHERE_GT && kWhIsOk == GZPX_WHERE_IS_OK &&
-                      kWhNotOk == GZPX_WHERE_NOT_OK,
-                  "the public constants state the kernels' limit and codes");
+                      kWhNotOk == GZPX_WHERE_NOT_OK && kWhPrefix == GZPX_WHERE_PREFIX && kWhNotPrefix == GZPX_WHERE_NOT_PREFIX &&
+                      kClText == GZPX_COL_TEXT && kWhTextMax == GZPX_WHERE_TEXT_MAX && kWhPoolMax == GZPX_WHERE_TEXT_POOL_MAX &&
+                      GZPX_WHERE_TEXT_MAX == GZPX_CELL_MAX_BYTES,
+                  "the public constants state the kernels' limits and codes");
+    WhTerms &t = tt.t;
+    *has_text = false;
     if (!terms || n_terms == 0 || n_terms > kWhMaxTerms || (flags & ~(GZPX_WHERE_ANY | GZPX_WHERE_INVERT))) return false;
+    if (text_len > kWhPoolMax || (!text && text_len) || (!with_text && text_len)) return false;
     for (size_t i = 0; i < kClMaxCols; i++) {
         list.field[i] = UINT64_MAX;
         list.type[i] = 0;
     }
-    memset(&t, 0, sizeof t);
+    memset(&tt, 0, offsetof(WhTextTerms, pool));
     uint32_t n = 0;  // distinct fields so far
     for (size_t i = 0; i < n_terms; i++) {
         const gzpx_where_term &m = terms[i];
-        if (m.type != GZPX_COL_INT64 && m.type != GZPX_COL_FLOAT64) return false;
-        if (m.op > GZPX_WHERE_NOT_OK) return false;
+        const bool is_text = with_text && m.type == GZPX_COL_TEXT;
+        if (m.type != GZPX_COL_INT64 && m.type != GZPX_COL_FLOAT64 && !is_text) return false;
+        if (m.op > (is_text ? GZPX_WHERE_NOT_PREFIX : GZPX_WHERE_NOT_OK)) return false;  // (the prefix ops: on TEXT alone)
         const bool status_op = m.op == GZPX_WHERE_IS_OK || m.op == GZPX_WHERE_NOT_OK;
         if (status_op && m.value) return false;
+        if (is_text && !status_op) {  // the constant text[offset, offset + len)
+            const uint64_t off = m.value & 0xFFFFFFFFull, len = m.value >> 32;
+            if (len > kWhTextMax || off + len > text_len) return false;
+        }
+        if (is_text) *has_text = true;
         if (!status_op && m.type == GZPX_COL_FLOAT64 && (m.value & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return false;  // a NaN
         if (i && terms[i - 1].field > m.field) return false;
         if (i && terms[i - 1].field == m.field) {
@@ -3228,19 +3242,23 @@ bool where_compile(const gzpx_where_term *terms, size_t n_terms, unsigned flags,
     }
     for (uint32_t c = n; c <= kClMaxCols; c++) t.first[c] = (uint32_t)n_terms;
     t.any = (flags & GZPX_WHERE_ANY) ? 1u : 0u;
+    tt.pool_len = *has_text ? (uint32_t)text_len : 0u;
+    if (tt.pool_len) memcpy(tt.pool, text, text_len);
     list.n = n;
     list.pad = 0;
     return true;
 }
 
-// gzpx_where_lines_device, and with `on_device` gzpx_where_lines_table_device: line_ranges is then a device array.  The
+// gzpx_where_lines_device and gzpx_where_text_device (`with_text`: TEXT terms and their pool of constants are allowed),
+// and with `on_device` their table forms: line_ranges is then a device array.  The
 // line search of read_lines, then the carries of gzpx_fields.h, the rows of gzpx_columns.h, the parse with the predicate
 // and the runs of gzpx_where.h, enqueued together; one record comes back.  The bitmaps are sized by a bound on the rows
 // that the host knows: the rows themselves in the host form, the ranges' bytes in the table form.
 int where_lines(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
                 const gzpx_range *line_ranges, bool on_device, size_t n_ranges, unsigned field_delim, const gzpx_where_term *terms,
-                size_t n_terms, unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_selected,
-                uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
+                size_t n_terms, unsigned flags, const void *text, size_t text_len, bool with_text, gzpx_range *d_runs, size_t runs_cap,
+                uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info,
+                void *hip_stream) {
     if (!c || !ix || !lt || !n_runs || !n_selected || !n_rows || (!line_ranges && n_ranges) || (!d_in && in_len))
         return GZPX_ERR_INVALID_ARG;
     *n_runs = *n_selected = *n_rows = 0;
@@ -3254,8 +3272,9 @@ int where_lines(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, cons
     if (!lines_match(c, ix, lt, in_len) || n_ranges > 0x7FFFFFF0ull) return GZPX_ERR_INVALID_ARG;
     if (field_delim > 255u || field_delim == lt->delim || ((uintptr_t)d_runs & 7u)) return GZPX_ERR_INVALID_ARG;
     ClCols list;
-    WhTerms compiled;
-    if (!where_compile(terms, n_terms, flags, list, compiled)) return GZPX_ERR_INVALID_ARG;
+    WhTextTerms compiled;
+    bool has_text;
+    if (!where_compile(terms, n_terms, flags, text, text_len, with_text, list, compiled, &has_text)) return GZPX_ERR_INVALID_ARG;
     if (n_ranges == 0) return GZPX_OK;
     if (hipSetDevice(c->device) != hipSuccess) return GZPX_ERR_DEVICE;
     const int si = free_slot(c, lk, true);  // (stays free: the call returns synchronised under the lock)
@@ -3281,15 +3300,17 @@ int where_lines(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, cons
     const uint64_t cap = d_runs ? runs_cap : 0;
     const int invert = ((flags & GZPX_WHERE_ANY) ? 0 : 1) ^ ((flags & GZPX_WHERE_INVERT) ? 1 : 0);  // without ANY the bits say "rejected"
     *f.h_cols = list;
-    *f.h_terms = compiled;
+    // (the terms, and with TEXT terms the pool's bytes in use behind them)
+    const size_t terms_bytes = has_text ? offsetof(WhTextTerms, pool) + ((compiled.pool_len + 3u) & ~(size_t)3u) : sizeof(WhTerms);
+    memcpy(f.h_terms, &compiled, offsetof(WhTextTerms, pool) + compiled.pool_len);
     HIP_TRY(hipMemcpyAsync(cl.cols, f.h_cols, sizeof(ClCols), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(f.wh.terms, f.h_terms, sizeof(WhTerms), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(f.wh.terms, f.h_terms, terms_bytes, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(f.ev[0], stream));
     launch_fields_carry(c->stage.d, (uint32_t)n_ranges, rr, cl.fl, lt->delim, field_delim, (uint32_t)grid, stream);
     launch_columns_rows(c->stage.d, (uint32_t)n_ranges, rr, c->lines.ln, cl, lt->delim, field_delim, (uint32_t)grid, cl.row_off, stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(f.ev[1], stream));
-    launch_where_parse(c->stage.d, (uint32_t)n_ranges, rr, f.wh, lt->delim, field_delim, (uint32_t)grid, cl.row_off, bits, stream);
+    launch_where_parse(c->stage.d, (uint32_t)n_ranges, rr, f.wh, lt->delim, field_delim, (uint32_t)grid, cl.row_off, bits, has_text, stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(f.ev[2], stream));
     launch_where_runs((uint32_t)n_ranges, c->lines.ln, f.wh, cl.row_off, bits, invert, (uint64_t *)d_runs, cap, stream);
@@ -3316,8 +3337,8 @@ int gzpx_where_lines_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlin
                             size_t n_terms, unsigned flags, gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs,
                             uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info,
                             void *hip_stream) {
-    return where_lines(c, ix, lt, d_in, in_len, line_ranges, false, n_ranges, field_delim, terms, n_terms, flags, d_runs, runs_cap,
-                       n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
+    return where_lines(c, ix, lt, d_in, in_len, line_ranges, false, n_ranges, field_delim, terms, n_terms, flags, nullptr, 0, false,
+                       d_runs, runs_cap, n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
 }
 
 int gzpx_where_lines_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
@@ -3325,8 +3346,26 @@ int gzpx_where_lines_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzp
                                   const gzpx_where_term *terms, size_t n_terms, unsigned flags, gzpx_range *d_runs, size_t runs_cap,
                                   uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range,
                                   gzpx_check_info *info, void *hip_stream) {
-    return where_lines(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, field_delim, terms, n_terms, flags, d_runs, runs_cap,
-                       n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
+    return where_lines(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, field_delim, terms, n_terms, flags, nullptr, 0, false,
+                       d_runs, runs_cap, n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
+}
+
+int gzpx_where_text_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                           const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_where_term *terms,
+                           size_t n_terms, const void *text, size_t text_len, unsigned flags, gzpx_range *d_runs, size_t runs_cap,
+                           uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range,
+                           gzpx_check_info *info, void *hip_stream) {
+    return where_lines(c, ix, lt, d_in, in_len, line_ranges, false, n_ranges, field_delim, terms, n_terms, flags, text, text_len, true,
+                       d_runs, runs_cap, n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
+}
+
+int gzpx_where_text_table_device(gzpx_dctx *c, const gzpx_dindex *ix, const gzpx_dlines *lt, const void *d_in, size_t in_len,
+                                 const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim,
+                                 const gzpx_where_term *terms, size_t n_terms, const void *text, size_t text_len, unsigned flags,
+                                 gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows,
+                                 uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info, void *hip_stream) {
+    return where_lines(c, ix, lt, d_in, in_len, d_line_ranges, true, n_ranges, field_delim, terms, n_terms, flags, text, text_len, true,
+                       d_runs, runs_cap, n_runs, n_selected, n_rows, n_not_ok, bad_range, info, hip_stream);
 }
 
 int gzpx_dctx_last_where_ms(gzpx_dctx *ctx, float ms[3]) {

@@ -28,6 +28,11 @@
 // THE SINK.  What happens to a cell is a type parameter of the walk (cl_parse<Sink>): ClStore keeps it in the arrays,
 // gzpx_where.h's sink tests it against the terms of its column and keeps nothing.  cl_int, cl_float, cl_open, cl_close
 // and the walk itself are the same code for both, so a cell cannot be parsed differently by the two calls.
+//
+// TEXT COLUMNS.  A sink with kText set may list columns of type kClText (gzpx_where_text_device).  cl_open finds such a
+// field's extent like any other, skips both parsers and hands the sink the bytes in LDS and their number, capped at
+// kClMaxBytes + 1: 65 says "longer than 64", which is all a constant of at most 64 bytes has to know.  The cell is OK
+// whatever it holds; cl_close stores MISSING for it like for the others.  Sinks without kText compile as they did.
 
 constexpr uint32_t kClStageWords = kFlPiece / 16u + (kClOverhang + 15u) / 16u + 1u;
 static_assert(kClOverhang >= kClMaxBytes + 1u, "a field opened by a piece's last byte is parsed from LDS");
@@ -152,23 +157,27 @@ struct ClWalk {
 
 // the sink of gzpx_read_columns_device: the cell and its status byte into the arrays
 struct ClStore {
+    static constexpr bool kText = false;  // no column of type kClText (cols_compile)
     uint64_t *values;
     uint8_t *status;
     uint64_t rows_cap;
     // every piece leaves at once when an array is given and the rows do not fit
     __device__ __forceinline__ bool leaves(uint64_t rows) const { return (values || status) && rows > rows_cap; }
-    __device__ __forceinline__ void operator()(const ClWalk &, uint32_t c, uint64_t row, uint64_t bits, uint32_t st) const {
+    __device__ __forceinline__ void operator()(const ClWalk &, uint32_t c, uint64_t row, uint64_t bits, uint32_t st, const uint8_t *,
+                                               uint32_t) const {
         const uint64_t at = (uint64_t)c * rows_cap + row;
         if (values) values[at] = bits;
         if (status) status[at] = (uint8_t)st;
     }
 };
 
+// (b, len: the field's bytes in LDS and their number capped at kClMaxBytes + 1; null and 0 for MISSING)
 template <class Sink>
-__device__ __forceinline__ void cl_store(const ClWalk &k, const Sink &sink, uint32_t c, uint64_t row, uint64_t bits, uint32_t st) {
+__device__ __forceinline__ void cl_store(const ClWalk &k, const Sink &sink, uint32_t c, uint64_t row, uint64_t bits, uint32_t st,
+                                         const uint8_t *b, uint32_t len) {
     if (row >= k.row_end) return;
     if (st != kClOk) atomicAdd(&k.bad[c], 1u);
-    sink(k, c, row, bits, st);
+    sink(k, c, row, bits, st, b, len);
 }
 
 // the field of number f that starts at address s, in row `row`
@@ -186,6 +195,12 @@ __device__ __forceinline__ void cl_open(const ClWalk &k, const Sink &sink, uint6
     const uint32_t room = k.end - s < kClMaxBytes + 1u ? (uint32_t)(k.end - s) : kClMaxBytes + 1u;
     uint32_t len = 0;
     while (len < room && b[len] != k.fdelim && b[len] != k.delim) len++;
+    if constexpr (Sink::kText) {
+        if (k.type[lo] == kClText) {  // the bytes are the value: any length, any byte
+            cl_store(k, sink, lo, row, 0u, kClOk, b, len);
+            return;
+        }
+    }
     const bool is_int = k.type[lo] == 0u;
     uint64_t bits = is_int ? 0u : kClNaN;
     uint32_t st;
@@ -193,7 +208,7 @@ __device__ __forceinline__ void cl_open(const ClWalk &k, const Sink &sink, uint6
     else if (len > kClMaxBytes) st = kClInvalid;
     else st = is_int ? cl_int(b, len, &bits) : cl_float(b, len, &bits);
     if (st != kClOk) bits = is_int ? 0u : kClNaN;
-    cl_store(k, sink, lo, row, bits, st);
+    cl_store(k, sink, lo, row, bits, st, b, len);
 }
 
 // a line of F fields ends in row `row`
@@ -201,7 +216,7 @@ template <class Sink>
 __device__ __forceinline__ void cl_close(const ClWalk &k, const Sink &sink, uint64_t F, uint64_t row) {
     if (F > k.hi) return;
     for (uint32_t c = k.n; c > 0u && k.field[c - 1u] >= F; c--)
-        cl_store(k, sink, c - 1u, row, k.type[c - 1u] == 0u ? 0u : kClNaN, kClMissing);
+        cl_store(k, sink, c - 1u, row, k.type[c - 1u] == 0u ? 0u : kClNaN, kClMissing, nullptr, 0u);
 }
 
 // Workgroup x: rcnt[x] = the line delimiters of piece x.

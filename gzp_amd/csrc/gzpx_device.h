@@ -7,6 +7,7 @@
 // inside its payload (libdeflate starts a new one every 8192 matches); a *token* is one
 // literal or one match of the level-1 greedy parse.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace gzpx {
@@ -499,11 +500,26 @@ struct WhTerms {
     uint32_t first[kClMaxCols + 1u];
     uint32_t any;  // 1: a cell that makes a term TRUE marks its row; 0: one that makes a term FALSE does
 };
+// Terms on the TEXT of a field (gzpx_where_text_device).  A TEXT column's cell is the field's bytes where the walk staged
+// them; a TEXT term's value is offset | len << 32 into the pool of constants.  A constant of c <= kWhTextMax bytes is
+// decided by the field's first c + 1 bytes, which kClOverhang keeps in LDS behind the piece whatever byte opens the field.
+constexpr uint32_t kClText = 2;         // GZPX_COL_TEXT
+constexpr uint32_t kWhTextMax = 64;     // GZPX_WHERE_TEXT_MAX
+constexpr uint32_t kWhPoolMax = 2048;   // GZPX_WHERE_TEXT_POOL_MAX
+enum { kWhPrefix = 8, kWhNotPrefix = 9 };  // GZPX_WHERE_PREFIX, GZPX_WHERE_NOT_PREFIX
+static_assert(kWhTextMax == kClMaxBytes && kClOverhang >= kWhTextMax + 1u && kWhPoolMax == kWhMaxTerms * kWhTextMax,
+              "a constant is decided inside the overhang; every term may bring a constant of its own");
+struct WhTextTerms {
+    WhTerms t;          // (first: the numeric-only parse reads this much and no more)
+    uint32_t pool_len;  // the bytes of the pool in use
+    uint32_t pad;
+    uint8_t pool[kWhPoolMax];
+};
 // the record (u64 words): runs, selected rows, rows, cells that are not OK
 enum { kWhRecRuns = 0, kWhRecSelected = 1, kWhRecRows = 2, kWhRecNotOk = 3, kWhRecWords = 4 };
 struct WhereScratch {
     ColumnsScratch cl;           // the columns' stages: every member but the arrays of cells
-    WhTerms *terms = nullptr;    // the compiled terms
+    WhTextTerms *terms = nullptr;  // the compiled terms (its head is the WhTerms of a call without TEXT terms)
     uint32_t *bitmap = nullptr;  // [bits / 32] bit i: a cell of row i decided its row (rejected it, or under ANY accepted it)
     uint32_t *starts = nullptr;  // [bits / 32] bit i: row i is the first of its range; it lies behind bitmap, one memset clears both
     uint32_t *cnt = nullptr;     // [2 * groups] (rising edges, set bits) of every kSlRunRecords rows
@@ -513,9 +529,9 @@ struct WhereScratch {
 // the bits of a bitmap that serves `bound` rows: whole groups of the runs kernels
 inline uint64_t where_bits(uint64_t bound) { return select_groups(bound) * kSlRunRecords; }
 // behind launch_columns_rows on w.cl: both bitmaps cleared (`bits` = where_bits()), then the parse with the predicate;
-// nothing is marked when the record's rows exceed `bits`
+// nothing is marked when the record's rows exceed `bits`.  `text`: a term is on a TEXT column, and w.terms holds the pool.
 void launch_where_parse(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const WhereScratch &w, uint32_t delim,
-                        uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t bits, hipStream_t stream);
+                        uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t bits, bool text, hipStream_t stream);
 // behind it: w.rec, and the runs below rank `cap` into d_runs (null: counts only) as (begin, end) pairs of line numbers.
 // `invert`: the selected rows are those whose bit is clear.  l.bounds holds the (begin, end) line numbers of the ranges.
 void launch_where_runs(uint32_t n_ranges, const LinesScratch &l, const WhereScratch &w, const uint64_t *d_row_off, uint64_t bits,

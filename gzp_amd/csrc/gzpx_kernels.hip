@@ -6013,12 +6013,18 @@ void launch_columns_parse(const uint8_t *d_stage, uint32_t n_ranges, const Range
 // Selection of lines by their numbers (gzpx_where.h), behind launch_columns_rows on w.cl: the parse with the predicate,
 // then the runs.  The rows are known on the device only: `bits` sizes the bitmaps and bounds the grids.
 void launch_where_parse(const uint8_t *d_stage, uint32_t n_ranges, const RangeScratch &r, const WhereScratch &w, uint32_t delim,
-                        uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t bits, hipStream_t stream) {
+                        uint32_t field_delim, uint32_t grid, const uint64_t *d_row_off, uint64_t bits, bool text, hipStream_t stream) {
     (void)hipMemsetAsync(w.bitmap, 0, (size_t)(bits / 8u) * 2u, stream);  // (w.starts lies behind w.bitmap)
-    if (grid)
-        hipLaunchKernelGGL(k_wh_parse, dim3(grid), dim3(kFlThreads), 0, stream, fields_args(d_stage, n_ranges, r, w.cl.fl, delim, field_delim),
-                           (const ClCols *)w.cl.cols, (const WhTerms *)w.terms, (const uint64_t *)w.cl.fl.cin, (const uint64_t *)w.cl.rin,
-                           d_row_off, w.cl.rec, w.bitmap, bits);
+    if (!grid) return;
+    const FlArgs a = fields_args(d_stage, n_ranges, r, w.cl.fl, delim, field_delim);
+    if (text)
+        hipLaunchKernelGGL(k_wh_parse<true>, dim3(grid), dim3(kFlThreads), 0, stream, a, (const ClCols *)w.cl.cols,
+                           (const WhTextTerms *)w.terms, (const uint64_t *)w.cl.fl.cin, (const uint64_t *)w.cl.rin, d_row_off, w.cl.rec,
+                           w.bitmap, bits);
+    else
+        hipLaunchKernelGGL(k_wh_parse<false>, dim3(grid), dim3(kFlThreads), 0, stream, a, (const ClCols *)w.cl.cols,
+                           (const WhTextTerms *)w.terms, (const uint64_t *)w.cl.fl.cin, (const uint64_t *)w.cl.rin, d_row_off, w.cl.rec,
+                           w.bitmap, bits);
 }
 
 void launch_where_runs(uint32_t n_ranges, const LinesScratch &l, const WhereScratch &w, const uint64_t *d_row_off, uint64_t bits,

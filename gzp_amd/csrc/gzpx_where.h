@@ -3,16 +3,21 @@
 // comparisons, as a table of line ranges in device memory that the reads by line, field and column take where it lies.
 // Included from gzpx_kernels.hip behind gzpx_columns.h, whose stages run as they are with the terms' distinct fields as
 // the column list; no cell is stored.  (Definitions and the truth of a term: include/gzpx.h.)
+// gzpx_where_text_device adds terms on the TEXT of a field -- awk '$1 == "chr7" && $7 == "PASS" && $6 >= 30' -- to the
+// same walk: a third cell type whose value is the field's bytes where they are staged, and a pool of constants.
 //
 // Behind k_fl_plan .. k_cl_rows_scan (cin, rin, row_off, the rows R in the columns' record):
 //
-//   k_wh_parse       cl_parse (gzpx_columns.h) with the sink WhSink: the lane that owns a cell -- the opener's, or for
+//   k_wh_parse<kText>  (false: terms on numbers alone, the code as it was; true: a term is on a TEXT column)
+//                    cl_parse (gzpx_columns.h) with the sink WhSink: the lane that owns a cell -- the opener's, or for
 //                    MISSING the lane that closes the line -- has it in registers, tests it against the terms of its
 //                    column (staged in LDS once per workgroup, like the column list) and sets the row's bit in the row
 //                    bitmap with at most one atomicOr, only when the cell DECIDES something: without ANY a cell that
 //                    makes a term false rejects its row, with ANY a cell that makes a term true accepts it.  Lanes of
 //                    two workgroups set bits of one word whenever a row runs through a piece boundary.  Rows at or
 //                    behind row_off[r + 1] set no bit (cl_store), and nothing is set when R exceeds the bitmap.
+//                    A TEXT cell is the field's bytes in LDS and their number capped at 65 (cl_open); the constants lie in
+//                    a pool of at most 2 KiB staged in LDS behind the terms, and wh_text compares a byte at a time.
 //   k_wh_starts      a lane a range: bit row_off[r] of a second bitmap for every range that is not empty.
 //   k_wh_runs_count  the bitmap a byte a lane, 64 bytes a workgroup, read inverted when the bits mean "rejected" (XOR
 //                    the caller's INVERT); sl_byte clears the bits at and behind R.  A run never leaves its range: the
@@ -65,30 +70,82 @@ __device__ __forceinline__ bool wh_term(uint32_t op, uint64_t value, bool is_int
     }
 }
 
-// the sink of gzpx_where_lines_device: the cell against the terms of its column
+// The truth of one term on a TEXT cell (include/gzpx.h): the field's bytes b[0, len) against the constant
+// pool[value & 0xFFFFFFFF, + value >> 32), both in LDS, a byte at a time (neither is aligned).  len is capped at
+// kClMaxBytes + 1 and the constant holds c <= kWhTextMax bytes, so min(len, c) bytes and then len against c decide
+// every op exactly: a capped length still exceeds every c.  No byte behind b[min(len, c)) is read.
+__device__ __forceinline__ bool wh_text(uint32_t op, uint64_t value, const uint8_t *pool, const uint8_t *b, uint32_t len, uint32_t st) {
+    const bool ok = st == kClOk;
+    if (op == kWhIsOk) return ok;
+    if (op == kWhNotOk) return !ok;
+    if (!ok) return false;  // MISSING: NE and NOT_PREFIX too
+    const uint8_t *k = pool + (uint32_t)value;
+    const uint32_t c = (uint32_t)(value >> 32), n = len < c ? len : c;
+    uint32_t i = 0;
+    while (i < n && b[i] == k[i]) i++;
+    bool lt, gt;
+    if (i < n) {
+        lt = b[i] < k[i];  // (unsigned bytes)
+        gt = !lt;
+    } else {
+        lt = len < c;  // the shorter first
+        gt = len > c;
+    }
+    switch (op) {
+        case kWhLt: return lt;
+        case kWhLe: return !gt;
+        case kWhEq: return !lt && !gt;
+        case kWhNe: return lt || gt;
+        case kWhGe: return !lt;
+        case kWhGt: return gt;
+        case kWhPrefix: return i == c;
+        default: return i != c;  // kWhNotPrefix
+    }
+}
+
+// the sink of gzpx_where_lines_device: the cell against the terms of its column.  kText: columns of type kClText may be
+// among them, and `pool` holds their constants.
+template <bool kTextColumns>
 struct WhSink {
-    const WhTerms *t;  // LDS
+    static constexpr bool kText = kTextColumns;
+    const WhTerms *t;     // LDS
+    const uint8_t *pool;  // LDS (kText)
     uint32_t *bitmap;
     uint64_t cap;  // its bits
     __device__ __forceinline__ bool leaves(uint64_t rows) const { return rows > cap; }
-    __device__ __forceinline__ void operator()(const ClWalk &k, uint32_t c, uint64_t row, uint64_t bits, uint32_t st) const {
+    __device__ __forceinline__ void operator()(const ClWalk &k, uint32_t c, uint64_t row, uint64_t bits, uint32_t st, const uint8_t *b,
+                                               uint32_t len) const {
         const bool is_int = k.type[c] == 0u, mark = t->any != 0u;
+        bool is_text = false;
+        if constexpr (kText) is_text = k.type[c] == kClText;
         bool decided = false;
         for (uint32_t i = t->first[c]; i < t->first[c + 1u] && !decided; i++)
-            decided = wh_term(t->op[i], t->value[i], is_int, bits, st) == mark;
+            decided = (is_text ? wh_text(t->op[i], t->value[i], pool, b, len, st) : wh_term(t->op[i], t->value[i], is_int, bits, st)) == mark;
         if (decided) atomicOr(&bitmap[row >> 5], 1u << (row & 31u));
     }
 };
 
-// The walk with the testing sink: the rows that a cell decides into the row bitmap.
-__global__ __launch_bounds__(kFlThreads) void k_wh_parse(FlArgs a, const ClCols *__restrict__ cols, const WhTerms *__restrict__ terms,
+// The walk with the testing sink: the rows that a cell decides into the row bitmap.  kText false is the parse of terms on
+// numbers alone and reads the WhTerms at the head of `terms`; kText true stages the pool's bytes in use behind it.
+template <bool kText>
+__global__ __launch_bounds__(kFlThreads) void k_wh_parse(FlArgs a, const ClCols *__restrict__ cols, const WhTextTerms *__restrict__ terms,
                                                          const uint64_t *__restrict__ cin, const uint64_t *__restrict__ rin,
                                                          const uint64_t *__restrict__ row_off, uint64_t *rec, uint32_t *bitmap,
                                                          uint64_t cap) {
     __shared__ ClLds l;
-    __shared__ WhTerms t;
-    if (threadIdx.x < sizeof(WhTerms) / 4u) ((uint32_t *)&t)[threadIdx.x] = ((const uint32_t *)terms)[threadIdx.x];
-    cl_parse(a, l, cols, cin, rin, row_off, rec, WhSink{&t, bitmap, cap});
+    if constexpr (kText) {
+        __shared__ WhTextTerms t;
+        constexpr uint32_t head = (uint32_t)offsetof(WhTextTerms, pool) / 4u;
+        static_assert(offsetof(WhTextTerms, pool) % 4u == 0 && head <= kFlThreads, "the head a dword a lane, the pool by a loop");
+        if (threadIdx.x < head) ((uint32_t *)&t)[threadIdx.x] = ((const uint32_t *)terms)[threadIdx.x];
+        const uint32_t words = ((terms->pool_len < kWhPoolMax ? terms->pool_len : kWhPoolMax) + 3u) / 4u;
+        for (uint32_t i = threadIdx.x; i < words; i += kFlThreads) ((uint32_t *)t.pool)[i] = ((const uint32_t *)terms->pool)[i];
+        cl_parse(a, l, cols, cin, rin, row_off, rec, WhSink<true>{&t.t, t.pool, bitmap, cap});
+    } else {
+        __shared__ WhTerms t;
+        if (threadIdx.x < sizeof(WhTerms) / 4u) ((uint32_t *)&t)[threadIdx.x] = ((const uint32_t *)terms)[threadIdx.x];
+        cl_parse(a, l, cols, cin, rin, row_off, rec, WhSink<false>{&t, nullptr, bitmap, cap});
+    }
 }
 
 // Lane r: the first row of range r, if it has one.  (Ranges in front of it that are empty share its row_off; atomicOr:

@@ -702,6 +702,54 @@ int gzpx_where_lines_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const g
                                   size_t runs_cap, uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok,
                                   size_t *bad_range, gzpx_check_info *info, void *hip_stream);
 int gzpx_dctx_last_where_ms(gzpx_dctx *ctx, float ms[3]);
+/* ---- selection of lines by the TEXT of their fields (gzpx_where.h): awk '$1 == "chr7" && $7 == "PASS" && $6 >= 30' --
+ * the query a VCF is really asked -- with the constant anchored to its field: "PASS" inside an INFO string selects
+ * nothing.  gzpx_where_lines_device and gzpx_where_lines_table_device are untouched: they still answer type 2 and ops 8
+ * and 9 with GZPX_ERR_INVALID_ARG, and gzpx_read_columns_device still refuses GZPX_COL_TEXT.
+ * Everything but the third cell type.  Lines, delimiters, line ranges and their validation, fields, the numeric cells,
+ *   rows, runs ("never leave their range", at most (R + n_ranges) / 2 of them), selected rows, ANY and INVERT, the
+ *   outputs, counts and capacity (count-only with d_runs == NULL, the first runs_cap runs and
+ *   GZPX_ERR_INSUFFICIENT_SPACE), *bad_range, the context's lock, the slot, hip_stream, "returns synchronised", both
+ *   inflate routes, the report of a failing member (all counts 0), the bound of 0xFFFFFFF0 rows and bit-reproducibility
+ *   are gzpx_where_lines_device's, word for word; the four calls are one function.  gzpx_where_term is unchanged.  With
+ *   numeric terms only the two calls give what gzpx_where_lines_device gives, from the same kernel.
+ * The pool.  `text` is a HOST array of text_len <= GZPX_WHERE_TEXT_POOL_MAX constant bytes (NULL when text_len is 0).
+ *   A TEXT term's `value` is offset | (uint64_t)len << 32: its constant is text[offset, offset + len), len <=
+ *   GZPX_WHERE_TEXT_MAX, offset + len <= text_len.  Constants may overlap or share bytes; they may hold any byte.
+ *   GZPX_WHERE_TEXT_MAX equals GZPX_CELL_MAX_BYTES for a reason: a constant of c bytes is decided by the field's first
+ *   c + 1 bytes, and the walk keeps 65 bytes behind whatever byte opens a field in fast memory -- the guarantee the
+ *   numeric cells already rest on.  The pool is 32 terms x 64 bytes.
+ * Terms.  The rules of gzpx_where_lines_device, and: `type` may be GZPX_COL_TEXT; `op` may be GZPX_WHERE_PREFIX or
+ *   GZPX_WHERE_NOT_PREFIX on a TEXT term (on a numeric type: GZPX_ERR_INVALID_ARG); IS_OK and NOT_OK take value 0 on
+ *   every type; all terms of one field agree in their type.  len > 64, offset + len > text_len, text_len above the
+ *   maximum, text == NULL with text_len > 0: GZPX_ERR_INVALID_ARG with nothing inflated and nothing written.
+ * A TEXT cell.  Field f of a line with F fields is MISSING when f >= F.  Otherwise it is OK and its value is the field's
+ *   bytes: of any length, 0 included (an empty field is the OK empty string), of any value ('\r' and NUL are ordinary
+ *   bytes).  EMPTY, INVALID and RANGE do not occur.  *n_not_ok counts the MISSING cells of TEXT fields together with the
+ *   numeric cells that are not OK.
+ * Truth of a TEXT term.  IS_OK / NOT_OK look at the status alone.  Every other op is FALSE on a MISSING cell, NE and
+ *   NOT_PREFIX included.  On an OK cell LT .. GT compare as unsigned bytes, memcmp over the common length and then the
+ *   shorter first: Python's ordering of bytes, LC_ALL=C string comparison for NUL-free text.  PREFIX: the field begins
+ *   with the constant (the empty constant: every OK cell).  NOT_PREFIX: it does not.
+ * Mixing and chaining.  INT64, FLOAT64 and TEXT terms mix freely in one call under ALL, ANY and INVERT.  "CHROM in {a, b,
+ *   c} AND QUAL >= 30" is two chained calls: three EQ terms on CHROM under GZPX_WHERE_ANY write a table, and
+ *   gzpx_where_text_table_device (or gzpx_where_lines_table_device) takes it with the term on QUAL.
+ * gzpx_dctx_last_where_ms, gzpx_dctx_last_lines_ms and gzpx_dctx_last_lines_members answer for these calls too. */
+#define GZPX_COL_TEXT 2
+#define GZPX_WHERE_PREFIX 8      /* TEXT only: the field begins with the constant */
+#define GZPX_WHERE_NOT_PREFIX 9  /* TEXT only: it does not (false on a MISSING cell) */
+#define GZPX_WHERE_TEXT_MAX 64   /* bytes of one constant; == GZPX_CELL_MAX_BYTES */
+#define GZPX_WHERE_TEXT_POOL_MAX 2048 /* bytes of the pool: GZPX_WHERE_MAX_TERMS x GZPX_WHERE_TEXT_MAX */
+int gzpx_where_text_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in, size_t in_len,
+                           const gzpx_range *line_ranges, size_t n_ranges, unsigned field_delim, const gzpx_where_term *terms,
+                           size_t n_terms, const void *text, size_t text_len, unsigned flags, gzpx_range *d_runs, size_t runs_cap,
+                           uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows, uint64_t *n_not_ok, size_t *bad_range,
+                           gzpx_check_info *info, void *hip_stream);
+int gzpx_where_text_table_device(gzpx_dctx *ctx, const gzpx_dindex *ix, const gzpx_dlines *lines, const void *d_in,
+                                 size_t in_len, const gzpx_range *d_line_ranges, size_t n_ranges, unsigned field_delim,
+                                 const gzpx_where_term *terms, size_t n_terms, const void *text, size_t text_len, unsigned flags,
+                                 gzpx_range *d_runs, size_t runs_cap, uint64_t *n_runs, uint64_t *n_selected, uint64_t *n_rows,
+                                 uint64_t *n_not_ok, size_t *bad_range, gzpx_check_info *info, void *hip_stream);
 /* ---- search for a SET of byte strings (gzpx_findset.h): grep -F -e A -e B -f list on a device-resident BGZF / Mgzip
  * stream -- the VCF rows of a handful of contigs, the FASTQ records that carry any of 96 barcodes, the log lines with
  * any of a list of error codes -- in ONE inflate and one pass over it, the hits of all patterns already merged by

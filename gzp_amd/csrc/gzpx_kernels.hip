@@ -1152,16 +1152,19 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     // One workgroup per CU (the LDS is its alone), walking the blocks blockIdx.x, + gridDim.x, ...: while it
-    // parses a block, the NEXT block's bytes and first-pass d0 are already on their way into registers, so
-    // the CU waits for HBM once per launch instead of once per block (17 k of a block's 142 k cycles were
-    // that wait when every block was a workgroup of its own).
+    // parses a block, the NEXT block's bytes (requested at the top of the block) and first-pass d0 (requested behind
+    // the last pass's walks) are on their way into registers, so the CU waits for HBM once per launch instead of
+    // once per block (17 k of a block's 142 k cycles were that wait when every block was a workgroup of its own).
+    // Where the kernel waits for them is written down, not left to the compiler: its own place for the wait is the
+    // ds_write that stages the registers at the turn of a pass or a block, and there the wait also drains the token
+    // stores issued since (loads and stores share one counter, and every wave stood still for their acknowledgement).
     auto block_len = [&](uint32_t blk) -> uint32_t {  // k_init_meta's cut
         const uint64_t begin = (uint64_t)blk * cfg.block_size;
         const uint64_t len = slab_len > begin ? slab_len - begin : 0;
         return (uint32_t)(len > cfg.block_size ? cfg.block_size : len);
     };
     // d0 of a pass: 64 bytes per thread (the per-block stride is padded: whole uint4s are readable)
-    uint4 d0v0, d0v1, d0v2, d0v3;
+    uint4 d0v0 = make_uint4(0u, 0u, 0u, 0u), d0v1 = d0v0, d0v2 = d0v0, d0v3 = d0v0;
 #define GZPX_D0_REQUEST(cand_, hb_, n_)                                              \
     do {                                                                            \
         const uint32_t he_ = (hb_) + kMhHalf < (n_) ? (hb_) + kMhHalf : (n_);       \
@@ -1172,8 +1175,34 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
         d0v2 = src_[tid + 2 * kMpThreads < nq_ ? tid + 2 * kMpThreads : nq_ - 1];   \
         d0v3 = src_[tid + 3 * kMpThreads < nq_ ? tid + 3 * kMpThreads : nq_ - 1];   \
     } while (0)
+    // The request only issues the loads; GZPX_D0_ARRIVED is where the kernel waits for them: an empty statement that
+    // READS the registers (GZPX_HERE_VGPR), so the compiler puts its wait in front of it and knows them complete on
+    // every way on from there.  (A read, not GZPX_PIN_VGPR's read-and-write: a written operand is a new value, the
+    // register allocator then held the registers in a second set across the pass loop -- 113 to 127 VGPRs in the
+    // forms tried -- and the copies between the sets brought waits of their own.  And all four dwords as ONE
+    // 128-bit operand: the ds_write_b128 wants them as the tuple the load filled.)
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint32_t here4 __attribute__((ext_vector_type(4)));
+#define GZPX_HERE_UINT4(v_)                              \
+    do {                                                 \
+        const here4 t_ = {(v_).x, (v_).y, (v_).z, (v_).w}; \
+        GZPX_HERE_VGPR(t_);                              \
+    } while (0)
+#else
+#define GZPX_HERE_UINT4(v_) ((void)0)
+#endif
+    // (no next block: the registers still get a value, or the old one would stay alive, sixteen registers wide,
+    // through the walks up to the place that reads them)
+#define GZPX_D0_NONE() d0v0 = d0v1 = d0v2 = d0v3 = make_uint4(0u, 0u, 0u, 0u)
+#define GZPX_D0_ARRIVED()     \
+    do {                      \
+        GZPX_HERE_UINT4(d0v0); \
+        GZPX_HERE_UINT4(d0v1); \
+        GZPX_HERE_UINT4(d0v2); \
+        GZPX_HERE_UINT4(d0v3); \
+    } while (0)
     // a block's bytes (n <= kTile): four 16-byte loads per thread + one dword of tail for three threads
-    uint4 bv0, bv1, bv2, bv3;
+    uint4 bv0 = make_uint4(0u, 0u, 0u, 0u), bv1 = bv0, bv2 = bv0, bv3 = bv0;
     uint32_t bvt = 0;
     auto load16 = [](const dword4 *p4) -> uint4 {  // (a 16-byte load of a 4-byte-aligned address)
         const dword4 t = *p4;
@@ -1193,31 +1222,59 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
         bv3 = load16(src4_ + (tid + 3 * kMpThreads < nq_ ? tid + 3 * kMpThreads : last_)); \
         bvt = src_[4 * nq_ + tid < ndw_ ? 4 * nq_ + tid : ndw_ - 1];                \
     } while (0)
+#define GZPX_BLOCK_ARRIVED()  \
+    do {                     \
+        GZPX_HERE_UINT4(bv0); \
+        GZPX_HERE_UINT4(bv1); \
+        GZPX_HERE_UINT4(bv2); \
+        GZPX_HERE_UINT4(bv3); \
+        GZPX_HERE_VGPR(bvt);  \
+    } while (0)
     static_assert(((3 + kTile + 3) >> 4) <= 4 * kMpThreads, "a block is four uint4 per thread (+ tail dwords)");
 
     // Blocks are CLAIMED, not strided over (round 4): a workgroup's first two blocks are blockIdx.x and blockIdx.x +
     // gridDim.x, every later one comes from one global ticket counter -- the ticket for the block after the next is
-    // drawn while the current block is parsed, so its round trip is never waited for.  With the static stride
-    // (b += gridDim.x) 8,835 blocks over 256 CUs left 121 CUs idle for the last 35th of the launch, and a CU slowed
-    // by anything else on it (an RCCL channel, a heavier run of blocks) stretched the whole launch.
+    // drawn in the current block's last pass, beside the next block's d0 and in front of the same wait.  With the
+    // static stride (b += gridDim.x) 8,835 blocks over 256 CUs left 121 CUs idle for the last 35th of the launch, and
+    // a CU slowed by anything else on it (an RCCL channel, a heavier run of blocks) stretched the whole launch.
+    // (The counter's index goes through a VGPR: an atomic on a uniform address is rewritten by the compiler into a
+    // one-lane atomic whose result is broadcast at once, and the broadcast waits for the round trip where it stands.)
+    uint32_t my_ticket = 0;
+    auto draw_ticket = [&]() {
+        uint32_t slot = 0;
+        GZPX_PIN_VGPR(slot);
+        if (tid == 0) my_ticket = atomicAdd(claim + slot, 1u);
+    };
     uint32_t b = blockIdx.x;
     if (b >= nb) return;
     uint32_t next_b = b + gridDim.x;
-    bool staged;  // (uniform) block b's bytes and first-pass d0 have been requested
+    bool staged;  // (uniform) block b's bytes and first-pass d0 have been requested -- and have arrived
     {
         const uint32_t n0 = block_len(b);
         staged = n0 > cfg.passthrough;
         if (staged) {
             GZPX_D0_REQUEST(cand_all + (uint64_t)b * cfg.stride, 0u, n0);
             GZPX_BLOCK_REQUEST(b, n0);
+            GZPX_D0_ARRIVED();  // (the one HBM round trip a launch waits for)
+            GZPX_BLOCK_ARRIVED();
         }
     }
   for (;;) {
-    uint32_t my_ticket = 0;
-    if (tid == 0) my_ticket = atomicAdd(claim, 1u);  // (its value is looked at only at the end of this block)
     const uint32_t next_n = next_b < nb ? block_len(next_b) : 0u;
     const bool next_staged = next_n > cfg.passthrough;  // (uniform; implies next_b < nb)
-    bool next_d0_requested = false;
+    my_ticket = 0;
+    // A block that does not reach its last pass's token build (handed back, or stored-only) requests the next
+    // block's d0 and draws the ticket late, and waits for both on the spot, with the next block's bytes: every way to
+    // the top of a block leaves these registers finished, or the compiler would wait for them there, for all.
+#define GZPX_TURN_LATE()                                                                         \
+    do {                                                                                        \
+        if (next_staged) GZPX_D0_REQUEST(cand_all + (uint64_t)next_b * cfg.stride, 0u, next_n); \
+        else GZPX_D0_NONE();                                                                    \
+        draw_ticket();                                                                          \
+        GZPX_D0_ARRIVED();                                                                      \
+        GZPX_BLOCK_ARRIVED();                                                                   \
+        GZPX_HERE_VGPR(my_ticket);                                                               \
+    } while (0)
     BlockMeta *meta = meta_all + b;
     SubMeta *sub = sub_all + (uint64_t)b * cfg.max_sub;
     const uint32_t n = block_len(b);
@@ -1225,7 +1282,6 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
     const uint16_t *cand = cand_all + (uint64_t)b * cfg.stride;
     uint32_t *tok = tok_all + (uint64_t)b * cfg.stride;
     const uint32_t mis = (uint32_t)((uintptr_t)in & 3u);
-  if (staged) {  // (else: n <= cfg.passthrough, a stored-only block: nothing to parse)
 #ifdef GZPX_EXPERIMENT
     // measurement builds: cycles per phase, summed over the blocks of a launch (thread 0's clock)
     unsigned long long exp_t = __builtin_readcyclecounter();
@@ -1237,6 +1293,13 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
 #else
     auto exp_lap = [](uint32_t) {};
 #endif
+    // (A stored-only block -- !staged: n <= cfg.passthrough, nothing to parse -- takes the way of a block that is
+    // handed back in its first pass, without being put on the list: it stages what the registers hold (a few dwords
+    // nobody reads), walks nothing (no position has a candidate), meets the barriers -- without one, thread 0 could
+    // overwrite s_claimed while a slower wave has not read the previous iteration's value yet, ADVICE round 4 --
+    // requests its successor's bytes and leaves where the hand-back leaves.  Only a slab's last block can be that
+    // short today, but the parse must not depend on how batches are cut; and a way of its own to the top of the next
+    // block would be one more that has to leave the prefetch registers finished.)
     __syncthreads();  // the previous block is done with in_w
     {   // the block's bytes: registers -> LDS
         const uint32_t ndw = (mis + n + 3) >> 2;
@@ -1259,7 +1322,7 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
     const uint8_t *in_b = (const uint8_t *)in_w + mis;
 
     bool handed_back = false;
-    for (uint32_t hb = 0; hb < n; hb += kMhHalf) {
+    for (uint32_t hb = 0;; hb += kMhHalf) {  // (the last pass leaves below)
         const uint32_t he = hb + kMhHalf < n ? hb + kMhHalf : n;  // this pass: positions [hb, he)
         if (hb) __syncthreads();  // the previous pass is done with d0_w / seg_exit
         {
@@ -1282,13 +1345,8 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
             nz_b[tid + kMpThreads] = nz8(d0v1);
             nz_b[tid + 2 * kMpThreads] = nz8(d0v2);
             nz_b[tid + 3 * kMpThreads] = nz8(d0v3);
-            // (uniform) the next pass's d0 -- this block's, or the next block's first -- travels while this pass is walked
-            if (he < n) {
-                GZPX_D0_REQUEST(cand, he, n);
-            } else if (next_staged) {
-                GZPX_D0_REQUEST(cand_all + (uint64_t)next_b * cfg.stride, 0u, next_n);
-                next_d0_requested = true;
-            }
+            // (these registers arrived in the pass before, in front of its token build: nothing is waited for here,
+            // and that pass's token stores stay in flight across the turn)
         }
         __syncthreads();
         exp_lap(0);
@@ -1312,6 +1370,7 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
             if (n_srch < kMhSeg) nz &= (1u << n_srch) - 1u;
             if (seg_end - seg_begin < kMhSeg) nz |= ~0u << (seg_end - seg_begin);  // (inactive lanes never walk)
             if (cfg.debug & 8u) nz = ~0u;
+            if (!staged) nz = 0u;
         }
         // (whole waves take the TAIL form of the search together: the last wave of the block)
         const bool tail_wave = __ballot(active && seg_end + 266u > n) != 0;
@@ -1389,16 +1448,38 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
                 break;
             }
         }
-        if (!settled || (cfg.debug & 4u)) {  // uniform: the dense kernels take this block (debug bit 2: every block)
-            if (tid == 0) redo[1u + atomicAdd(&redo[0], 1u)] = b;
+        // The next block's bytes were requested at the top of this block, a first walk and its rounds ago: they are
+        // here.  Saying so in front of this branch covers every way the compiler sees from it to the top of the next
+        // block (it keeps one that goes round the hand-back's own wait, for no lane).
+        GZPX_BLOCK_ARRIVED();
+        if (!settled || (cfg.debug & 4u) || !staged) {  // uniform: the dense kernels take this block (debug bit 2: every block)
+            if (tid == 0 && staged) redo[1u + atomicAdd(&redo[0], 1u)] = b;
             handed_back = true;
+            GZPX_TURN_LATE();
             break;
         }
         const uint32_t n_seg = (he - hb + kMhSeg - 1) / kMhSeg;
         const uint32_t exit_pos = uniform(seg_exit[cur * kMpThreads + n_seg - 1]);  // where the parse leaves this pass
         exp_lap(3);
+        // (uniform) The next pass's d0 -- this block's, or the next block's first, and with that one the ticket -- is
+        // requested here, behind the walks (whose rare gather of an older candidate out of global memory waits for
+        // everything in flight) and waited for in front of the token build: the scan and the sub-block boundaries
+        // cover the round trip, and the only stores still counted there are those of the pass before.
+        const bool last_pass = he >= n;
+        // (one request whose operands are chosen, not one of two: the compiler keeps a way from the first of two
+        // into the second, and would have the second wait for the loads of the first)
+        {
+            const uint16_t *from = last_pass ? cand_all + (uint64_t)next_b * cfg.stride : cand;
+            const uint32_t from_hb = last_pass ? 0u : he, from_n = last_pass ? next_n : n;
+            if (!last_pass || next_staged) GZPX_D0_REQUEST(from, from_hb, from_n);
+            else GZPX_D0_NONE();
+            if (last_pass) draw_ticket();
+        }
         if (GZPX_EXP(cfg, 14)) {  // measurement: without the token build
+            GZPX_D0_ARRIVED();
+            GZPX_HERE_VGPR(my_ticket);
             entry_carry = exit_pos;
+            if (last_pass) break;
             continue;
         }
 
@@ -1470,6 +1551,11 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
         // ---- phase 3b: every lane writes the tokens of its own segment: the length of a match is
         // the distance to the next token start (the next mark, or the segment's exit), its distance
         // d0 or d0 + d0[p - d0] out of LDS again, a literal is the byte itself
+        // (in front of the first token store: everything requested for the next pass or the next block has arrived)
+        // (the next block's bytes were requested before any of this, at the top of the block: they are complete
+        // here without a word about them)
+        GZPX_D0_ARRIVED();
+        GZPX_HERE_VGPR(my_ticket);
         {
             uint32_t m = marks, ti = my_tok0;
             while (m) {
@@ -1496,6 +1582,7 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
         mat_carry += tile_mat;
         entry_carry = exit_pos;
         exp_lap(4);
+        if (last_pass) break;
     }
     if (tid == 0 && !handed_back) {
         sub[cur_sub].tok_begin = sub_start_tok;
@@ -1506,26 +1593,20 @@ __global__ __launch_bounds__(kMpThreads, 4) void k_mparse(
         meta->ntok = tok_carry;
         meta->nsub = cur_sub + 1;
     }
-  }  // staged
-    // (a block that was not staged met no barrier in this iteration: without this one, thread 0 could overwrite
-    // s_claimed while a slower wave has not read the previous iteration's value yet -- ADVICE round 4.  Unreachable
-    // today, only a slab's last block can be that short, but the parse must not depend on how batches are cut)
-    if (!staged) __syncthreads();
     if (tid == 0) s_claimed = 2u * gridDim.x + my_ticket;
     if (next_b >= nb) break;  // (tickets only grow: nothing is left for this workgroup either)
-    // (a block handed back in its first pass, or one of a single pass: the next block's d0 is not on its way yet)
-    if (next_staged && !next_d0_requested) GZPX_D0_REQUEST(cand_all + (uint64_t)next_b * cfg.stride, 0u, next_n);
-    // (a stored-only block -- n <= passthrough -- in front of a parsed one did not request its successor's bytes
-    // above; only the last block of a slab can be that short today, so this never fires, but the parse must not
-    // depend on how batches are cut)
-    if (next_staged && !staged) GZPX_BLOCK_REQUEST(next_b, next_n);
     __syncthreads();  // s_claimed is written; everybody is done with this block's LDS
     b = next_b;
     staged = next_staged;
     next_b = s_claimed;
   }
 #undef GZPX_D0_REQUEST
+#undef GZPX_TURN_LATE
+#undef GZPX_D0_NONE
+#undef GZPX_D0_ARRIVED
 #undef GZPX_BLOCK_REQUEST
+#undef GZPX_BLOCK_ARRIVED
+#undef GZPX_HERE_UINT4
 }
 
 // ------------------------------------------------------------------------------------------

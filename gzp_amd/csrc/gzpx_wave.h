@@ -1,5 +1,5 @@
 // gzpx_wave.h -- what more than one stage or more than one header of gzpx_kernels.hip uses: the measurement switch
-// GZPX_EXP and the GZPX_EXPERIMENT counter tables, wave_sync, rdlane / uniform, the two pinning macros,
+// GZPX_EXP and the GZPX_EXPERIMENT counter tables, wave_sync, rdlane / uniform, the pinning macros,
 // load_le32_global, the wave and workgroup scans, dword4, length_entry / build_length_table.  It also brings in the
 // three headers of shared arithmetic, gzpx_policy.h (libdeflate's parsing rules: lz_hash, where a sub-block ends, which
 // matches count), gzpx_deflate.h (with its wave routines, behind wave_sync) and gzpx_crc.h (with its device half,
@@ -48,6 +48,14 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 #define GZPX_PIN_VGPR(x) asm volatile("" : "+v"(x))
 #else
 #define GZPX_PIN_VGPR(x) ((void)0)
+#endif
+
+// a value that a load brings is complete here: the compiler's wait for that load goes in front of this statement and,
+// the register not being written, in front of no later use (the value itself stays what and where it is)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GZPX_HERE_VGPR(x) asm volatile("" ::"v"(x))
+#else
+#define GZPX_HERE_VGPR(x) ((void)0)
 #endif
 
 // last statement of one arm of a branch whose arms end alike: keeps the compiler from sinking the like
